@@ -11,7 +11,13 @@ north_star's "only a final RCCL gather"), so the result transfer is INSIDE the t
 holds all site arrays (400 MB) and scans every N-th block of 4096 test sites of each chromosome: strong scaling, no
 data-path collective, results bitwise independent of N.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4|3|5] [--total-snps T] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4|3|5] [--total-snps T] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, checksum of the last step).
+`--full` adds everything else the line can carry: the cold first pass (end_to_end_*), the roofline figures, the parity
+sample of the last step against the C oracle and the CPU baseline (each of these can still be dropped with its --no-* flag).
+`--dump-outputs DIR` writes the records of the last timed step (a fixed, seeded sample of at most 2^20 windows) as
+DIR/window.npy, clr.npy, lin.npy, nsites.npy (float64), so that two builds can be compared output for output.
 
 `--gpus N` with N > 1 needs no launcher: a parent that never touches the GPU starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
@@ -37,6 +43,8 @@ MEASURED_FMA_STREAM_TFLOPS = 66.6     # pure FP64 FMA stream, 2 waves per SIMD, 
 HBM_PEAK_GBS = 8000.0            # /opt/skills/guides/MI355X_MICROARCH.md (spec; ~6300 achievable)
 SURVEY_FLOP_PER_EVAL = 32        # SURVEY.md 8(d) convention for the reference's FMA + log1p form
 CALIBRATION = os.path.join(REPO, 'profiles', 'r04_pmc_calibration.json')
+DUMP_WINDOWS = 1 << 20           # --dump-outputs: windows written at most (4 float64 arrays: 32 MiB)
+DUMP_SEED = 20240607
 
 
 def parse_args(argv=None):
@@ -55,12 +63,23 @@ def parse_args(argv=None):
                          'can exceed LDS and exercises the R-from-L2 path')
     ap.add_argument('--variant', type=int, default=0)
     ap.add_argument('--step', type=int, default=1, help='test site = every step-th SNP (the reference\'s -s)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-cold-pass', action='store_true', help='no extra (cold) first step before the warm-up steps and no end_to_end_* figures (PMC runs: the '
-                                                                'counters must see exactly the timed step)')
-    ap.add_argument('--no-parity-sample', action='store_true', help='skip the oracle check of 256 windows of the last step (outside the timed region)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the cold pass (end_to_end_*), the roofline figures, the parity sample against the C oracle and the CPU '
+                         'baseline; a plain run measures only the timed steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the records of the last timed step (a fixed, seeded sample of at most %d windows) as DIR/<name>.npy, '
+                         'float64' % DUMP_WINDOWS)
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: no CPU baseline')
+    ap.add_argument('--no-cold-pass', action='store_true', help='--full: no extra (cold) first step before the warm-up steps and no end_to_end_* '
+                                                                'figures (PMC runs: the counters must see exactly the timed step)')
+    ap.add_argument('--no-parity-sample', action='store_true', help='--full: skip the oracle check of 256 windows of the last step (outside the timed region)')
     ap.add_argument('--cpu-seconds', type=float, default=24.0, help='budget of the faithful CPU port (both legs together)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    return args
 
 
 def load_calibration(config, kernel, build_id):
@@ -321,6 +340,45 @@ def parity_sample(chroms, model, spect, props, min_count, xs, ab, As, step, worl
                        'CLR to 1e-6 relative (1e-9 floor); outside the timed region'}
 
 
+def ordered_records(last, layout, sharded, world_size):
+    """The last step's records in window order (chromosome by chromosome, test sites ascending), whatever the number of
+    ranks: `last` holds one record array per rank, `layout` per chromosome the per-rank test-site counts."""
+    import numpy as np
+    from ballermixplus_amd import distributed
+    if world_size == 1 or not sharded:            # one rank, or every rank its own chromosome: already in order
+        return np.concatenate(last)
+    base = [0] * world_size
+    out = []
+    for cnts in layout:
+        parts = distributed.assign(int(sum(cnts)), world_size)
+        g = np.empty(int(sum(cnts)), dtype=last[0].dtype)
+        for r in range(world_size):
+            g[parts[r]] = last[r][base[r]:base[r] + cnts[r]]
+            base[r] += cnts[r]
+        out.append(g)
+    return np.concatenate(out)
+
+
+def dump_sample(total, cap=DUMP_WINDOWS, seed=DUMP_SEED):
+    """Window indices written by --dump-outputs: all of them up to `cap`, else a fixed, seeded sample of `cap`, ascending."""
+    import numpy as np
+    if total <= cap:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total, size=cap, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, rec):
+    """DIR/<name>.npy in float64: window (index in the step's window order), clr, lin (grid index (A*nx + x)*nalpha + alpha,
+    -1 = none) and nsites -- the record fields a caller of the scan receives."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample(len(rec))
+    sel = rec[idx]
+    for name, a in (('window', idx), ('clr', sel['clr']), ('lin', sel['lin']), ('nsites', sel['nsites'])):
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+    return len(idx)
+
+
 class _QuietStdout:
     """RCCL prints a version banner through C stdio on stdout (flushed at exit, i.e. after
     anything Python printed).  The contract is ONE JSON line on stdout, so fd 1 points at stderr
@@ -484,12 +542,13 @@ def _run(args):
             slots.append(ci)
             if plan is None:
                 plan = ctx.plan()
-        if rank == 0:            # algorithmic work of the WHOLE job (all ranks), from a 1/64 sample of the test sites
-            wsum, wmax = window_work(gen, As, zcut, tidx, sample=64 if len(tidx) > 200000 else 1)
+        if rank == 0:
             mult = 1 if sharded else world.size
-            evals_per_step += wsum * len(xs) * len(ab) * mult
-            bytes_per_step += (wmax * 10.0 + 24.0 * len(tidx)) * mult      # W_max*10 B + 24 B per window
             windows_per_step += len(tidx) * mult
+            if args.full:        # algorithmic work of the WHOLE job (all ranks), from a 1/64 sample of the test sites
+                wsum, wmax = window_work(gen, As, zcut, tidx, sample=64 if len(tidx) > 200000 else 1)
+                evals_per_step += wsum * len(xs) * len(ab) * mult
+                bytes_per_step += (wmax * 10.0 + 24.0 * len(tidx)) * mult      # W_max*10 B + 24 B per window
     t_plan = time.time() - t_plan
     stream_bytes = 0
     for ci in slots:
@@ -559,9 +618,9 @@ def _run(args):
         return got
 
     # ---- the COLD pass: everything above that a caller of the C ABI pays once per genome (t_abi) plus the FIRST step on the fresh
-    # context (scans + result transfer, first-touch costs included); untimed, before the warm-up steps
+    # context (scans + result transfer, first-touch costs included); untimed, before the warm-up steps; --full only
     t_cold, cold = None, None
-    if not args.no_cold_pass:
+    if args.full and not args.no_cold_pass:
         barrier()
         t0 = time.perf_counter()
         cold = one_step()
@@ -593,16 +652,11 @@ def _run(args):
 
     if rank == 0:
         checksum = float(sum(float(np.sum(g['clr'])) for g in last))
-        cold_same = cold is not None and all(np.array_equal(a, b) for a, b in zip(last, cold))
         nrec = int(sum(len(g) for g in last))
         k_step_s = k_total / args.steps * 1e-3                     # scan kernels of one step (slowest rank)
         windows = float(windows_per_step) * args.steps
-        evals_s = evals_per_step / k_step_s
         kname = plan['kernel'] if plan else 'none'
         build_id = _lib.lib().bmx_build_id().decode()
-        cal_key = 'config%d' % args.config + ('_step%d' % args.step if args.step != 1 else '') + \
-                  ('_nspread%d' % args.n_spread if args.n_spread else '')
-        cal, why = load_calibration(cal_key, kname, build_id)
         nchrom = len(chroms)
         workload = {
             4: 'BASELINE config 4: synthetic whole genome, %d SNPs over %d chromosomes (GRCh37 proportions), n=%d, default '
@@ -623,7 +677,7 @@ def _run(args):
             'n_gpus': world.size, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': dt / args.steps * 1e3,
             'higher_is_better': True, 'scaling': 'strong' if sharded else 'weak', 'vs_baseline': None,
-            'dtype': 'f64', 'data': 'synthetic', 'argv': sys.argv[1:],
+            'dtype': 'f64', 'data': 'synthetic', 'argv': sys.argv[1:], 'full': args.full,
             'config': {'workload': workload, 'windows_per_step': windows_per_step, 'launches_per_step': len(slots),
                        'grid_points': len(As) * len(xs) * len(ab),
                        'parallelism': ('test-site sharding, dp%d; one context per GPU holds every chromosome; ONE gather of all 16-B records '
@@ -634,19 +688,29 @@ def _run(args):
                        'kernel_ms_per_step': k_step_s * 1e3,
                        'records_per_step': nrec,
                        'checksum_clr': checksum,
-                       'end_to_end_windows_per_s': windows_per_step / t_cold if t_cold else None,
-                       'end_to_end_seconds': t_cold,
-                       'end_to_end_phases_rank0': {k_: round(v_, 4) for k_, v_ in phases.items()} if t_cold else None,
-                       'end_to_end_note': 'the COLD pass of this run, outside the timed steps: from host buffers through the calls a user of the C '
-                                          'ABI makes once per genome -- context creation, table build (K1), H2D of all site arrays and test sites, '
-                                          'test-site location + planning / counting pass (wall clock inside those calls) -- plus the FIRST step on '
-                                          'the fresh context: the scans and the result records to the host (N > 1: the gather); slowest rank; records '
-                                          'bitwise equal to the timed steps\': %s' % cold_same,
                        'input_sha256': digest.hexdigest(),
                        'library_build': build_id,
                        'plan_seconds_outside_timed_region': t_plan,
                        'prepared_stream_bytes_per_window': stream_bytes / max(mine_total, 1)},
-            'roofline': {
+        }
+        if args.dump_outputs:
+            res['dumped_windows'] = dump_outputs(args.dump_outputs, ordered_records(last, layout, sharded, world.size))
+        if args.full:
+            cold_same = cold is not None and all(np.array_equal(a, b) for a, b in zip(last, cold))
+            res['config'].update({
+                'end_to_end_windows_per_s': windows_per_step / t_cold if t_cold else None,
+                'end_to_end_seconds': t_cold,
+                'end_to_end_phases_rank0': {k_: round(v_, 4) for k_, v_ in phases.items()} if t_cold else None,
+                'end_to_end_note': 'the COLD pass of this run, outside the timed steps: from host buffers through the calls a user of the C '
+                                   'ABI makes once per genome -- context creation, table build (K1), H2D of all site arrays and test sites, '
+                                   'test-site location + planning / counting pass (wall clock inside those calls) -- plus the FIRST step on '
+                                   'the fresh context: the scans and the result records to the host (N > 1: the gather); slowest rank; records '
+                                   'bitwise equal to the timed steps\': %s' % cold_same})
+            evals_s = evals_per_step / k_step_s
+            cal_key = 'config%d' % args.config + ('_step%d' % args.step if args.step != 1 else '') + \
+                      ('_nspread%d' % args.n_spread if args.n_spread else '')
+            cal, why = load_calibration(cal_key, kname, build_id)
+            res['roofline'] = {
                 'bound': 'valu_fp64', 'kernel': kname,
                 'peak': FP64_VALU_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'traffic': None, 'achieved': None, 'frac': None,
                 'kernel_ms': k_step_s * 1e3 / max(len(slots), 1), 'launches': len(slots),
@@ -662,55 +726,54 @@ def _run(args):
                         'kernel_ms: HIP events around each chromosome\'s launches (per-group preparation kernel + scan kernel + finalize) on the '
                         'library\'s stream. Algorithmic work: evals_per_s mixture-likelihood evaluations; under SURVEY 8(d) '
                         '"1 evaluation = 32 flop" that is survey_convention_tflops, above the peak because near sites are multiplied four '
-                        'per step in product form and far sites are summed as moments.'},
-            'roofline_hbm': {
+                        'per step in product form and far sites are summed as moments.'}
+            res['roofline_hbm'] = {
                 'bound': 'hbm', 'kernel': kname,
                 'achieved': bytes_per_step / k_step_s / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                 'frac': bytes_per_step / k_step_s / 1e9 / HBM_PEAK_GBS, 'traffic': None,
-                'algorithmic_bytes_per_step': bytes_per_step},
-        }
-        if cal:
-            r = res['roofline']
-            r['fp64_flops_per_eval'] = cal['fp64_flops_per_eval']
-            r['achieved'] = evals_s * cal['fp64_flops_per_eval'] / 1e12          # FP64 flop actually executed per second
-            r['frac'] = r['achieved'] / FP64_VALU_PEAK_TFLOPS
-            r['fp64_tflops'], r['fp64_flops_frac'] = r['achieved'], r['frac']    # (the names round 3's line used)
-            r['valu_insts_per_64_evals'] = cal['valu_per_64_evals']
-            r['valu_issue_tflops_equiv'] = evals_s * cal['valu_per_64_evals'] * 128 / 64 / 1e12
-            r['valu_issue_frac'] = r['valu_issue_tflops_equiv'] / FP64_VALU_PEAK_TFLOPS
-            # what a pure v_fma_f64 stream reaches on this chip at two waves per SIMD (scripts/ubench_dep.hip: 4.45 cycles per
-            # instruction at a core clock that falls to 2.26 GHz under it; profiles/r04_ubench_dependent_fp64.txt) -- context for
-            # `frac`, which stays against the nominal peak
-            r['measured_fma_stream_tflops'] = MEASURED_FMA_STREAM_TFLOPS
-            r['frac_of_measured_fma_stream'] = r['achieved'] / MEASURED_FMA_STREAM_TFLOPS
-            r['calibration'] = cal['source']
-            # HBM traffic of one average launch, from the PMC counters per window (FETCH_SIZE doubled as the guide
-            # prescribes for gfx950, WRITE_SIZE as read)
-            per_launch_windows = windows_per_step / max(len(slots), 1)
-            per_window = cal['hbm_read_bytes_per_window'] + cal['hbm_write_bytes_per_window']
-            r['traffic'] = res['roofline_hbm']['traffic'] = per_window * per_launch_windows
-            res['roofline_hbm']['measured_hbm_gbs'] = per_window * windows_per_step / k_step_s / 1e9
-        else:
-            res['roofline']['calibration_warning'] = why
-        if not args.no_parity_sample and not args.n_spread:
-            try:
-                ps = parity_sample(chroms, model, spect, props, min_count, xs, ab, As, args.step, world.size, layout, last)
-                res['parity_sample'] = ps
-                res['parity_sample_max_rel'] = ps['max_rel']
-                if ps['mismatches']:
-                    res['parity_sample_FAILED'] = True
-                    sys.stderr.write('bench.py: PARITY SAMPLE FAILED: %r\n' % (ps['first_mismatches'],))
-            except Exception as e:
-                res['parity_sample'] = {'error': repr(e)[:500]}
-        if not args.no_cpu_baseline and world.size == 1:      # reported baseline: rank 0, N = 1 only
-            specs = [(int(Nc), int(n), int(cid), spect, props, min_count, args.config == 5) for cid, Nc in zip(chrom_ids, sizes_c)]
-            if args.n_spread:
-                res['cpu_baseline'] = {'skipped': 'not defined for --n-spread runs (the recipe of the thinned sample sizes is not shared with the workers)'}
+                'algorithmic_bytes_per_step': bytes_per_step}
+            if cal:
+                r = res['roofline']
+                r['fp64_flops_per_eval'] = cal['fp64_flops_per_eval']
+                r['achieved'] = evals_s * cal['fp64_flops_per_eval'] / 1e12          # FP64 flop actually executed per second
+                r['frac'] = r['achieved'] / FP64_VALU_PEAK_TFLOPS
+                r['fp64_tflops'], r['fp64_flops_frac'] = r['achieved'], r['frac']    # (the names round 3's line used)
+                r['valu_insts_per_64_evals'] = cal['valu_per_64_evals']
+                r['valu_issue_tflops_equiv'] = evals_s * cal['valu_per_64_evals'] * 128 / 64 / 1e12
+                r['valu_issue_frac'] = r['valu_issue_tflops_equiv'] / FP64_VALU_PEAK_TFLOPS
+                # what a pure v_fma_f64 stream reaches on this chip at two waves per SIMD (scripts/ubench_dep.hip: 4.45 cycles per
+                # instruction at a core clock that falls to 2.26 GHz under it; profiles/r04_ubench_dependent_fp64.txt) -- context for
+                # `frac`, which stays against the nominal peak
+                r['measured_fma_stream_tflops'] = MEASURED_FMA_STREAM_TFLOPS
+                r['frac_of_measured_fma_stream'] = r['achieved'] / MEASURED_FMA_STREAM_TFLOPS
+                r['calibration'] = cal['source']
+                # HBM traffic of one average launch, from the PMC counters per window (FETCH_SIZE doubled on gfx950,
+                # WRITE_SIZE as read)
+                per_launch_windows = windows_per_step / max(len(slots), 1)
+                per_window = cal['hbm_read_bytes_per_window'] + cal['hbm_write_bytes_per_window']
+                r['traffic'] = res['roofline_hbm']['traffic'] = per_window * per_launch_windows
+                res['roofline_hbm']['measured_hbm_gbs'] = per_window * windows_per_step / k_step_s / 1e9
             else:
+                res['roofline']['calibration_warning'] = why
+            if not args.no_parity_sample and not args.n_spread:
                 try:
-                    res['cpu_baseline'] = cpu_baseline(specs, sizes_c, args.cpu_seconds)
-                except Exception as e:       # the GPU measurement above stands on its own: say what went wrong with the baseline leg
-                    res['cpu_baseline'] = {'error': repr(e)[:500]}
+                    ps = parity_sample(chroms, model, spect, props, min_count, xs, ab, As, args.step, world.size, layout, last)
+                    res['parity_sample'] = ps
+                    res['parity_sample_max_rel'] = ps['max_rel']
+                    if ps['mismatches']:
+                        res['parity_sample_FAILED'] = True
+                        sys.stderr.write('bench.py: PARITY SAMPLE FAILED: %r\n' % (ps['first_mismatches'],))
+                except Exception as e:
+                    res['parity_sample'] = {'error': repr(e)[:500]}
+            if not args.no_cpu_baseline and world.size == 1:      # reported baseline: rank 0, N = 1 only
+                specs = [(int(Nc), int(n), int(cid), spect, props, min_count, args.config == 5) for cid, Nc in zip(chrom_ids, sizes_c)]
+                if args.n_spread:
+                    res['cpu_baseline'] = {'skipped': 'not defined for --n-spread runs (the recipe of the thinned sample sizes is not shared with the workers)'}
+                else:
+                    try:
+                        res['cpu_baseline'] = cpu_baseline(specs, sizes_c, args.cpu_seconds)
+                    except Exception as e:       # the GPU measurement above stands on its own: say what went wrong with the baseline leg
+                        res['cpu_baseline'] = {'error': repr(e)[:500]}
         line = json.dumps(res)
     else:
         line = None

@@ -9,7 +9,7 @@ R=$(pwd)
 OUT=$R/gpurun_out/${ROUND:-r04}/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$* --steps 1 --warmup 0 --no-cpu-baseline --no-cold-pass --no-parity-sample"
+ARGS="$* --steps 1 --warmup 0 --full --no-cpu-baseline --no-cold-pass --no-parity-sample"
 pass() {   # name, counters...
   local name=$1; shift
   rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -- python3 $R/bench.py $ARGS > $OUT/$name.json 2> $OUT/$name.err

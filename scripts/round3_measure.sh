@@ -4,12 +4,12 @@ R=$(pwd)
 O=$R/gpurun_out/r03
 mkdir -p $O
 if [ "$1" = "A" ]; then
-  timeout 900 python bench.py > $O/bench_1gpu.json 2> $O/bench_1gpu.err
-  timeout 600 python bench.py --config 3 --no-cpu-baseline > $O/bench_1gpu_config3.json 2>/dev/null
-  timeout 900 python bench.py --config 5 --no-cpu-baseline > $O/bench_1gpu_config5.json 2>/dev/null
-  timeout 600 python bench.py --config 3 --n-spread 10 --no-cpu-baseline > $O/bench_1gpu_config3_11_sample_sizes.json 2>/dev/null
-  timeout 600 python bench.py --config 3 --n-spread 40 --no-cpu-baseline > $O/bench_1gpu_config3_41_sample_sizes.json 2>/dev/null
-  timeout 600 python bench.py --config 3 --snps 4000000 --step 64 --no-cpu-baseline > $O/bench_1gpu_config3_step64.json 2>/dev/null
+  timeout 900 python bench.py --full > $O/bench_1gpu.json 2> $O/bench_1gpu.err
+  timeout 600 python bench.py --config 3 --no-cpu-baseline --full > $O/bench_1gpu_config3.json 2>/dev/null
+  timeout 900 python bench.py --config 5 --no-cpu-baseline --full > $O/bench_1gpu_config5.json 2>/dev/null
+  timeout 600 python bench.py --config 3 --n-spread 10 --no-cpu-baseline --full > $O/bench_1gpu_config3_11_sample_sizes.json 2>/dev/null
+  timeout 600 python bench.py --config 3 --n-spread 40 --no-cpu-baseline --full > $O/bench_1gpu_config3_41_sample_sizes.json 2>/dev/null
+  timeout 600 python bench.py --config 3 --snps 4000000 --step 64 --no-cpu-baseline --full > $O/bench_1gpu_config3_step64.json 2>/dev/null
   timeout 900 python scripts/e2e_timing.py > $O/cli_end_to_end_1M.txt 2>&1
   timeout 1500 python scripts/config4_cli_pipeline.py > $O/config4_file_pipeline_1gpu.txt 2>&1
   for f in $O/bench_1gpu*.json; do python -c "
@@ -23,7 +23,7 @@ else
   PMC_KEY=config3_nspread40 bash scripts/pmc_collect.sh c3ns40 --config 3 --n-spread 40 > $O/pmc_c3ns40.log 2>&1
   PMC_KEY=config3_nspread10 bash scripts/pmc_collect.sh c3ns10 --config 3 --n-spread 10 > $O/pmc_c3ns10.log 2>&1
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/stats_bench.json 2> $O/stats_bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --full > $O/stats_bench.json 2> $O/stats_bench.err
   cd $R
   find $O/stats -name "*kernel_stats.csv" | xargs cat | cut -c1-220 | head -12
   for t in c3 c4 c5 c3s64 c3ns40 c3ns10; do head -1 $O/$t/summary.txt | cut -c1-300; grep -E "valu_per_64|cycles_per_valu|hbm_read|hbm_write|l2_hit" $O/$t/summary.txt; done

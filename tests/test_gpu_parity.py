@@ -48,7 +48,7 @@ def test_device_selection_table_matches_reference(path):
     ctx.close()
 
 
-def _run_case(name):
+def _run_case(name, tmp_path):
     eng = _engine()
     from ballermixplus_amd import scan as scanmod
     argv, gold = cases.ALL_CASES[name]
@@ -56,7 +56,7 @@ def _run_case(name):
     sel = eng.NormalizedBetaBinom(case.data, case.grid, opt.nofreq, opt.MAF, opt.nosub)
     sel.bind(case.neut)
     res = eng.scan_batch(sel, ts.test_gen, ts.lo, ts.hi)
-    out = '/tmp/bmx_gpu_%s.tsv' % name
+    out = str(tmp_path / ('bmx_gpu_%s.tsv' % name))
     scanmod.write_rows(out, ts, res, sel)
     with open(out) as f:
         lines = f.readlines()[1:]
@@ -64,11 +64,11 @@ def _run_case(name):
 
 
 @pytest.mark.parametrize('name', sorted(cases.ALL_CASES))
-def test_scan_reproduces_golden_file(name):
+def test_scan_reproduces_golden_file(name, tmp_path):
     """Every row of every golden output file (configs 1 and 2 of BASELINE.json among them)."""
     if not os.path.exists(cases.ALL_CASES[name][1]):
         pytest.skip('fixture not generated')
-    case, ts, lines, gold = _run_case(name)
+    case, ts, lines, gold = _run_case(name, tmp_path)
     worst, ties = cases.compare_rows(lines, gold, rtol=1e-6, case=case, ts=ts)
     assert worst < 1e-6
     assert ties == 0 or name.endswith('B1'), ties

@@ -280,7 +280,7 @@ def test_cli_two_ranks_on_one_gpu_write_the_single_rank_file(tmp_path):
     assert r.returncode != 0 and '--device cannot be combined' in r.stdout + r.stderr
 
 
-def test_bench_contract_two_ranks_on_one_gpu():
+def test_bench_contract_two_ranks_on_one_gpu(tmp_path):
     """PLAIN `python bench.py --gpus 2 ...` -- no launcher: the parent, which never touches the GPU, starts the two ranks itself
     (torch.distributed.run as a child) and relays their one JSON line.  Default workload (config 4, here a 1/100 genome), two
     ranks sharing this box's one GPU (gloo gather through the host instead of RCCL): exit code 0, exactly ONE JSON line on
@@ -290,8 +290,8 @@ def test_bench_contract_two_ranks_on_one_gpu():
     env = dict(os.environ, BMX_DIST_BACKEND='gloo', BMX_SINGLE_DEVICE='1')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    common = ['--steps', '2', '--warmup', '1', '--total-snps', '400000', '--no-cpu-baseline']
-    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2'] + common,
+    common = ['--steps', '2', '--warmup', '1', '--total-snps', '400000', '--no-cpu-baseline', '--full']
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2'] + common + ['--dump-outputs', str(tmp_path / 'two')],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -306,12 +306,17 @@ def test_bench_contract_two_ranks_on_one_gpu():
     for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic'):
         assert k in d['roofline']
     assert 'cpu_baseline' not in d            # reported at N = 1 only
-    r1 = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + common, capture_output=True, text=True, timeout=600, env=env)
+    r1 = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + common + ['--dump-outputs', str(tmp_path / 'one')],
+                        capture_output=True, text=True, timeout=600, env=env)
     assert r1.returncode == 0, r1.stderr[-2000:]
     d1 = json.loads([l for l in r1.stdout.splitlines() if l.strip()][-1])
     assert d1['n_gpus'] == 1 and d1['config']['records_per_step'] == W
     assert d1['config']['checksum_clr'] == pytest.approx(d['config']['checksum_clr'], rel=1e-12)    # same rows, summed in another order
     assert d1['config']['input_sha256'] == d['config']['input_sha256']
+    # --dump-outputs puts the records in window order whatever the number of ranks: both runs write the same arrays
+    assert d['dumped_windows'] == d1['dumped_windows'] == W
+    for name in ('window', 'clr', 'lin', 'nsites'):
+        assert np.array_equal(np.load(tmp_path / 'two' / (name + '.npy')), np.load(tmp_path / 'one' / (name + '.npy'))), name
     print('bench step: 2 ranks on one GPU %.1f ms, 1 rank %.1f ms (ratio %.3f)' % (d['ms_per_step'], d1['ms_per_step'], d['ms_per_step'] / d1['ms_per_step']))
     assert d['ms_per_step'] < 1.25 * d1['ms_per_step']
 

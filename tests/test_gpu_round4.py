@@ -157,11 +157,8 @@ def test_config5_every_contig_against_the_oracle():
     assert worst < 1e-6
 
 
-def test_native_rccl_gather_with_one_rank():
-    """bmx_comm_*: the library's own RCCL communicator (librccl.so through dlopen, ncclCommInitRank on the context's device) and
-    ONE gather of the packed records of two chromosome slots -- with a single rank the group holds no send / receive, the path
-    through ncclGroupStart / ncclGroupEnd, the packing into the receive buffer and the copy to the host is the same one N ranks
-    take.  (N > 1 needs N GPUs: RCCL refuses two ranks on one device.  Not run on this 1-GPU box.)"""
+def _native_rccl_gather_checks():
+    """The body of test_native_rccl_gather_with_one_rank, run in a process of its own."""
     from ballermixplus_amd import _lib, engine as eng, synth
     from ballermixplus_amd.hostmodel import Grids
     xs, ab, As = Grids(None, None, False, False, None, None).scan_order()
@@ -191,6 +188,23 @@ def test_native_rccl_gather_with_one_rank():
     ctx.close()
 
 
+def test_native_rccl_gather_with_one_rank():
+    """bmx_comm_*: the library's own RCCL communicator (librccl.so through dlopen, ncclCommInitRank on the context's device) and
+    ONE gather of the packed records of two chromosome slots -- with a single rank the group holds no send / receive, the path
+    through ncclGroupStart / ncclGroupEnd, the packing into the receive buffer and the copy to the host is the same one N ranks
+    take.  (N > 1 needs N GPUs: RCCL refuses two ranks on one device.  Not run on this 1-GPU box.)
+    The checks run in a fresh process, as a rank does: in the test process the library is loaded before anything imports
+    torch, and a test that imports torch later brings torch's own librccl.so.1 and HIP runtime into it; dlopen("librccl.so.1")
+    would then return torch's copy, bound to a HIP runtime this process never initialised (ncclCommInitRank: "no
+    ROCm-capable device is detected")."""
+    import subprocess
+    from util import HERE
+    r = subprocess.run([sys.executable, '-c', 'import sys; sys.path.insert(0, sys.argv[1]); import test_gpu_round4 as t; '
+                        't._native_rccl_gather_checks(); print("native gather ok")', HERE],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and 'native gather ok' in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
+
+
 def test_bench_step_through_the_native_gather():
     """bench.py with BMX_NATIVE_GATHER=1 and the process group forced on for a single rank: every step's records go through
     bmx_comm_gather_records (the library's own ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd path) instead of
@@ -201,7 +215,8 @@ def test_bench_step_through_the_native_gather():
     env = dict(os.environ, BMX_FORCE_DIST='1', BMX_NATIVE_GATHER='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29673')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'BMX_DIST_BACKEND', 'BMX_SINGLE_DEVICE'):
         env.pop(k, None)
-    common = [sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--total-snps', '400000', '--no-cpu-baseline']
+    common = [sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--total-snps', '400000', '--no-cpu-baseline',
+              '--full']
     r = subprocess.run(common, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
