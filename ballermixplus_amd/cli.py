@@ -10,6 +10,9 @@ Additions (do not change any reference command line):
                     (created; outputs are <dir>/<input basename>.out.txt) or a pattern containing {} (replaced by the
                     input's basename without extension).  The reference handles one file per process
                     (BalLeRMix+_v1.py:777-799); looping it pays process start, HIP start-up and the table once per file.
+  --nullPerm R [--nullSeed S] [--nullBlock B]     permutation null (ballermixplus_amd/null.py): after the observed scan of
+                    each file, R more scans with the sites' (k, n) rows permuted on the device; writes <out>.null.txt (several
+                    files: <dir>/null.txt or the -o pattern with `null`) and <out>.pval.txt next to each output file.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -19,6 +22,8 @@ import argparse
 import os
 import sys
 from datetime import datetime
+
+import numpy as np
 
 
 def build_parser():
@@ -71,7 +76,62 @@ def build_parser():
                              'equivalent to -i a.txt,b.txt,...; -o is then a directory or a pattern containing {}')
     parser.add_argument('--device', dest='device', type=int, default=None,
                         help='GPU index for a single-process run (MI355X build only; not allowed under torch.distributed.run, where every rank uses GPU LOCAL_RANK)')
+    parser.add_argument('--nullPerm', dest='nullPerm', type=int, default=0,
+                        help='MI355X build only: R > 0 scans every input R more times with the sites\' (k, n) labels permuted within '
+                             'the chromosome and writes <out>.null.txt (maximum CLR of every replicate) and <out>.pval.txt '
+                             '(pointwise and genome-wide p-value of every window); default 0: off')
+    parser.add_argument('--nullSeed', dest='nullSeed', type=int, default=1,
+                        help='MI355X build only: seed of the --nullPerm permutations (default 1)')
+    parser.add_argument('--nullBlock', dest='nullBlock', type=int, default=1,
+                        help='MI355X build only: --nullPerm moves blocks of this many consecutive sites intact (default 1: single sites)')
     return parser
+
+
+def null_refusal(opt):
+    """The message that refuses a --nullPerm command line, or None when it can run."""
+    if not opt.nullPerm:
+        return None
+    if opt.nullPerm < 0:
+        return '--nullPerm takes a number of replicates >= 1 (0: off).'
+    if opt.nullBlock < 1:
+        return '--nullBlock must be >= 1.'
+    if opt.getSpec or opt.getConfig:
+        return '--nullPerm scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if not opt.outfile:
+        return '--nullPerm needs -o: the null and p-value files are written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--nullPerm runs in a single process; multi-rank launches are not supported.'
+    return None
+
+
+def null_name(outspec, what):
+    """<out>.null.txt of a one-file run; for several files <dir>/null.txt, or the -o pattern with `null` for {}."""
+    return outspec.replace('{}', what) if '{}' in outspec else os.path.join(outspec, what + '.txt')
+
+
+def finish_null(opt, per_file, null_path, say):
+    """per_file: (outfile, test sites, observed clr, iA, counts, maxima[R]) of every file.  The genome-wide maximum of a
+    replicate is the maximum over the files; writes the null file and one p-value file per output file."""
+    from . import null
+    R = opt.nullPerm
+    gmax = np.full(R, -np.inf)
+    for rec in per_file:
+        gmax = np.maximum(gmax, rec[5])
+    null.write_null(null_path, gmax)
+    for outfile, ts, clr, iA, counts, _ in per_file:
+        null.write_pval(outfile + '.pval.txt', ts, clr, iA, counts, gmax)
+    say(f'\n{datetime.now()}. Permutation null: {R} replicates (seed {opt.nullSeed}, blocks of {opt.nullBlock} site/s) -> {null_path}')
+    say('Genome-wide CLR threshold, 5%% level: %r' % null.threshold(gmax, 0.95))
+    say('Genome-wide CLR threshold, 1%% level: %r' % null.threshold(gmax, 0.99))
+
+
+def null_of_file(opt, ctx, ts, f):
+    """The null replicates of one file whose observed scan has just run on ctx's selected slot."""
+    from . import null
+    if len(ts) == 0:
+        z = np.zeros(0)
+        return z, z.astype(np.int32), z.astype(np.int32), np.full(opt.nullPerm, -np.inf)
+    return null.run_file(ctx, opt.nullPerm, opt.nullSeed, opt.nullBlock, f)
 
 
 def main(argv=None):
@@ -87,6 +147,10 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
+    refused = null_refusal(opt)
+    if refused:
+        print(refused)
+        sys.exit(1)
     files = None
     if opt.inputs is not None:
         if opt.getSpec or opt.getConfig:
@@ -160,9 +224,13 @@ def main(argv=None):
     # BMX_SHARD_BLOCK: test sites per shard block (default distributed.BLOCK = 4096; a multiple of 16 keeps every window's
     # arithmetic independent of the number of ranks) -- lets small inputs exercise real sharding in the tests
     runner = world.sharded_runner(block=shard_block(), balance=os.environ.get('BMX_SHARD_BALANCE') == '1') if world.distributed else None
-    Scan(data, Neutral, Sel_Probs, grid, opt.outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w,
-         s=opt.step, phys=opt.phys, noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False)
+    sc = Scan(data, Neutral, Sel_Probs, grid, opt.outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w,
+              s=opt.step, phys=opt.phys, noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False)
     stamp('table, scan, output')
+    if opt.nullPerm:
+        got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
+        finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
+        stamp('permutation null')
     world.finish()
     say(f'\n{datetime.now()}. Pipeline finished.')
 
@@ -256,6 +324,7 @@ def main_many(opt, files, stamp=lambda what: None):
     ctx = engine.Context(device)        # HIP start-up (0.2-0.3 s) while the first file is being read
     tables = 0
     kernel_ms = 0.0
+    null_files = []
     for i, (infile, outfile) in enumerate(zip(files, outs)):
         th.join()
         got = nxt.pop(i)
@@ -266,8 +335,8 @@ def main_many(opt, files, stamp=lambda what: None):
             th = threading.Thread(target=host_stage, args=(i + 1,))
             th.start()
         say(f"\n{datetime.now()}. {infile} -> {outfile}")
-        Scan(data, neut, sel, grid, outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w, s=opt.step, phys=opt.phys,
-             noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False, reuse_ctx=ctx)
+        sc = Scan(data, neut, sel, grid, outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w, s=opt.step, phys=opt.phys,
+                  noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False, reuse_ctx=ctx)
         ctx = sel.ctx
         tables += 0 if sel.table_reused else 1
         try:
@@ -275,6 +344,13 @@ def main_many(opt, files, stamp=lambda what: None):
         except Exception:           # a file without test sites
             pass
         stamp('file %d of %d' % (i + 1, len(files)))
+        if opt.nullPerm:
+            # per-file permutations are independent (key of file ordinal i): only the host copies of this file's observed
+            # CLR and counts stay until the genome-wide maxima are known
+            null_files.append((outfile, sc.test_sites) + null_of_file(opt, ctx, sc.test_sites, i))
+            stamp('file %d of %d: permutation null' % (i + 1, len(files)))
+    if opt.nullPerm:
+        finish_null(opt, null_files, null_name(opt.outfile, 'null'), say)
     world.finish()
     say(f'\n{datetime.now()}. Pipeline finished: {len(files)} files, selection table built {tables} time(s), '
         f'scan kernels {kernel_ms / 1e3:.2f} s.')

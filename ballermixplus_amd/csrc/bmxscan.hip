@@ -278,6 +278,86 @@ __global__ void gap_kernel(const int64_t *center, int64_t stride, int64_t ns, in
     gap[k] = center[k * stride + 1] - center[k * stride];
 }
 
+// ----------------------------------------------------------------------------- permutation null
+// splitmix64: the mixer of the permutation and of its keys (ballermixplus_amd/null.py mix, bitwise)
+__host__ __device__ __forceinline__ uint64_t bmx_mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// sigma(i; N, B, K) of null.block_permutation: blocks of B sites permuted by an 8-round Feistel network on 2h bits with
+// cycle walking (only the first nb * B sites move; nb < 2 is the identity and never launches)
+struct PermParams {
+    int64_t N, B, nb;
+    int h;
+    uint64_t mask;
+    uint64_t rk[8];        // mix(K + j), j = 0..7: the round keys, made on the host
+};
+
+__device__ __forceinline__ uint64_t feistel(uint64_t x, const PermParams &Q) {
+    uint64_t L = x >> Q.h, R = x & Q.mask;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint64_t t = R;
+        R = L ^ (bmx_mix64(R ^ Q.rk[j]) & Q.mask);
+        L = t;
+    }
+    return (L << Q.h) | R;
+}
+
+// dst[i] = src[sigma(i)]: positions stay, the (k, n) rows move; grid-stride over the N sites
+template <class T>
+__global__ __launch_bounds__(256) void permute_rows_kernel(const T *__restrict__ src, T *__restrict__ dst, PermParams Q) {
+    const int64_t moved = Q.nb * Q.B;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < Q.N; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t j = i;
+        if (i < moved) {
+            const int64_t b = i / Q.B;
+            uint64_t x = feistel((uint64_t)b, Q);
+            while (x >= (uint64_t)Q.nb) x = feistel(x, Q);      // a cycle of the permutation leads back into [0, nb)
+            j = (int64_t)x * Q.B + (i - b * Q.B);
+        }
+        dst[i] = src[j];
+    }
+}
+
+constexpr int NULL_THREADS = 256;
+constexpr int NULL_BLOCKS_MAX = 1024;
+
+__device__ __forceinline__ double block_max(double m) {
+    __shared__ double wmax[NULL_THREADS / WAVE];
+    for (int o = WAVE / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    if ((threadIdx.x & (WAVE - 1)) == 0) wmax[threadIdx.x / WAVE] = m;
+    __syncthreads();
+    m = wmax[0];
+    for (int w = 1; w < NULL_THREADS / WAVE; w++) m = fmax(m, wmax[w]);
+    return m;
+}
+
+// one replicate's exceedances (every test site is one thread's: no atomics) and the first pass of its maximum CLR: one
+// partial per workgroup
+__global__ __launch_bounds__(NULL_THREADS) void null_count_kernel(const double *__restrict__ clr, const double *__restrict__ obs,
+                                                                  int32_t *__restrict__ count, int64_t M, double *__restrict__ part) {
+    double m = -INFINITY;
+    for (int64_t t = (int64_t)blockIdx.x * NULL_THREADS + threadIdx.x; t < M; t += (int64_t)gridDim.x * NULL_THREADS) {
+        const double v = clr[t];
+        count[t] += v >= obs[t] ? 1 : 0;
+        m = fmax(m, v);
+    }
+    m = block_max(m);
+    if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+
+// second pass: the maximum of the n workgroup partials (max is exact, so the result does not depend on the split)
+__global__ __launch_bounds__(NULL_THREADS) void null_max_kernel(const double *__restrict__ part, int n, double *__restrict__ out) {
+    double m = -INFINITY;
+    for (int k = threadIdx.x; k < n; k += NULL_THREADS) m = fmax(m, part[k]);
+    m = block_max(m);
+    if (threadIdx.x == 0) *out = m;
+}
+
 // LUT row of a site: 2 bytes per site normally (<= 65535 rows), 4 when the table is larger
 // (hundreds of distinct sample sizes).
 struct RowArray {
@@ -3289,9 +3369,21 @@ struct ChromSlot {
     DevBuf<int32_t> blob_units;
     DevBuf<int64_t> blob_prefix;
     std::vector<PrepRange> ranges;
+    uint64_t scan_seq = 0;       // scans launched in this slot (the null's accumulate takes each replicate's scan once)
+    // permutation null: the rows given to set_sites while the row arrays hold a permutation of them (bmx_ctx_permute_rows) ...
+    bool has_orig = false;
+    DevBuf<uint16_t> orig16;
+    DevBuf<uint32_t> orig32;
+    // ... and the null's state (bmx_ctx_null_begin): observed CLR, exceedance counts, workgroup maxima, replicates so far
+    bool null_ok = false;
+    uint64_t null_seq = 0;       // scan_seq at null_begin / the last accumulate
+    int32_t null_reps = 0;
+    DevBuf<double> null_obs, null_part;
+    DevBuf<int32_t> null_cnt;
 
     void release() {
         genpos.release(); rowmax.release(); rowthr.release(); row16.release(); row32.release(); kmom.release(); d_row_of_slot.release();
+        orig16.release(); orig32.release(); null_obs.release(); null_part.release(); null_cnt.release();
         test_gen.release(); win_lo.release(); win_hi.release(); center.release(); center_hi.release();
         clr.release(); lin.release(); nsites.release(); rec.release();
         blob_units.release(); blob_prefix.release();
@@ -3352,9 +3444,11 @@ void drop_tests(ChromSlot *s) {
     s->timed = false;       // results belong to the test sites they were computed for
     s->plan_ok = false;
     s->prep_ok = false;
+    s->null_ok = false;     // the observed CLR and the counts belong to those test sites
 }
 void drop_sites(ChromSlot *s) {
     s->has_sites = false;
+    s->has_orig = false;    // new rows: nothing is permuted
     drop_tests(s);          // test sites were located in the old site array
 }
 
@@ -4043,7 +4137,11 @@ int ensure_prep(bmx_ctx *c, ChromSlot *s) {
         need = std::max(need, units);
         g0 = g1;
     }
-    HIP_TRY(c->arena.ensure((size_t)need + 8 * WAVE));     // the consumers' read-ahead runs up to five chunks past a blob's end
+    // the consumers' read-ahead runs up to five chunks past a blob's end.  A slot with permuted rows (permutation null) is
+    // prepared again for every replicate and its stream size varies a little with the permutation: an arena that has to grow
+    // then takes an eighth more, so that it is not re-allocated replicate after replicate (~0.4 s each at 1 M test sites)
+    const size_t want = (size_t)need + 8 * WAVE;
+    HIP_TRY(c->arena.ensure(s->has_orig && want > c->arena.cap ? want + want / 8 : want));
     TRACE("prepared: %lld groups, %.1f MB of blobs, %zu launch range(s), arena %.1f MB", (long long)ngroups, (double)pre[(size_t)ngroups] * 16e-6,
           s->ranges.size(), (double)c->arena.cap * 16e-6);
     s->prep_ok = true;
@@ -4146,6 +4244,7 @@ int bmx_ctx_scan(bmx_ctx *c) {
         if ((rc = launch_range(c, s, s->plan, r.off, r.cnt, s->plan.mode >= 4 ? &r : nullptr))) return rc;
     HIP_TRY(hipEventRecord(s->ev1, c->stream));
     s->timed = true;
+    s->scan_seq++;
     return BMX_OK;
 }
 
@@ -4313,6 +4412,112 @@ int bmx_ctx_fetch(bmx_ctx *c, double *clr, int32_t *ix, int32_t *ia, int32_t *iA
             if (iA) iA[t] = d;
         }
     });
+    return BMX_OK;
+}
+
+/* ---- permutation null (ballermixplus_amd/null.py holds the host reference of the permutation) ---- */
+
+int bmx_ctx_permute_rows(bmx_ctx *c, uint64_t key, int64_t block) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_sites) return fail(BMX_E_STATE, "set_sites must precede permute_rows");
+    if (block < 1) return fail(BMX_E_INVALID, "permutation block size must be >= 1");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t N = (size_t)s->N;
+    const size_t bytes = N * (s->wide_rows ? sizeof(uint32_t) : sizeof(uint16_t));
+    void *cur = s->wide_rows ? (void *)s->row32.p : (void *)s->row16.p;
+    if (!s->has_orig) {         // first permutation since set_sites: keep the given rows (on the stream, after any scan reading them)
+        if (s->wide_rows) HIP_TRY(s->orig32.ensure(N));
+        else HIP_TRY(s->orig16.ensure(N));
+        HIP_TRY(hipMemcpyAsync(s->wide_rows ? (void *)s->orig32.p : (void *)s->orig16.p, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
+        s->has_orig = true;
+    }
+    PermParams Q;
+    Q.N = s->N;
+    Q.B = block;
+    Q.nb = s->N / block;
+    if (Q.nb < 2) {             // sigma is the identity: the rows given to set_sites
+        HIP_TRY(hipMemcpyAsync(cur, s->wide_rows ? (const void *)s->orig32.p : (const void *)s->orig16.p, bytes, hipMemcpyDeviceToDevice,
+                               c->stream));
+    } else {
+        int w = 0;
+        for (uint64_t v = (uint64_t)(Q.nb - 1); v; v >>= 1) w++;
+        Q.h = std::max(4, (w + 1) / 2);
+        Q.mask = (1ull << Q.h) - 1;
+        for (int j = 0; j < 8; j++) Q.rk[j] = bmx_mix64(key + (uint64_t)j);
+        const unsigned blocks = (unsigned)std::min<int64_t>((s->N + 255) / 256, 8192);
+        if (s->wide_rows) hipLaunchKernelGGL(permute_rows_kernel<uint32_t>, dim3(blocks), dim3(256), 0, c->stream, s->orig32.p, s->row32.p, Q);
+        else hipLaunchKernelGGL(permute_rows_kernel<uint16_t>, dim3(blocks), dim3(256), 0, c->stream, s->orig16.p, s->row16.p, Q);
+        HIP_TRY(hipGetLastError());
+    }
+    // the per-row site counts (moment slots, rowthr) do not change; which sites are near a test site does: the prepared
+    // pipeline's counting pass and launch ranges are redone by the next scan
+    s->plan_ok = false;
+    s->prep_ok = false;
+    return BMX_OK;
+}
+
+int bmx_ctx_restore_rows(bmx_ctx *c) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_sites) return fail(BMX_E_STATE, "set_sites must precede restore_rows");
+    if (!s->has_orig) return BMX_OK;        // never permuted: the rows are the given ones
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)s->N * (s->wide_rows ? sizeof(uint32_t) : sizeof(uint16_t));
+    if (s->wide_rows) HIP_TRY(hipMemcpyAsync(s->row32.p, s->orig32.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    else HIP_TRY(hipMemcpyAsync(s->row16.p, s->orig16.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    s->plan_ok = false;
+    s->prep_ok = false;
+    return BMX_OK;
+}
+
+int bmx_ctx_null_begin(bmx_ctx *c) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "null_begin needs the observed scan: call bmx_ctx_scan first");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t M = (size_t)s->M;
+    HIP_TRY(s->null_obs.ensure(M));
+    HIP_TRY(s->null_cnt.ensure(M));
+    HIP_TRY(s->null_part.ensure((size_t)NULL_BLOCKS_MAX + 1));
+    HIP_TRY(hipMemcpyAsync(s->null_obs.p, s->clr.p, M * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(s->null_cnt.p, 0, M * sizeof(int32_t), c->stream));
+    s->null_ok = true;
+    s->null_reps = 0;
+    s->null_seq = s->scan_seq;
+    return BMX_OK;
+}
+
+int bmx_ctx_null_accumulate(bmx_ctx *c, double *max_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->null_ok) return fail(BMX_E_STATE, "null_begin must precede null_accumulate");
+    if (!s->timed || s->scan_seq == s->null_seq) return fail(BMX_E_STATE, "null_accumulate needs a new scan (one per replicate)");
+    HIP_TRY(hipSetDevice(c->device));
+    const int blocks = (int)std::min<int64_t>((s->M + NULL_THREADS - 1) / NULL_THREADS, NULL_BLOCKS_MAX);
+    double *part = s->null_part.p, *mx = s->null_part.p + NULL_BLOCKS_MAX;
+    hipLaunchKernelGGL(null_count_kernel, dim3(blocks), dim3(NULL_THREADS), 0, c->stream, (const double *)s->clr.p,
+                       (const double *)s->null_obs.p, s->null_cnt.p, s->M, part);
+    hipLaunchKernelGGL(null_max_kernel, dim3(1), dim3(NULL_THREADS), 0, c->stream, (const double *)part, blocks, mx);
+    HIP_TRY(hipGetLastError());
+    double m = 0.0;
+    HIP_TRY(hipMemcpyAsync(&m, mx, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int st = check_status(c)) return st;      // the replicate's scan must have been sound (a stale prepared stream shows here)
+    s->null_seq = s->scan_seq;
+    s->null_reps++;
+    if (max_out) *max_out = m;
+    return BMX_OK;
+}
+
+int bmx_ctx_null_fetch(bmx_ctx *c, int32_t *counts, int32_t *replicates) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->null_ok) return fail(BMX_E_STATE, "null_begin must precede null_fetch");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (counts) HIP_TRY(hipMemcpy(counts, s->null_cnt.p, (size_t)s->M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (replicates) *replicates = s->null_reps;
     return BMX_OK;
 }
 
@@ -4605,6 +4810,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
         const bool wfail = fclose(f) != 0;
         bmx_row_tables_free_(tabs);
         s->timed = all_launched && !werr && !code;     // results are fetchable only when every chunk was scanned
+        if (s->timed) s->scan_seq++;
         if (code) return fail(code, msg);
         if (werr == 1) return fail(BMX_E_HIP, "streaming writer: waiting for a result copy failed");
         if (werr == 2) return fail(BMX_E_INVALID, std::string("streaming writer: ") + wmsg);

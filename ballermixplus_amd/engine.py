@@ -223,6 +223,32 @@ class Context:
         _lib.check(self._L.bmx_ctx_scan_write(self._h, path.encode(), _lib.as_lp(phys), _lib.as_dp(gen_label), pack(xs), len(xs),
                                               pack(abs_), len(abs_), pack(As), len(As), int(chunk)))
 
+    def permute_rows(self, key, block=1):
+        """Permute the selected slot's site rows on the device: row[i] = given_row[sigma(i)], sigma =
+        null.block_permutation(N, key, block).  Always from the rows given to set_sites."""
+        _lib.check(self._L.bmx_ctx_permute_rows(self._h, C.c_uint64(int(key) & ((1 << 64) - 1)), int(block)))
+
+    def restore_rows(self):
+        """Back to the rows given to set_sites."""
+        _lib.check(self._L.bmx_ctx_restore_rows(self._h))
+
+    def null_begin(self):
+        """The last scan's CLR becomes the observed one; exceedance counts are zeroed."""
+        _lib.check(self._L.bmx_ctx_null_begin(self._h))
+
+    def null_accumulate(self):
+        """After a replicate's scan: counts += (clr >= observed); returns the replicate's maximum CLR."""
+        m = C.c_double()
+        _lib.check(self._L.bmx_ctx_null_accumulate(self._h, C.byref(m)))
+        return m.value
+
+    def null_fetch(self):
+        """(exceedance counts i32[M], number of accumulated replicates)."""
+        counts = np.empty(self.M, dtype=np.int32)
+        reps = C.c_int32()
+        _lib.check(self._L.bmx_ctx_null_fetch(self._h, _lib.as_ip(counts), C.byref(reps)))
+        return counts, reps.value
+
     def surface(self, test_gen, win_lo, win_hi):
         """T[nA, nx, nab] (NaN where the window is empty) and nsites[nA] of one test site."""
         m = self.model

@@ -207,6 +207,31 @@ int bmx_ctx_plan(bmx_ctx *c, int32_t *J, int32_t *use_lds, int32_t *mode, int64_
  * independently.  Valid once the test sites are set. */
 int bmx_ctx_launch_ranges(bmx_ctx *c, int64_t *offs, int32_t cap, int32_t *n_out);
 
+/* ---- permutation null (opt-in; the CLI's --nullPerm) ------------------------------------------------------------------
+ * A null distribution of the CLR on the user's own sites: the (k, n) rows of the selected slot's sites are permuted on the
+ * device while positions, windows, test sites and the selection table stay; each replicate is scanned with bmx_ctx_scan and
+ * its exceedances and maximum are accumulated on the device.  Under the composite likelihood's assumption that sites (or
+ * blocks of sites) are exchangeable; LD beyond a block and demography are not modelled.
+ *
+ * permute_rows: row[i] = given_row[sigma(i)], sigma the keyed block permutation of ballermixplus_amd/null.py
+ * (block_permutation: blocks of `block` consecutive sites moved intact by an 8-round Feistel network with cycle walking over
+ * the N / block whole blocks, the N mod block tail in place).  A pseudorandom permutation, not an exactly uniform shuffle.
+ * The first call after set_sites keeps the given rows on the device (2 or 4 bytes per site); later calls permute those, not
+ * the previous permutation.  restore_rows: back to the rows given to set_sites (nothing to do if never permuted).  Both are
+ * asynchronous on the context's stream and make the next scan redo its plan and the prepared pipeline's counting pass.
+ * block < 1: BMX_E_INVALID.  set_sites drops the kept rows. */
+int bmx_ctx_permute_rows(bmx_ctx *c, uint64_t key, int64_t block);
+int bmx_ctx_restore_rows(bmx_ctx *c);
+/* The selected slot's last scan results become the observed CLR and the M exceedance counts are zeroed (12 bytes per test
+ * site).  BMX_E_STATE before a scan; set_tests (and so set_sites / set_model) drops this state. */
+int bmx_ctx_null_begin(bmx_ctx *c);
+/* After the scan of one replicate: counts[t] += (clr[t] >= observed clr[t]); *max_out (may be NULL) = the maximum CLR over
+ * the slot's M test sites (two-pass reduction: deterministic, no atomics).  Blocks.  BMX_E_STATE without null_begin or when no
+ * scan was launched since null_begin / the previous accumulate. */
+int bmx_ctx_null_accumulate(bmx_ctx *c, double *max_out);
+/* counts[M] (may be NULL): exceedances per test site; *replicates (may be NULL): accumulates since null_begin.  Blocks. */
+int bmx_ctx_null_fetch(bmx_ctx *c, int32_t *counts, int32_t *replicates);
+
 /* ---- the final gather over RCCL, inside the library (north_star: "only a final RCCL gather over xGMI") --
  * One process per GPU, each with its own context.  Rank 0 makes an id (bmx_comm_unique_id: 128 bytes) and hands it to the other
  * ranks by whatever channel the caller has (MPI, a file, a socket, torch's store); every rank then calls bmx_comm_create with
