@@ -13,6 +13,9 @@ Additions (do not change any reference command line):
   --nullPerm R [--nullSeed S] [--nullBlock B]     permutation null (ballermixplus_amd/null.py): after the observed scan of
                     each file, R more scans with the sites' (k, n) rows permuted on the device; writes <out>.null.txt (several
                     files: <dir>/null.txt or the -o pattern with `null`) and <out>.pval.txt next to each output file.
+  --profiles A,x,abeta     profile likelihoods (ballermixplus_amd/profiles.py): per window the CLR with A, x or alpha_beta fixed
+                    to each grid value, from the same scan; writes <out>.profile_A.txt / .profile_x.txt / .profile_abeta.txt
+                    next to each output file.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -84,7 +87,41 @@ def build_parser():
                         help='MI355X build only: seed of the --nullPerm permutations (default 1)')
     parser.add_argument('--nullBlock', dest='nullBlock', type=int, default=1,
                         help='MI355X build only: --nullPerm moves blocks of this many consecutive sites intact (default 1: single sites)')
+    parser.add_argument('--profiles', dest='profiles', default=None,
+                        help='MI355X build only: comma list of A, x, abeta.  Writes <out>.profile_<name>.txt next to each output '
+                             'file: per window the CLR with that parameter fixed to each grid value (columns in ascending grid '
+                             'order; the abeta file adds CLR_bal and CLR_pos); default: off')
     return parser
+
+
+def profiles_refusal(opt):
+    """The message that refuses a --profiles command line, or None when it can run (or profiles are off)."""
+    if opt.profiles is None:
+        return None
+    from . import profiles
+    try:
+        profiles.parse(opt.profiles)
+    except ValueError as e:
+        return str(e)
+    if opt.getSpec or opt.getConfig:
+        return '--profiles scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if not opt.outfile:
+        return '--profiles needs -o: the profile files are written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--profiles runs in a single process; multi-rank launches are not supported.'
+    return None
+
+
+def profile_names(opt):
+    from . import profiles
+    return profiles.parse(opt.profiles) if opt.profiles is not None else ()
+
+
+def write_profiles(opt, ctx, sel, outfile, ts):
+    """The profile files of one file whose observed scan has just run on ctx's selected slot."""
+    from . import profiles
+    grids = {'A': list(sel.grid_A), 'x': list(sel.grid_x), 'abeta': list(sel.grid_abeta)}
+    profiles.fetch_and_write(ctx, profile_names(opt), outfile, ts, grids)
 
 
 def null_refusal(opt):
@@ -147,7 +184,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = null_refusal(opt)
+    refused = null_refusal(opt) or profiles_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -219,6 +256,10 @@ def main(argv=None):
     if 'err' in warm:
         raise warm['err']
     stamp('HIP context ready')
+    pnames = profile_names(opt)
+    if pnames:
+        from . import profiles
+        warm['ctx'].set_profiles(profiles.mask(pnames))
     Sel_Probs = engine.NormalizedBetaBinom(data, grid, opt.nofreq, opt.MAF, opt.nosub, device=device, ctx=warm['ctx'])
     say(("\n%s. Start computing likelihood ratios..." % (datetime.now())))
     # BMX_SHARD_BLOCK: test sites per shard block (default distributed.BLOCK = 4096; a multiple of 16 keeps every window's
@@ -227,6 +268,11 @@ def main(argv=None):
     sc = Scan(data, Neutral, Sel_Probs, grid, opt.outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w,
               s=opt.step, phys=opt.phys, noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False)
     stamp('table, scan, output')
+    if pnames:
+        # the observed scan's profiles only: off before the null's replicates, whose cost and output stay as they are
+        write_profiles(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites)
+        Sel_Probs.ctx.set_profiles(0)
+        stamp('profiles')
     if opt.nullPerm:
         got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
         finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
@@ -322,6 +368,10 @@ def main_many(opt, files, stamp=lambda what: None):
     th = threading.Thread(target=host_stage, args=(0,))
     th.start()
     ctx = engine.Context(device)        # HIP start-up (0.2-0.3 s) while the first file is being read
+    pnames = profile_names(opt)
+    if pnames:
+        from . import profiles
+        pmask = profiles.mask(pnames)
     tables = 0
     kernel_ms = 0.0
     null_files = []
@@ -335,6 +385,8 @@ def main_many(opt, files, stamp=lambda what: None):
             th = threading.Thread(target=host_stage, args=(i + 1,))
             th.start()
         say(f"\n{datetime.now()}. {infile} -> {outfile}")
+        if pnames:
+            ctx.set_profiles(pmask)         # (switched off for the previous file's null replicates)
         sc = Scan(data, neut, sel, grid, outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w, s=opt.step, phys=opt.phys,
                   noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False, reuse_ctx=ctx)
         ctx = sel.ctx
@@ -344,6 +396,10 @@ def main_many(opt, files, stamp=lambda what: None):
         except Exception:           # a file without test sites
             pass
         stamp('file %d of %d' % (i + 1, len(files)))
+        if pnames:
+            write_profiles(opt, ctx, sel, outfile, sc.test_sites)
+            if opt.nullPerm:
+                ctx.set_profiles(0)
         if opt.nullPerm:
             # per-file permutations are independent (key of file ordinal i): only the host copies of this file's observed
             # CLR and counts stay until the genome-wide maxima are known

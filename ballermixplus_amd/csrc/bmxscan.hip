@@ -2033,11 +2033,56 @@ struct PrepView {
     int64_t prefix_base;          // prefix of the launch range's first group
     int64_t grp_base;             // absolute index of the launch range's first group
     int *status;
+    // profile likelihoods (PL kernels only; NULL: that profile is off), keys (mantissa, clamped exponent + 2^17) of the launch
+    // range: per (slice, A, test site) the best over the slice's pairs, and per (test site, pair) the best over A
+    double *pl_am; int32_t *pl_ae;    // [nslices][nA][M]
+    double *pl_pm; int32_t *pl_pe;    // [M][NP]
 };
+
+// Profile likelihoods: the key (mantissa m, exponent e) of a product that beats "product 1" (T = 0), or (0, 0) -- below every
+// such key.  Keys are compared exactly as the best-tracking compares them; one conversion of the maximum key (key_clr, shared
+// with finalize_kernel) makes the maximum of every profile equal to the CLR bit for bit.
+__device__ __forceinline__ bool key_gt(int e, double m, int be, double bm) { return e > be || (e == be && m > bm); }
+
+// J keys per lane (one per test site of the group) reduced over the wave's 64 lanes: a transposed butterfly -- at each of the
+// first log2(J) steps a lane swaps half of its keys with its partner and keeps the larger of each pair (J - 1 exchanges), then a
+// plain butterfly over the remaining lane bits.  Afterwards E[0]/m[0] of lane l hold the maximum of test site
+// j = (l >> (6 - log2 J)), the same in all 64 / J lanes that share j.  The steps are a template recursion so that every array
+// index is a constant: a runtime index would move acc[] / E[] of the whole scan loop to scratch memory.
+template <int J, int H>
+__device__ __forceinline__ void pl_transpose_step(int (&E)[J], double (&m)[J], int lane) {
+    if constexpr (H >= 1) {
+        constexpr int off = WAVE * H / J;          // keys H.. go to the partner across this lane bit
+        const bool up = (lane & off) != 0;
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            const int se = up ? E[k] : E[k + H], ke = up ? E[k + H] : E[k];
+            const double sm = up ? m[k] : m[k + H], km = up ? m[k + H] : m[k];
+            const int re = __shfl_xor(se, off);
+            const double rm = __shfl_xor(sm, off);
+            const bool take = key_gt(re, rm, ke, km);
+            E[k] = take ? re : ke;
+            m[k] = take ? rm : km;
+        }
+        pl_transpose_step<J, H / 2>(E, m, lane);
+    }
+}
+
+template <int J>
+__device__ __forceinline__ void pl_wave_max(int (&E)[J], double (&m)[J], int lane) {
+    pl_transpose_step<J, J / 2>(E, m, lane);
+#pragma unroll
+    for (int off = WAVE / J / 2; off >= 1; off >>= 1) {
+        const int re = __shfl_xor(E[0], off);
+        const double rm = __shfl_xor(m[0], off);
+        if (key_gt(re, rm, E[0], m[0])) { E[0] = re; m[0] = rm; }
+    }
+}
 
 // (groups of 8 with the table in LDS: 168 registers, so that one workgroup of twelve waves -- one R slice, twelve rings -- gives
 // three waves per SIMD; the 16-test-site form needs 243 and runs two)
-template <int J, bool USE_LDS>
+// PL: also the profile likelihoods' keys (V.pl_*); PL = false is the plain scan
+template <int J, bool USE_LDS, bool PL = false>
 __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREADS_MAX) void clr_scan_prepared_kernel(ScanParams P, PrepView V) {
 #ifdef BMX_PROFILE
     // sections: 0 sites between the test sites, 1 zone header, 2 pair list, 3 quad list, 4 generic walks past the zones, 5 fold of the
@@ -2664,10 +2709,45 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                     bestK[j] = (ec << 13) | iA;
                 }
             }
+            if constexpr (PL) {
+                if (V.pl_am) {
+                    // A profile: this A's keys over the slice's pairs, in place (acc / E are dead until the next A sets them),
+                    // counted exactly where the best-tracking above would count them
+#pragma unroll
+                    for (int j = 0; j < J; ++j) {
+                        const int ec = min(max(E[j], -131071), 131071) + 131072;
+                        const bool beats = key_gt(ec, acc[j], 131072 + (BMX_FREXP ? 1 : 0), BMX_FREXP ? 0.5 : 1.0) && (!BMX_FREXP || acc[j] > 0.0) &&
+                                           p < P.npairs;
+                        E[j] = beats ? ec : 0;
+                        acc[j] = beats ? acc[j] : 0.0;
+                    }
+                    pl_wave_max<J>(E, acc, lane);
+                    const int jm = lane >> (6 - __builtin_ctz(J));
+                    if ((lane & (WAVE / J - 1)) == 0 && jm < nvalid) {
+                        const size_t o = ((size_t)slice * P.nA + iA) * P.M + (tb + jm);
+                        V.pl_am[o] = acc[0];
+                        V.pl_ae[o] = E[0];
+                    }
+                }
+            }
             if (bad) break;
         }
         PROF_MARK(9);
         if (bad && lane == 0) atomicOr(V.status, 2);
+        if constexpr (PL) {
+            if (V.pl_pm) {
+                // x and alpha_beta profiles: each pair's best over A, before the winners' reduction below overwrites it
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    if (j < nvalid) {
+                        const bool any = (bestK[j] & 8191) != 8191 && !bad;
+                        const size_t o = (size_t)(tb + j) * P.NP + p;
+                        V.pl_pm[o] = any ? bestM[j] : 0.0;
+                        V.pl_pe[o] = any ? bestK[j] >> 13 : 0;
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             const int biA = bestK[j] & 8191;
@@ -2956,7 +3036,7 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_solo_kernel(PrepParams P) {
     }
 }
 
-template <bool USE_LDS>
+template <bool USE_LDS, bool PL = false>
 __global__ __launch_bounds__(SITE_THREADS) void clr_scan_solo_kernel(ScanParams P, PrepView V) {
     extern __shared__ __attribute__((aligned(16))) double lds_R[];  // [rows][64] when USE_LDS, then one ring per wave
     const int lane = threadIdx.x & (WAVE - 1);
@@ -3102,8 +3182,29 @@ __global__ __launch_bounds__(SITE_THREADS) void clr_scan_solo_kernel(ScanParams 
                 bestEc = ec;
                 bestA = iA;
             }
+            if constexpr (PL) {
+                if (V.pl_am) {       // A profile: this A's best key over the slice's pairs (see the prepared kernel)
+                    const bool beats = key_gt(ec, acc, 131072 + 1, 0.5) && acc > 0.0 && p < P.npairs;
+                    int ek[1] = {beats ? ec : 0};
+                    double mk[1] = {beats ? acc : 0.0};
+                    pl_wave_max<1>(ek, mk, lane);
+                    if (lane == 0) {
+                        const size_t o = ((size_t)slice * P.nA + iA) * P.M + t;
+                        V.pl_am[o] = mk[0];
+                        V.pl_ae[o] = ek[0];
+                    }
+                }
+            }
         }
         if (bad && lane == 0) atomicOr(V.status, 2);
+        if constexpr (PL) {
+            if (V.pl_pm) {       // x and alpha_beta profiles: this pair's best over A
+                const bool any = bestA >= 0 && !bad;
+                const size_t o = (size_t)t * P.NP + p;
+                V.pl_pm[o] = any ? bestM : 0.0;
+                V.pl_pe[o] = any ? bestEc : 0;
+            }
+        }
         int bE = bestEc;
         int bL = (bestA < 0 || bad) ? 0x7fffffff : bestA * P.npairs + p;
         for (int off = 32; off > 0; off >>= 1) {
@@ -3135,6 +3236,14 @@ struct FinalParams {
     bmx_record *rec;   // the same three values as one 16-byte record per test site (what the multi-GPU gather moves)
 };
 
+// A winning key (mantissa, clamped exponent + 2^17) to its CLR: the one conversion of the scan's result and of every profile entry
+__device__ __forceinline__ double key_clr(double bM, int bE) {
+    // kernels that normalise with v_frexp hand over mantissas in [1/2, 1): back to [1, 2), or a product just above 1 would come
+    // out as LN2 + log(0.5000...) -- a difference of two numbers of size 0.69
+    if (bM < 1.0) { bM *= 2.0; bE -= 1; }
+    return 2.0 * ((double)(bE - 131072) * LN2 + log(bM));
+}
+
 __global__ void finalize_kernel(FinalParams F) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= F.M) return;
@@ -3152,12 +3261,7 @@ __global__ void finalize_kernel(FinalParams F) {
             bL = L;
         }
     }
-    if (bL != 0x7fffffff) {
-        // kernels that normalise with v_frexp hand over mantissas in [1/2, 1): back to [1, 2), or a product just above 1 would come
-        // out as LN2 + log(0.5000...) -- a difference of two numbers of size 0.69
-        if (bM < 1.0) { bM *= 2.0; bE -= 1; }
-        bT = 2.0 * ((double)(bE - 131072) * LN2 + log(bM));
-    }
+    if (bL != 0x7fffffff) bT = key_clr(bM, bE);
     const bool none = (bL == 0x7fffffff);
     if (!none) {
         const double A = F.A[bL / F.npairs], tg = F.test_gen[t];
@@ -3183,6 +3287,44 @@ __global__ void finalize_kernel(FinalParams F) {
     F.lin[t] = none ? -1 : bL;
     F.nsites[t] = none ? 0 : bN;
     F.rec[t] = bmx_record{none ? 0.0 : bT, none ? -1 : bL, none ? 0 : bN};
+}
+
+// Profile likelihoods of one launch range: entry (t, v) of profile `kind` (0: A, 1: x, 2: alpha_beta) is the largest key over
+// the slices (A) or over the pairs with that x / alpha_beta, converted by key_clr; +0.0 where no key beat T = 0.  One thread
+// per entry; no atomics, so the result does not depend on the launch order.  Neighbouring threads take neighbouring keys: test
+// sites fastest for A ([slice][A][t]), grid values fastest for x and alpha_beta ([t][pair], pair = ix * nab + ia).
+struct PlFinalParams {
+    const double *am; const int32_t *ae;       // [nslices][nA][M]
+    const double *pm; const int32_t *pe;       // [M][NP]
+    int kind, nslices, nA, nx, nab, NP;
+    int64_t M;
+    double *out;                               // [M][n] of the kind, grid order
+};
+
+__global__ void profile_finalize_kernel(PlFinalParams F) {
+    const int n = F.kind == 0 ? F.nA : F.kind == 1 ? F.nx : F.nab;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= F.M * n) return;
+    const int64_t t = F.kind == 0 ? i % F.M : i / n;
+    const int v = (int)(F.kind == 0 ? i / F.M : i % n);
+    int be = 0;
+    double bm = 0.0;
+    auto take = [&](double m, int e) {
+        if (key_gt(e, m, be, bm)) { be = e; bm = m; }
+    };
+    if (F.kind == 0) {
+        for (int s = 0; s < F.nslices; ++s) {
+            const size_t o = ((size_t)s * F.nA + v) * F.M + t;
+            take(F.am[o], F.ae[o]);
+        }
+    } else if (F.kind == 1) {
+        const size_t o = (size_t)t * F.NP + (size_t)v * F.nab;
+        for (int ia = 0; ia < F.nab; ++ia) take(F.pm[o + ia], F.pe[o + ia]);
+    } else {
+        const size_t o = (size_t)t * F.NP + v;
+        for (int ix = 0; ix < F.nx; ++ix) take(F.pm[o + (size_t)ix * F.nab], F.pe[o + (size_t)ix * F.nab]);
+    }
+    F.out[(size_t)t * n + v] = be ? key_clr(bm, be) : 0.0;
 }
 
 // ----------------------------------------------------------------------------- surface
@@ -3318,6 +3460,7 @@ struct PrepRange {
 struct ScanPlan {
     ScanParams P;
     const void *fn = nullptr;
+    const void *fn_pl = nullptr;    // the same kernel with the profile likelihoods (nullptr: the plan's kernel has no such form)
     int J = 0, threads = SCAN_THREADS;
     size_t lds_bytes = 0;
     int spb = 0;            // test sites per workgroup
@@ -3369,6 +3512,10 @@ struct ChromSlot {
     DevBuf<int32_t> blob_units;
     DevBuf<int64_t> blob_prefix;
     std::vector<PrepRange> ranges;
+    int plan_pl = 0;             // the context's profile set the plan (its launch ranges) was made for
+    // profile likelihoods of the last scan: which ones it computed (BMX_PL_* bits), [M][nA] / [M][nx] / [M][nab] f64
+    int pl_have = 0;
+    DevBuf<double> pl_out[3];
     uint64_t scan_seq = 0;       // scans launched in this slot (the null's accumulate takes each replicate's scan once)
     // permutation null: the rows given to set_sites while the row arrays hold a permutation of them (bmx_ctx_permute_rows) ...
     bool has_orig = false;
@@ -3387,6 +3534,7 @@ struct ChromSlot {
         test_gen.release(); win_lo.release(); win_hi.release(); center.release(); center_hi.release();
         clr.release(); lin.release(); nsites.release(); rec.release();
         blob_units.release(); blob_prefix.release();
+        for (auto &b : pl_out) b.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         ev0 = ev1 = nullptr;
@@ -3424,6 +3572,10 @@ struct bmx_ctx {
     DevBuf<double> surf_T;
     DevBuf<int32_t> surf_ns;
     DevBuf<int64_t> gap_sample;
+    // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
+    int pl_which = 0;
+    DevBuf<double> pl_am, pl_pm;
+    DevBuf<int32_t> pl_ae, pl_pe;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
     size_t h_stage_cap = 0;
@@ -3445,6 +3597,7 @@ void drop_tests(ChromSlot *s) {
     s->plan_ok = false;
     s->prep_ok = false;
     s->null_ok = false;     // the observed CLR and the counts belong to those test sites
+    s->pl_have = 0;         // ... and so do the profiles
 }
 void drop_sites(ChromSlot *s) {
     s->has_sites = false;
@@ -3571,6 +3724,7 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->slots.clear();
     c->part_T.release(); c->part_lin.release(); c->part_ns.release(); c->arena.release(); c->gap_sample.release();
     c->surf_T.release(); c->surf_ns.release();
+    c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     dfree(c->d_prof);
     dfree(c->d_status);
     for (int k = 0; k < 2; k++) {
@@ -3910,6 +4064,15 @@ namespace {
 // (threads of bmx_scan_multi, a caller's own threads) must not interleave
 std::mutex g_launch_mu;
 
+// Profile likelihoods' scratch: keys of one launch range, per test site
+constexpr int64_t PL_SCRATCH_BYTES = (int64_t)1 << 30;
+int64_t pl_bytes_per_test(const bmx_ctx *c, int which) {
+    int64_t b = 0;
+    if (which & BMX_PL_A) b += 12 * (int64_t)c->nslices * c->nA;
+    if (which & (BMX_PL_X | BMX_PL_ABETA)) b += 12 * (int64_t)c->NP;
+    return b;
+}
+
 int plan_scan(bmx_ctx *c, ChromSlot *s, ScanPlan &pl) {
     ScanParams &P = pl.P;
     P.genpos = s->genpos.p; P.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; P.N = s->N; P.Rt = c->d_Rt;
@@ -4005,6 +4168,14 @@ int plan_scan(bmx_ctx *c, ChromSlot *s, ScanPlan &pl) {
     else if (J == 4) fn = GPICK(4);
     else if (solo) fn = PICK(clr_scan_solo_kernel);
     else fn = PICK(clr_scan_kernel);
+    // profile likelihoods: the prepared and solo pipelines only
+#define GPL(JJ) (use_lds ? (const void *)clr_scan_prepared_kernel<JJ, true, true> : (const void *)clr_scan_prepared_kernel<JJ, false, true>)
+    const void *fn_pl = nullptr;
+    if (mode == 4 && J == 16) fn_pl = GPL(16);
+    else if (mode == 4 && J == 8) fn_pl = GPL(8);
+    else if (mode == 4 && J == 4) fn_pl = GPL(4);
+    else if (solo) fn_pl = use_lds ? (const void *)clr_scan_solo_kernel<true, true> : (const void *)clr_scan_solo_kernel<false, true>;
+#undef GPL
 #undef GP2
 #undef GP4
 #undef GPICK
@@ -4035,12 +4206,14 @@ int plan_scan(bmx_ctx *c, ChromSlot *s, ScanPlan &pl) {
     if (lds_bytes > (size_t)LDS_LIMIT_BYTES) return fail(BMX_E_LIMIT, "LDS budget exceeded");
     if (lds_bytes) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     P.sites_per_block = spb;
-    pl.fn = fn; pl.J = solo ? 1 : J; pl.threads = threads; pl.lds_bytes = lds_bytes; pl.spb = spb; pl.use_lds = use_lds;
+    pl.fn = fn; pl.fn_pl = fn_pl; pl.J = solo ? 1 : J; pl.threads = threads; pl.lds_bytes = lds_bytes; pl.spb = spb; pl.use_lds = use_lds;
     pl.mode = solo ? 5 : J ? mode : -1;
     // test sites per launch: keeps the per-slice winners (16 B x slices per test site) within ~512 MB and the grid
     // within 2^31 workgroups; a multiple of the workgroup's share, so ranges cut the test sites where workgroups do
     int64_t range = std::max<int64_t>((int64_t)(512u << 20) / (16 * (int64_t)c->nslices), spb);
     range = std::min<int64_t>(range, (int64_t)0x7fffff00LL / c->nslices * spb);
+    // with profile likelihoods on, also their per-range keys (12 B per slice and A, 12 B per pair) within PL_SCRATCH_BYTES
+    if (const int64_t plb = pl_bytes_per_test(c, c->pl_which)) range = std::min<int64_t>(range, std::max<int64_t>(PL_SCRATCH_BYTES / plb, spb));
     range = std::max<int64_t>(range / spb, 1) * spb;
     pl.range = range;
     if (prepared || solo) {
@@ -4149,13 +4322,14 @@ int ensure_prep(bmx_ctx *c, ChromSlot *s) {
 }
 
 int ensure_plan(bmx_ctx *c, ChromSlot *s) {
-    if (!s->plan_ok || s->plan_variant != c->variant) {
+    if (!s->plan_ok || s->plan_variant != c->variant || s->plan_pl != c->pl_which) {
         s->plan_ok = false;
         s->prep_ok = false;
         int rc = plan_scan(c, s, s->plan);
         if (rc) return rc;
         s->plan_ok = true;
         s->plan_variant = c->variant;
+        s->plan_pl = c->pl_which;
     }
     return ensure_prep(c, s);
 }
@@ -4171,7 +4345,20 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
     P.test_gen = s->test_gen.p + off; P.win_lo = s->win_lo.p + off; P.win_hi = s->win_hi.p + off;
     P.center = s->center.p + off; P.center_hi = s->center_hi.p + off; P.M = cnt;
     P.part_T = c->part_T.p; P.part_lin = c->part_lin.p; P.part_ns = c->part_ns.p;
-    if (pl.lds_bytes) HIP_TRY(hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+    const int plw = c->pl_which;
+    const void *fn = plw ? pl.fn_pl : pl.fn;
+    if (!fn) return fail(BMX_E_LIMIT, "profile likelihoods: this scan plan has no profile form");
+    if (plw) {
+        if (plw & BMX_PL_A) {
+            HIP_TRY(c->pl_am.ensure((size_t)cnt * c->nslices * c->nA));
+            HIP_TRY(c->pl_ae.ensure((size_t)cnt * c->nslices * c->nA));
+        }
+        if (plw & (BMX_PL_X | BMX_PL_ABETA)) {
+            HIP_TRY(c->pl_pm.ensure((size_t)cnt * c->NP));
+            HIP_TRY(c->pl_pe.ensure((size_t)cnt * c->NP));
+        }
+    }
+    if (pl.lds_bytes) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
     int64_t blocks = (cnt + pl.spb - 1) / pl.spb * c->nslices;
     if (pr && (pl.mode == 5 ? BMX_SOLO_XCD_MAP : BMX_XCD_MAP)) blocks = ((cnt + pl.spb - 1) / pl.spb + 7) / 8 * 8 * c->nslices;     // chunks padded to whole XCD rounds
     if (pr) {
@@ -4187,11 +4374,13 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
         HIP_TRY(hipLaunchKernel(pl.prep_fill, dim3((unsigned)((pr->ng + gpw - 1) / gpw)), dim3(pl.prep_threads), qargs, pl.prep_lds, c->stream));
         PrepView V;
         V.arena = c->arena.p; V.blob_prefix = s->blob_prefix.p; V.prefix_base = pr->pbase; V.grp_base = pr->g0; V.status = c->d_status;
+        V.pl_am = (plw & BMX_PL_A) ? c->pl_am.p : nullptr; V.pl_ae = (plw & BMX_PL_A) ? c->pl_ae.p : nullptr;
+        V.pl_pm = (plw & (BMX_PL_X | BMX_PL_ABETA)) ? c->pl_pm.p : nullptr; V.pl_pe = (plw & (BMX_PL_X | BMX_PL_ABETA)) ? c->pl_pe.p : nullptr;
         void *kargs[] = {&P, &V};
-        HIP_TRY(hipLaunchKernel(pl.fn, dim3((unsigned)blocks), dim3(pl.threads), kargs, pl.lds_bytes, c->stream));
+        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(pl.threads), kargs, pl.lds_bytes, c->stream));
     } else {
         void *kargs[] = {&P};
-        HIP_TRY(hipLaunchKernel(pl.fn, dim3((unsigned)blocks), dim3(pl.threads), kargs, pl.lds_bytes, c->stream));
+        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(pl.threads), kargs, pl.lds_bytes, c->stream));
     }
     FinalParams F;
     F.part_T = c->part_T.p; F.part_lin = c->part_lin.p; F.part_ns = c->part_ns.p;
@@ -4202,6 +4391,32 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
     const int fthreads = 256;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((cnt + fthreads - 1) / fthreads)), dim3(fthreads), 0, c->stream, F);
     HIP_TRY(hipGetLastError());
+    for (int kind = 0; kind < 3; ++kind) {
+        if (!(plw & (1 << kind))) continue;
+        PlFinalParams G;
+        G.am = c->pl_am.p; G.ae = c->pl_ae.p; G.pm = c->pl_pm.p; G.pe = c->pl_pe.p;
+        G.kind = kind; G.nslices = c->nslices; G.nA = c->nA; G.nx = c->nx; G.nab = c->nab; G.NP = c->NP; G.M = cnt;
+        const int n = kind == 0 ? c->nA : kind == 1 ? c->nx : c->nab;
+        G.out = s->pl_out[kind].p + (size_t)off * n;
+        const int64_t items = cnt * n;
+        hipLaunchKernelGGL(profile_finalize_kernel, dim3((unsigned)((items + fthreads - 1) / fthreads)), dim3(fthreads), 0, c->stream, G);
+        HIP_TRY(hipGetLastError());
+    }
+    return BMX_OK;
+}
+
+// before the launches of a scan: the profile set it computes (the slot's profile arrays sized for it), or BMX_E_LIMIT where the
+// plan's kernels have no profile form.  The slot's profiles are valid again once every range has been launched.
+int begin_profiles(bmx_ctx *c, ChromSlot *s) {
+    s->pl_have = 0;
+    const int w = c->pl_which;
+    if (!w) return BMX_OK;
+    if (!s->plan.fn_pl)
+        return fail(BMX_E_LIMIT, "profile likelihoods need the prepared or solo scan kernels; this plan uses a round-2 kernel "
+                                 "(a table of 4 GiB or more, 2^31 sites or more, or a diagnostic variant)");
+    const int n[3] = {c->nA, c->nx, c->nab};
+    for (int k = 0; k < 3; ++k)
+        if (w & (1 << k)) HIP_TRY(s->pl_out[k].ensure((size_t)s->M * n[k]));
     return BMX_OK;
 }
 
@@ -4239,11 +4454,13 @@ int bmx_ctx_scan(bmx_ctx *c) {
     std::vector<PrepRange> rs;
     int rc = scan_ranges(c, s, rs);
     if (rc) return rc;
+    if ((rc = begin_profiles(c, s))) return rc;
     HIP_TRY(hipEventRecord(s->ev0, c->stream));
     for (const PrepRange &r : rs)
         if ((rc = launch_range(c, s, s->plan, r.off, r.cnt, s->plan.mode >= 4 ? &r : nullptr))) return rc;
     HIP_TRY(hipEventRecord(s->ev1, c->stream));
     s->timed = true;
+    s->pl_have = c->pl_which;
     s->scan_seq++;
     return BMX_OK;
 }
@@ -4412,6 +4629,40 @@ int bmx_ctx_fetch(bmx_ctx *c, double *clr, int32_t *ix, int32_t *ia, int32_t *iA
             if (iA) iA[t] = d;
         }
     });
+    return BMX_OK;
+}
+
+/* ---- profile likelihoods (ballermixplus_amd/profiles.py holds the host definition and the writers) ---- */
+
+int bmx_ctx_set_profiles(bmx_ctx *c, int32_t which) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (which < 0 || which > (BMX_PL_A | BMX_PL_X | BMX_PL_ABETA)) return fail(BMX_E_INVALID, "profiles: a set of BMX_PL_A, BMX_PL_X, BMX_PL_ABETA");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->pl_which = which;
+    if (!which) {       // off: nothing of the profiles stays on the device
+        c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
+        for (ChromSlot *s : c->slots) {
+            if (!s) continue;
+            s->pl_have = 0;
+            for (auto &b : s->pl_out) b.release();
+        }
+    }
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_profile(bmx_ctx *c, int32_t which, double *out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (which != BMX_PL_A && which != BMX_PL_X && which != BMX_PL_ABETA) return fail(BMX_E_INVALID, "fetch_profile: one of BMX_PL_A, BMX_PL_X, BMX_PL_ABETA");
+    if (!out) return fail(BMX_E_INVALID, "NULL argument");
+    ChromSlot *s = c->cur;
+    if (!s->has_tests || !s->timed || !(s->pl_have & which)) return fail(BMX_E_STATE, "the slot's last scan did not compute this profile");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int st = check_status(c)) return st;
+    const int k = which == BMX_PL_A ? 0 : which == BMX_PL_X ? 1 : 2;
+    const int n = k == 0 ? c->nA : k == 1 ? c->nx : c->nab;
+    if (s->M) HIP_TRY(hipMemcpy(out, s->pl_out[k].p, (size_t)s->M * n * sizeof(double), hipMemcpyDeviceToHost));
     return BMX_OK;
 }
 
@@ -4719,6 +4970,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
     std::vector<PrepRange> rs;
     int rc = scan_ranges(c, s, rs);
     if (rc) return rc;
+    if ((rc = begin_profiles(c, s))) return rc;
     ScanPlan &pl = s->plan;
     // chunks: the prepared pipeline's launch ranges as they are (their blobs were sized per range); otherwise `chunk` test
     // sites at a time (0: 65536; whole workgroups, which keeps every result bit-identical to bmx_ctx_scan)
@@ -4811,6 +5063,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
         bmx_row_tables_free_(tabs);
         s->timed = all_launched && !werr && !code;     // results are fetchable only when every chunk was scanned
         if (s->timed) s->scan_seq++;
+        s->pl_have = s->timed ? c->pl_which : 0;
         if (code) return fail(code, msg);
         if (werr == 1) return fail(BMX_E_HIP, "streaming writer: waiting for a result copy failed");
         if (werr == 2) return fail(BMX_E_INVALID, std::string("streaming writer: ") + wmsg);

@@ -249,6 +249,25 @@ class Context:
         _lib.check(self._L.bmx_ctx_null_fetch(self._h, _lib.as_ip(counts), C.byref(reps)))
         return counts, reps.value
 
+    PROFILES = {'A': 1, 'x': 2, 'abeta': 4}
+
+    def set_profiles(self, which):
+        """Profile likelihoods of later scans of every slot: a BMX_PL_* bit set (1 A, 2 x, 4 abeta; 0 off), one name
+        ('A', 'x', 'abeta') or an iterable of names."""
+        if isinstance(which, str):
+            which = [which]
+        if not isinstance(which, (int, np.integer)):
+            which = sum(self.PROFILES[n] for n in set(which))
+        _lib.check(self._L.bmx_ctx_set_profiles(self._h, int(which)))
+
+    def fetch_profile(self, which):
+        """f64 [M][n] of one profile ('A', 'x', 'abeta' or its bit) of the selected slot's last scan, the model's grid order."""
+        bit = self.PROFILES[which] if isinstance(which, str) else int(which)
+        n = {1: self.nA, 2: len(self.model.x), 4: len(self.model.abeta)}.get(bit, 0)
+        out = np.empty((self.M, max(n, 1)), dtype=np.float64)
+        _lib.check(self._L.bmx_ctx_fetch_profile(self._h, bit, _lib.as_dp(out)))
+        return out[:, :n]
+
     def surface(self, test_gen, win_lo, win_hi):
         """T[nA, nx, nab] (NaN where the window is empty) and nsites[nA] of one test site."""
         m = self.model

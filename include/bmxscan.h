@@ -232,6 +232,22 @@ int bmx_ctx_null_accumulate(bmx_ctx *c, double *max_out);
 /* counts[M] (may be NULL): exceedances per test site; *replicates (may be NULL): accumulates since null_begin.  Blocks. */
 int bmx_ctx_null_fetch(bmx_ctx *c, int32_t *counts, int32_t *replicates);
 
+/* ---- profile likelihoods (opt-in; the CLI's --profiles) -----------------------------------------------------------------
+ * For test site t and grid value v of a parameter P in {A, x, alpha_beta}: profile_P[t][v] = max(0, the largest T over the
+ * other two grids with P = v) -- the CLR the scan reports at t when P is fixed to v (0 where no grid point has T > 0).  The
+ * kernels compare the exact (mantissa, exponent) keys of the products and convert each maximum with the conversion of the
+ * CLR, so max_v profile_P[t][v] == clr[t] bit for bit.
+ *
+ * set_profiles: the set (0: off, the default) that later scans of every slot compute, bmx_ctx_scan and bmx_ctx_scan_write
+ * alike.  Off releases every profile buffer.  While on, a slot holds 8 * (nA + nx + nab) bytes per test site and the scan's
+ * launch ranges are kept short enough for the keys of one range to fit 1 GiB.  Plans on the round-2 kernels (tables of 4 GiB
+ * or more, 2^31 sites or more, diagnostic variants) have no profile form: their scan fails with BMX_E_LIMIT.
+ * fetch_profile: one BMX_PL_* of the selected slot's last scan, f64 [M][n] with n = nA, nx or nab, the model's grid order.
+ * Blocks.  BMX_E_STATE when that scan ran without this profile; set_tests (and so set_sites / set_model) drops them. */
+enum { BMX_PL_A = 1, BMX_PL_X = 2, BMX_PL_ABETA = 4 };
+int bmx_ctx_set_profiles(bmx_ctx *c, int32_t which);
+int bmx_ctx_fetch_profile(bmx_ctx *c, int32_t which, double *out);
+
 /* ---- the final gather over RCCL, inside the library (north_star: "only a final RCCL gather over xGMI") --
  * One process per GPU, each with its own context.  Rank 0 makes an id (bmx_comm_unique_id: 128 bytes) and hands it to the other
  * ranks by whatever channel the caller has (MPI, a file, a socket, torch's store); every rank then calls bmx_comm_create with
