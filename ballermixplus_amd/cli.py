@@ -16,6 +16,8 @@ Additions (do not change any reference command line):
   --profiles A,x,abeta     profile likelihoods (ballermixplus_amd/profiles.py): per window the CLR with A, x or alpha_beta fixed
                     to each grid value, from the same scan; writes <out>.profile_A.txt / .profile_x.txt / .profile_abeta.txt
                     next to each output file.
+  --refine [--refineMin C]     off-grid refinement (ballermixplus_amd/refine.py): a compass search from each window's grid argmax
+                    (windows with grid CLR >= C); writes <out>.refined.txt next to each output file, the main output's format.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -91,7 +93,37 @@ def build_parser():
                         help='MI355X build only: comma list of A, x, abeta.  Writes <out>.profile_<name>.txt next to each output '
                              'file: per window the CLR with that parameter fixed to each grid value (columns in ascending grid '
                              'order; the abeta file adds CLR_bal and CLR_pos); default: off')
+    parser.add_argument('--refine', dest='refine', action='store_true', default=False,
+                        help='MI355X build only: polish every window\'s grid maximum off the grid (a local compass search in ln A, x '
+                             'and ln alpha_beta inside the hull of the grid) and write <out>.refined.txt next to each output file: '
+                             'the main output\'s rows, with CLR, x_hat, s_hat, A_hat and nSites replaced where the refined CLR is '
+                             'higher; default: off')
+    parser.add_argument('--refineMin', dest='refineMin', type=float, default=None,
+                        help='MI355X build only, with --refine: refine only the windows whose grid CLR is >= this value')
     return parser
+
+
+def refine_refusal(opt):
+    """The message that refuses a --refine / --refineMin command line, or None when it can run (or refinement is off)."""
+    if opt.refineMin is not None and not opt.refine:
+        return '--refineMin needs --refine.'
+    if not opt.refine:
+        return None
+    if opt.refineMin is not None and opt.refineMin != opt.refineMin:
+        return '--refineMin takes a number.'
+    if opt.getSpec or opt.getConfig:
+        return '--refine scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if not opt.outfile:
+        return '--refine needs -o: the refined file is written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--refine runs in a single process; multi-rank launches are not supported.'
+    return None
+
+
+def write_refined(opt, ctx, outfile, ts):
+    """<outfile>.refined.txt of one file whose observed scan has just run on ctx's selected slot."""
+    from . import refine
+    refine.refine_and_write(ctx, outfile, ts, opt.refineMin if opt.refineMin is not None else 0.0)
 
 
 def profiles_refusal(opt):
@@ -184,7 +216,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = null_refusal(opt) or profiles_refusal(opt)
+    refused = null_refusal(opt) or profiles_refusal(opt) or refine_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -273,6 +305,9 @@ def main(argv=None):
         write_profiles(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites)
         Sel_Probs.ctx.set_profiles(0)
         stamp('profiles')
+    if opt.refine:
+        write_refined(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites)
+        stamp('refine')
     if opt.nullPerm:
         got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
         finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
@@ -400,6 +435,8 @@ def main_many(opt, files, stamp=lambda what: None):
             write_profiles(opt, ctx, sel, outfile, sc.test_sites)
             if opt.nullPerm:
                 ctx.set_profiles(0)
+        if opt.refine:
+            write_refined(opt, ctx, outfile, sc.test_sites)
         if opt.nullPerm:
             # per-file permutations are independent (key of file ordinal i): only the host copies of this file's observed
             # CLR and counts stay until the genome-wide maxima are known

@@ -3370,6 +3370,423 @@ __global__ void surface_kernel(SurfParams S) {
     if (slice == 0 && lane == 0) S.ns[iA] = ns;
 }
 
+// ----------------------------------------------------------------------------- refinement
+// Off-grid polish of each window's grid argmax (bmx_ctx_refine / bmx_ctx_eval_points; the definition, which the CPU tests run
+// on a host restatement of T, is ballermixplus_amd/refine.py).  The objective at an arbitrary point (A, x, alpha_beta) is
+//     T = 2 * sum_i log1p(alpha_i R_i),  alpha_i = exp(-A |g_i - t|),  over i in [win_lo, win_hi] with A |g_i - t| <= zcut, g_i != t,
+//     R_i = psel(k_i, n_i | x, alpha_beta) * prop(n_i) / g(k_i, n_i) - 1          (-inf: no such site; non-finite: -inf)
+// with psel computed as K1 computes it for grid points (refine_psel is K1's arithmetic, one inlined pmf call site inside loops).
+// K1's LogPatch covers only the logs of the grid's arguments; off the grid the device's correctly rounded log is used as it
+// is -- at most one unit in the last place of a log inside lgam, far below the 1e-9 to which the tests compare T.
+// A compass search in (u = ln A, x, v = ln alpha_beta) starts at the scan's argmax.  One workgroup per window, grid-striding
+// over a device-compacted list of the windows to refine.  Each round:
+//   1. thread 0 lays out the <= 6 candidates (u-, u+, x-, x+, v-, v+, clamped to the grid's hull; one that clamps onto the
+//      centre is skipped); wave 0 finds the site range of the smallest A among them (64-way search on genpos), once per A;
+//   2. the rows that range references are marked in a byte map (plain stores of 1: no atomics) and compacted in order; the
+//      R entries of the new (x, alpha_beta) candidates -- and of the centre when it changed -- are built for those rows only,
+//      in LDS when the workspace fits REFINE_LDS_WS, else in a per-workgroup global slab;
+//   3. threads stride over the sites ALIGNED TO THE SITE INDEX (site i goes to thread i % REFINE_THREADS, in increasing i), so
+//      a point's T does not depend on the range it was summed over, on the round that summed it or on the launch;
+//   4. the per-thread sums are reduced in a fixed order (xor butterfly in each wave, then the waves in order); thread 0
+//      decides the move (strict '>', first in order wins ties; no move halves every step) and broadcasts it through LDS.
+// No atomics: a window's result is a function of that window alone.
+constexpr int REFINE_THREADS = 256;
+constexpr int REFINE_WAVES = REFINE_THREADS / WAVE;
+constexpr int64_t REFINE_LDS_WS = 32 * 1024;     // workspace bytes held in LDS (else the global slab)
+constexpr int REFINE_TABS = 5;                   // R entries of: the centre, x-, x+, v-, v+
+constexpr int REFINE_EVALS = 7;                  // T of: the centre, u-, u+, x-, x+, v-, v+
+constexpr int REFINE_GRID_MAX = 2048;            // workgroups of a refinement launch (grid-stride over the windows)
+
+struct RefineParams {
+    int stat, min_count, n_sizes, rows;
+    const int32_t *sizes, *row_off;
+    const double *g, *prop;
+    const double *gA, *gx, *gab;       // the model's grids
+    int npairs, nab;
+    const double *cu, *cv;             // ln of every grid A / alpha_beta (the host's log: a start's coordinates)
+    const double *h0u, *h0x, *h0v;     // initial step at every grid value
+    double lo[3], hi[3], tol[3];       // hull and tolerance of u, x, v
+    int fr[3];                         // 1: the coordinate is free
+    int max_rounds;
+    const double *genpos; RowArray row; int64_t N;
+    const double *test_gen; const int64_t *win_lo, *win_hi;
+    double zcut;
+    const int32_t *list; const int64_t *count;     // refine: the windows to refine; point evaluation: nullptr (all M)
+    int64_t M;
+    const int32_t *lin; const double *clr;         // refine: the last scan
+    const double *pA, *px, *pab;                   // point evaluation: the points
+    char *slab; int64_t ws_bytes; int ws_lds;      // workspace: [REFINE_TABS][rows] f64, [rows] i32 list, [rows] u8 map
+    double *o_clr, *o_A, *o_x, *o_ab;
+    int32_t *o_ns, *o_rounds;
+};
+
+// bmx::betabinom_pmf without a LogPatch, operation for operation, with its three log-beta terms from ONE inlined call site in
+// a loop the compiler may not unroll.  (Every function of bmx_math.h is inlined; with three copies of lbeta_pos, or with
+// the pmf unrolled, a loop around the pmf spans more than a branch instruction reaches and the compiler would have to jump
+// with s_setpc_b64.)
+__device__ __forceinline__ double refine_pmf(int k, int n, double a, double b) {
+    if (k < 0 || k > n) return 0.0;
+    double l0 = 0., l1 = 0., l2 = 0.;
+#pragma nounroll
+    for (int i = 0; i < 3; ++i) {
+        const double p = i == 0 ? (double)(n - k + 1) : i == 1 ? k + a : a;
+        const double q = i == 0 ? (double)(k + 1) : i == 1 ? n - k + b : b;
+        const double v = bmx::cephes::lbeta_pos(p, q, bmx::LogPatch{nullptr, nullptr, 0});
+        if (i == 0) l0 = v; else if (i == 1) l1 = v; else l2 = v;
+    }
+    const double combiln = -bmx::crlog((double)(n + 1)) - l0;
+    const double lpm = combiln + l1 - l2;
+    double p = exp(lpm);
+    if (p < 0.0) p = 0.0;
+    if (p > 1.0) p = 1.0;
+    return p;
+}
+
+// R of LUT row r at (x, alpha_beta): bb_lut_kernel's arithmetic (refine_pmf for its pmf), in loops that are not unrolled.
+__device__ __forceinline__ double refine_R(const RefineParams &P, int r, double x, double a) {
+    int j = 0;
+    while (j + 1 < P.n_sizes && r >= P.row_off[j + 1]) j++;
+    const int n = P.sizes[j], k = r - P.row_off[j];
+    const double xm = 1. - x;
+    const double b1 = a / x - a, b2 = a / xm - a;
+    const int m = P.min_count, stat = P.stat;
+    const bool maf = (stat == BMX_STAT_B2MAF || stat == BMX_STAT_B0MAF);
+    int nex = m;
+    if (stat == BMX_STAT_B2MAF) nex += (m - 1 > 0 ? m - 1 : 0);
+    if (stat == BMX_STAT_B0) nex += 1;
+    if (stat == BMX_STAT_B0MAF) nex += m;
+    const int nblk = nex < 8 ? 0 : nex - (nex % 8);
+    double r8[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    double res = 0.;
+    double raw = 0.;
+#pragma nounroll
+    for (int it = 0; it <= nex; ++it) {
+        const bool site = (it == nex);
+        int c;
+        if (site) c = (stat == BMX_STAT_B1) ? n : k;
+        else if (it < m) c = it;
+        else if (stat == BMX_STAT_B0) c = n;
+        else c = n - m + 1 + (it - m);
+        const int nfold = (site && maf) ? 2 : 1;
+        double v0 = 0., v1 = 0., pr = 0.;
+#pragma nounroll
+        for (int sf = 0; sf < 2 * nfold; ++sf) {        // (side, fold) pairs: b(x) then b(1 - x)
+            const int side = sf / nfold, f = sf % nfold;
+            const double q = refine_pmf(f ? n - c : c, n, a, side ? b2 : b1);
+            pr = f ? pr + q : q;
+            if (f == nfold - 1) {
+                if (site && maf && (n % 2 == 0) && c == n / 2) pr = pr / 2;
+                if (site && stat == BMX_STAT_B1) pr = (k == 0) ? pr : (1. - pr - pr);
+                if (side) v1 = pr; else v0 = pr;
+            }
+        }
+        const double e = 0.5 * (v0 + v1);
+        if (site) {
+            raw = e;
+        } else if (nex < 8) {
+            res += e;
+        } else if (it < nblk) {
+            if (it < 8) r8[it] = e; else r8[it & 7] += e;
+            if (it == nblk - 1)
+                res = ((r8[0] + r8[1]) + (r8[2] + r8[3])) + ((r8[4] + r8[5]) + (r8[6] + r8[7]));
+        } else {
+            res += e;
+        }
+    }
+    const double psel = raw / (1. - res);
+    return psel * P.prop[j] / P.g[r] - 1.0;
+}
+
+// First index in [a, b) where pred holds (pred: false ... false true ... true on [a, b)), b if none.  All 64 lanes of one
+// wave call it with the same arguments; 64 probes per step.
+template <class F>
+__device__ __forceinline__ int64_t wave_first_true(int64_t a, int64_t b, F pred) {
+    const int lane = threadIdx.x % WAVE;
+    while (a < b) {
+        const int64_t n = b - a;
+        const int64_t step = (n + WAVE - 1) / WAVE;
+        const int64_t p = min(a + (int64_t)(lane + 1) * step - 1, b - 1);
+        const unsigned long long m = __ballot(pred(p));
+        if (!m) return b;
+        const int L = __ffsll((long long)m) - 1;
+        const int64_t pL = min(a + (int64_t)(L + 1) * step - 1, b - 1);
+        const int64_t pP = L ? min(a + (int64_t)L * step - 1, b - 1) : a - 1;
+        a = pP + 1;
+        b = pL;         // pred(pL) holds: the answer is in [a, pL) or is pL
+        if (a >= b) return pL;
+        if (step == 1) return pL;
+    }
+    return b;
+}
+
+struct RefineState {
+    double c[3], nat[3];            // the centre: coordinates (u, x, v) and natural values (A, x, alpha_beta)
+    double c0[3], nat0[3];          // the start
+    double h[3];
+    double Tc;
+    int nsc, have_c, rounds, phase, cand;
+    int valid[REFINE_EVALS];
+    double cc[REFINE_EVALS][3], cn[REFINE_EVALS][3];
+    double Aev[3];                  // A of the centre, u-, u+
+    int need_tab[REFINE_TABS];
+    double tx[REFINE_TABS], tab_ab[REFINE_TABS];
+    double built_x0, built_ab0;     // (x, alpha_beta) the centre's entries hold, for rows version built_rv0 (-1: none)
+    int built_rv0;
+    double rangeA;                  // the A the current range and row list were made for (0: none)
+    int64_t ctr, wlo, whi, rlo, rhi;
+    int nused, rv;
+    double tg;
+    double red[REFINE_WAVES][REFINE_EVALS];
+    int redn[REFINE_WAVES][3];
+    int wtot[REFINE_WAVES];
+};
+
+__device__ __forceinline__ double refine_nat(const RefineState &S, int k, double v) {
+    return v == S.c0[k] ? S.nat0[k] : (k == 1 ? v : exp(v));
+}
+
+__global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(RefineParams P) {
+    extern __shared__ __attribute__((aligned(16))) double lds_ws[];
+    __shared__ RefineState S;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
+    double *tab = (double *)ws;                                              // [REFINE_TABS][rows]
+    int32_t *list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
+    uint8_t *map = (uint8_t *)(list + P.rows);
+    const int64_t count = P.list ? *P.count : P.M;
+    for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
+        const int64_t t = P.list ? (int64_t)P.list[w] : w;
+        if (tid == 0) {
+            if (P.list) {
+                const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
+                S.nat0[0] = P.gA[iA]; S.nat0[1] = P.gx[ix]; S.nat0[2] = P.gab[ia];
+                S.c0[0] = P.cu[iA]; S.c0[1] = P.gx[ix]; S.c0[2] = P.cv[ia];
+                S.h[0] = P.h0u[iA]; S.h[1] = P.h0x[ix]; S.h[2] = P.h0v[ia];
+            } else {
+                S.nat0[0] = P.pA[t]; S.nat0[1] = P.px[t]; S.nat0[2] = P.pab[t];
+                S.c0[0] = log(P.pA[t]); S.c0[1] = P.px[t]; S.c0[2] = log(P.pab[t]);
+                S.h[0] = S.h[1] = S.h[2] = 0.0;
+            }
+            for (int k = 0; k < 3; ++k) { S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k]; }
+            S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
+            S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
+            S.tg = P.test_gen[t];
+            S.wlo = max(P.win_lo[t], (int64_t)0);
+            S.whi = min(P.win_hi[t], P.N - 1);
+        }
+        __syncthreads();
+        const double tg = S.tg;
+        if (wave == 0) {            // first site at or right of the test position
+            const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
+            if (lane == 0) S.ctr = ctr;
+        }
+        for (;;) {
+            // ---- 1. the round's candidates (thread 0)
+            if (tid == 0) {
+                for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
+                S.valid[0] = !S.have_c;
+                bool conv = true;
+                for (int k = 0; k < 3; ++k)
+                    if (P.fr[k] && !(S.h[k] < P.tol[k])) conv = false;
+                S.cand = S.rounds < P.max_rounds && !conv;
+                if (S.cand) {
+                    for (int d = 0; d < 6; ++d) {
+                        const int k = d >> 1;
+                        if (!P.fr[k]) continue;
+                        const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
+                        if (v == S.c[k]) continue;
+                        S.valid[d + 1] = 1;
+                        for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
+                        S.cc[d + 1][k] = v;
+                        S.cn[d + 1][k] = refine_nat(S, k, v);
+                    }
+                }
+                bool any = false;
+                for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
+                S.phase = any ? 1 : S.cand ? 2 : 0;
+                S.Aev[0] = S.nat[0];
+                S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
+                S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
+                S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
+                S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
+                for (int q = 1; q < REFINE_TABS; ++q) {
+                    S.need_tab[q] = S.valid[q + 2];
+                    S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
+                    S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
+                }
+            }
+            __syncthreads();
+            const int phase = S.phase;
+            if (phase == 0) break;
+            if (phase == 2) {       // every candidate clamps onto the centre: halve
+                if (tid == 0) {
+                    for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+                    S.rounds++;
+                }
+                __syncthreads();
+                continue;
+            }
+            // ---- the site range of the smallest A of the round, and the rows it references
+            double Amin = S.Aev[0];
+            if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
+            if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
+            if (Amin != S.rangeA) {
+                if (wave == 0) {
+                    const double zc = P.zcut;
+                    const int64_t ctr = S.ctr;
+                    const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
+                    const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
+                    if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
+                }
+                for (int r = tid; r < P.rows; r += REFINE_THREADS) map[r] = 0;
+                __syncthreads();
+                for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) map[P.row[i]] = 1;
+                __syncthreads();
+                int base = 0;
+                for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
+                    const int r = r0 + tid;
+                    const bool on = r < P.rows && map[r];
+                    const unsigned long long m = __ballot(on);
+                    if (lane == 0) S.wtot[wave] = __popcll(m);
+                    __syncthreads();
+                    int off = base;
+                    for (int q = 0; q < wave; ++q) off += S.wtot[q];
+                    if (on) list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+                    for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
+                    __syncthreads();
+                }
+                if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
+                __syncthreads();
+            }
+            // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
+            {
+                int qs[REFINE_TABS], nq = 0;
+                const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
+                for (int q = 0; q < REFINE_TABS; ++q)
+                    if (S.need_tab[q] && !(q == 0 && keep0)) qs[nq++] = q;
+                const int nu = S.nused;
+                for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
+                    const int q = qs[it / nu], r = list[it % nu];
+                    tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
+                }
+                __syncthreads();
+                if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
+            }
+            // ---- 3. the site sums, aligned to the site index
+            double acc[REFINE_EVALS];
+            int ns[3] = {0, 0, 0};
+            for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
+            {
+                int vmask = 0;
+                for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
+                const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
+                const int64_t lo = S.rlo, hi = S.rhi;
+                int64_t i = lo - (lo % REFINE_THREADS) + tid;
+                if (i < lo) i += REFINE_THREADS;
+                for (; i <= hi; i += REFINE_THREADS) {
+                    const double gi = P.genpos[i];
+                    const int r = P.row[i];
+                    const double d = fabs(gi - tg);
+                    const bool same = gi == tg;
+                    const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
+                    const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
+                    const double a0 = exp(-z0);
+                    ns[0] += in0; ns[1] += in1; ns[2] += in2;
+                    if (vmask & 1) { const double v = log1p(a0 * tab[r]); if (in0) acc[0] += v; }
+                    if (vmask & 2) { const double v = log1p(exp(-z1) * tab[r]); if (in1) acc[1] += v; }
+                    if (vmask & 4) { const double v = log1p(exp(-z2) * tab[r]); if (in2) acc[2] += v; }
+                    for (int q = 1; q < REFINE_TABS; ++q)
+                        if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += v; }
+                }
+            }
+            // ---- 4. fixed-order reduction, the decision
+            for (int off = 1; off < WAVE; off <<= 1) {
+                for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
+                for (int k = 0; k < 3; ++k) ns[k] += __shfl_xor(ns[k], off);
+            }
+            if (lane == 0) {
+                for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
+                for (int k = 0; k < 3; ++k) S.redn[wave][k] = ns[k];
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double T[REFINE_EVALS];
+                int nk[3];
+                for (int k = 0; k < 3; ++k) nk[k] = (S.redn[0][k] + S.redn[1][k]) + (S.redn[2][k] + S.redn[3][k]);
+                for (int e = 0; e < REFINE_EVALS; ++e) {
+                    const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
+                    const int n = nk[e == 1 ? 1 : e == 2 ? 2 : 0];
+                    const double v = 2.0 * s;
+                    T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
+                }
+                if (S.valid[0]) { S.Tc = T[0]; S.nsc = nk[0]; S.have_c = 1; }
+                if (S.cand) {
+                    double best = S.Tc;
+                    int bi = -1;
+                    for (int e = 1; e < REFINE_EVALS; ++e)
+                        if (S.valid[e] && T[e] > best) { best = T[e]; bi = e; }
+                    if (bi >= 0) {
+                        for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
+                        S.Tc = best;
+                        S.nsc = nk[bi == 1 ? 1 : bi == 2 ? 2 : 0];
+                    } else {
+                        for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+                    }
+                    S.rounds++;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (P.list) {
+                if (S.Tc > P.clr[t]) {
+                    P.o_clr[t] = S.Tc; P.o_A[t] = S.nat[0]; P.o_x[t] = S.nat[1]; P.o_ab[t] = S.nat[2]; P.o_ns[t] = S.nsc;
+                }
+                P.o_rounds[t] = S.rounds;
+            } else {
+                P.o_clr[t] = S.Tc;
+                P.o_ns[t] = S.nsc;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Before a refinement: every window's row is the scan's (A, x, alpha_beta of its lin; NaN without a grid result), rounds -1,
+// and flag[t] = 1 for the windows to refine (lin >= 0, clr >= min_clr).
+struct RefineInitParams {
+    const double *clr; const int32_t *lin, *nsites;
+    const double *gA, *gx, *gab;
+    int npairs, nab;
+    int64_t M;
+    double min_clr;
+    int32_t *flag;
+    double *o_clr, *o_A, *o_x, *o_ab;
+    int32_t *o_ns, *o_rounds;
+};
+
+__global__ void refine_init_kernel(RefineInitParams Q) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= Q.M) return;
+    const int L = Q.lin[t];
+    const double clr = Q.clr[t];
+    Q.flag[t] = (L >= 0 && clr >= Q.min_clr) ? 1 : 0;
+    Q.o_clr[t] = clr;
+    Q.o_ns[t] = Q.nsites[t];
+    Q.o_rounds[t] = -1;
+    if (L >= 0) {
+        const int p = L % Q.npairs;
+        Q.o_A[t] = Q.gA[L / Q.npairs]; Q.o_x[t] = Q.gx[p / Q.nab]; Q.o_ab[t] = Q.gab[p % Q.nab];
+    } else {
+        Q.o_A[t] = Q.o_x[t] = Q.o_ab[t] = NAN;
+    }
+}
+
+__global__ void refine_compact_kernel(const int32_t *flag, const int64_t *pre, int64_t M, int32_t *list) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < M && flag[t]) list[pre[t]] = (int32_t)t;
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -3527,7 +3944,15 @@ struct ChromSlot {
     int32_t null_reps = 0;
     DevBuf<double> null_obs, null_part;
     DevBuf<int32_t> null_cnt;
+    // refinement of the last scan (bmx_ctx_refine): clr, A, x, alpha_beta, nSites and rounds of every test site
+    bool rf_have = false;
+    DevBuf<double> rf_clr, rf_A, rf_x, rf_ab;
+    DevBuf<int32_t> rf_ns, rf_rounds;
 
+    void release_refined() {
+        rf_have = false;
+        rf_clr.release(); rf_A.release(); rf_x.release(); rf_ab.release(); rf_ns.release(); rf_rounds.release();
+    }
     void release() {
         genpos.release(); rowmax.release(); rowthr.release(); row16.release(); row32.release(); kmom.release(); d_row_of_slot.release();
         orig16.release(); orig32.release(); null_obs.release(); null_part.release(); null_cnt.release();
@@ -3535,6 +3960,7 @@ struct ChromSlot {
         clr.release(); lin.release(); nsites.release(); rec.release();
         blob_units.release(); blob_prefix.release();
         for (auto &b : pl_out) b.release();
+        release_refined();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         ev0 = ev1 = nullptr;
@@ -3576,6 +4002,13 @@ struct bmx_ctx {
     int pl_which = 0;
     DevBuf<double> pl_am, pl_pm;
     DevBuf<int32_t> pl_ae, pl_pe;
+    // refinement scratch (bmx_ctx_refine / bmx_ctx_eval_points): windows to refine, per-grid-value starts and steps, the
+    // per-workgroup workspace of models whose workspace does not fit LDS, points and their results
+    DevBuf<int32_t> rf_flag, rf_list, rf_pns;
+    DevBuf<int64_t> rf_pre;
+    DevBuf<double> rf_grid, rf_pts, rf_pT;
+    DevBuf<char> rf_slab;
+    std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
     size_t h_stage_cap = 0;
@@ -3598,6 +4031,7 @@ void drop_tests(ChromSlot *s) {
     s->prep_ok = false;
     s->null_ok = false;     // the observed CLR and the counts belong to those test sites
     s->pl_have = 0;         // ... and so do the profiles
+    s->release_refined();   // ... and the refinement
 }
 void drop_sites(ChromSlot *s) {
     s->has_sites = false;
@@ -3725,6 +4159,8 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->part_T.release(); c->part_lin.release(); c->part_ns.release(); c->arena.release(); c->gap_sample.release();
     c->surf_T.release(); c->surf_ns.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
+    c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
+    c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
     dfree(c->d_prof);
     dfree(c->d_status);
     for (int k = 0; k < 2; k++) {
@@ -3781,6 +4217,8 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
     if ((rc = upload(c->d_abeta, m->abeta, (size_t)m->nab, c->stream))) return rc;
     if ((rc = upload(c->d_A, A, (size_t)nA, c->stream))) return rc;
     c->h_A.assign(A, A + nA);
+    c->h_x.assign(m->x, m->x + m->nx);
+    c->h_ab.assign(m->abeta, m->abeta + m->nab);
     size_t tab = (size_t)c->npairs * c->rows;
     HIP_TRY(hipMalloc((void **)&c->d_psel, tab * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&c->d_R, tab * sizeof(double)));
@@ -4800,6 +5238,161 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
     HIP_TRY(hipMemcpyAsync(T_out, c->surf_T.p, (size_t)c->nA * c->npairs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out, c->surf_ns.p, (size_t)c->nA * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return BMX_OK;
+}
+
+}  // extern "C"
+
+/* ---- refinement (ballermixplus_amd/refine.py holds the definition: bounds, initial steps, the compass search) ---- */
+
+namespace {
+
+// The model's part of a refinement launch: grids, each grid value's coordinate and initial step, hull, free coordinates
+// (uploaded into c->rf_grid: cu[nA], cv[nab], h0u[nA], h0x[nx], h0v[nab]).
+int refine_setup(bmx_ctx *c, ChromSlot *s, RefineParams &P, int max_rounds) {
+    const int nA = c->nA, nx = c->nx, nab = c->nab;
+    std::vector<double> cu(nA), cv(nab), h0u(nA), h0x(nx), h0v(nab);
+    for (int i = 0; i < nA; i++) cu[i] = std::log(c->h_A[i]);
+    for (int i = 0; i < nab; i++) cv[i] = std::log(c->h_ab[i]);
+    auto axis = [&](const std::vector<double> &vals, std::vector<double> &h0, int k) {
+        std::vector<double> S(vals);
+        std::sort(S.begin(), S.end());
+        S.erase(std::unique(S.begin(), S.end()), S.end());
+        P.fr[k] = S.size() >= 2;
+        P.lo[k] = S.front();
+        P.hi[k] = S.back();
+        for (size_t i = 0; i < vals.size(); i++) {
+            const size_t p = (size_t)(std::lower_bound(S.begin(), S.end(), vals[i]) - S.begin());
+            double h = INFINITY;
+            if (p > 0) h = std::min(h, S[p] - S[p - 1]);
+            if (p + 1 < S.size()) h = std::min(h, S[p + 1] - S[p]);
+            h0[i] = S.size() >= 2 ? 0.5 * h : 0.0;
+        }
+    };
+    axis(cu, h0u, 0);
+    axis(c->h_x, h0x, 1);
+    axis(cv, h0v, 2);
+    P.tol[0] = 1e-4; P.tol[1] = 1e-5; P.tol[2] = 1e-4;
+    std::vector<double> all;
+    for (auto *v : {&cu, &cv, &h0u, &h0x, &h0v}) all.insert(all.end(), v->begin(), v->end());
+    int rc;
+    if ((rc = upload(c->rf_grid, (const double *)all.data(), all.size(), c->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));      // `all` goes out of scope here
+    const double *d = c->rf_grid.p;
+    P.cu = d; P.cv = d + nA; P.h0u = d + nA + nab; P.h0x = d + 2 * nA + nab; P.h0v = d + 2 * nA + nab + nx;
+    P.stat = c->stat; P.min_count = c->min_count; P.n_sizes = c->n_sizes; P.rows = c->rows;
+    P.sizes = c->d_sizes; P.row_off = c->d_row_off; P.g = c->d_g; P.prop = c->d_prop;
+    P.gA = c->d_A; P.gx = c->d_x; P.gab = c->d_abeta; P.npairs = c->npairs; P.nab = nab;
+    P.max_rounds = max_rounds;
+    P.genpos = s->genpos.p; P.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; P.N = s->N;
+    P.test_gen = s->test_gen.p; P.win_lo = s->win_lo.p; P.win_hi = s->win_hi.p; P.zcut = c->zcut;
+    P.M = s->M;
+    P.list = nullptr; P.count = nullptr; P.lin = nullptr; P.clr = nullptr; P.pA = P.px = P.pab = nullptr;
+    P.o_A = P.o_x = P.o_ab = nullptr; P.o_rounds = nullptr;
+    return BMX_OK;
+}
+
+// Workspace (LDS or slab) and launch of refine_kernel over `blocks` workgroups at most
+int refine_launch(bmx_ctx *c, RefineParams &P, int64_t work) {
+    const int64_t ws = ((int64_t)c->rows * (REFINE_TABS * 8 + 4 + 1) + 15) / 16 * 16;
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    int64_t blocks = std::min<int64_t>(std::max<int64_t>(work, 1), std::min<int64_t>(REFINE_GRID_MAX, 8LL * std::max(cus, 1)));
+    P.ws_bytes = ws;
+    P.ws_lds = ws <= REFINE_LDS_WS;
+    if (!P.ws_lds) {
+        blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (512LL << 20) / ws));
+        HIP_TRY(c->rf_slab.ensure((size_t)(blocks * ws)));
+        P.slab = c->rf_slab.p;
+    } else {
+        P.slab = nullptr;
+    }
+    hipLaunchKernelGGL(refine_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), P.ws_lds ? (size_t)ws : 0, c->stream, P);
+    HIP_TRY(hipGetLastError());
+    return BMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmx_ctx_eval_points(bmx_ctx *c, const double *A, const double *x, const double *abeta, double *T_out, int32_t *nsites_out) {
+    if (!c || !A || !x || !abeta || !T_out) return fail(BMX_E_INVALID, "NULL argument");
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before eval_points");
+    const int64_t M = s->M;
+    for (int64_t t = 0; t < M; t++)
+        if (!(A[t] > 0.0) || !(x[t] > 0.0 && x[t] < 1.0) || !(abeta[t] > 0.0) || !std::isfinite(A[t]) || !std::isfinite(abeta[t]))
+            return fail(BMX_E_INVALID, "eval_points: A > 0, 0 < x < 1 and alpha_beta > 0 (finite) at every point");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    RefineParams P;
+    int rc = refine_setup(c, s, P, 0);
+    if (rc) return rc;
+    HIP_TRY(c->rf_pts.ensure((size_t)3 * M));
+    HIP_TRY(hipMemcpyAsync(c->rf_pts.p, A, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + M, x, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + 2 * M, abeta, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->rf_pT.ensure((size_t)M));
+    HIP_TRY(c->rf_pns.ensure((size_t)M));
+    P.pA = c->rf_pts.p; P.px = c->rf_pts.p + M; P.pab = c->rf_pts.p + 2 * M;
+    P.o_clr = c->rf_pT.p; P.o_ns = c->rf_pns.p;
+    if ((rc = refine_launch(c, P, M))) return rc;
+    HIP_TRY(hipMemcpyAsync(T_out, c->rf_pT.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out, c->rf_pns.p, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BMX_OK;
+}
+
+int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_tests || !s->timed) return fail(BMX_E_STATE, "refine: no scan results (scan the slot first)");
+    if (min_clr != min_clr) return fail(BMX_E_INVALID, "refine: min_clr is NaN");
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t M = s->M;
+    RefineParams P;
+    int rc = refine_setup(c, s, P, 256);
+    if (rc) return rc;
+    HIP_TRY(s->rf_clr.ensure((size_t)M)); HIP_TRY(s->rf_A.ensure((size_t)M)); HIP_TRY(s->rf_x.ensure((size_t)M));
+    HIP_TRY(s->rf_ab.ensure((size_t)M)); HIP_TRY(s->rf_ns.ensure((size_t)M)); HIP_TRY(s->rf_rounds.ensure((size_t)M));
+    HIP_TRY(c->rf_flag.ensure((size_t)M));
+    HIP_TRY(c->rf_pre.ensure((size_t)M + 1));
+    HIP_TRY(c->rf_list.ensure((size_t)M));
+    RefineInitParams Q;
+    Q.clr = s->clr.p; Q.lin = s->lin.p; Q.nsites = s->nsites.p;
+    Q.gA = c->d_A; Q.gx = c->d_x; Q.gab = c->d_abeta; Q.npairs = c->npairs; Q.nab = c->nab;
+    Q.M = M; Q.min_clr = min_clr; Q.flag = c->rf_flag.p;
+    Q.o_clr = s->rf_clr.p; Q.o_A = s->rf_A.p; Q.o_x = s->rf_x.p; Q.o_ab = s->rf_ab.p; Q.o_ns = s->rf_ns.p; Q.o_rounds = s->rf_rounds.p;
+    const unsigned nb = (unsigned)((M + 255) / 256);
+    hipLaunchKernelGGL(refine_init_kernel, dim3(nb), dim3(256), 0, c->stream, Q);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rf_flag.p, M, c->rf_pre.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)c->rf_flag.p,
+                       (const int64_t *)c->rf_pre.p, M, c->rf_list.p);
+    HIP_TRY(hipGetLastError());
+    P.list = c->rf_list.p; P.count = c->rf_pre.p + M;
+    P.lin = s->lin.p; P.clr = s->clr.p;
+    P.o_clr = s->rf_clr.p; P.o_A = s->rf_A.p; P.o_x = s->rf_x.p; P.o_ab = s->rf_ab.p; P.o_ns = s->rf_ns.p; P.o_rounds = s->rf_rounds.p;
+    if ((rc = refine_launch(c, P, M))) return rc;
+    s->rf_have = true;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_refined(bmx_ctx *c, double *clr, double *A, double *x, double *abeta, int32_t *nsites, int32_t *rounds) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->rf_have) return fail(BMX_E_STATE, "no refinement of the slot's test sites: call bmx_ctx_refine after a scan");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t M = (size_t)s->M;
+    if (clr) HIP_TRY(hipMemcpy(clr, s->rf_clr.p, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (A) HIP_TRY(hipMemcpy(A, s->rf_A.p, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (x) HIP_TRY(hipMemcpy(x, s->rf_x.p, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (abeta) HIP_TRY(hipMemcpy(abeta, s->rf_ab.p, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (nsites) HIP_TRY(hipMemcpy(nsites, s->rf_ns.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (rounds) HIP_TRY(hipMemcpy(rounds, s->rf_rounds.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BMX_OK;
 }
 

@@ -268,6 +268,31 @@ class Context:
         _lib.check(self._L.bmx_ctx_fetch_profile(self._h, bit, _lib.as_dp(out)))
         return out[:, :n]
 
+    def eval_points(self, A, x, abeta):
+        """T (f64[M], -inf where the window is empty) and nSites (i32[M]) of every test site of the selected slot at the
+        point (A[t], x[t], abeta[t]) -- the refinement's arithmetic (ballermixplus_amd/refine.py).  Scalars broadcast."""
+        M = self.M
+        A, x, abeta = (_lib.f64(np.broadcast_to(np.asarray(v, dtype=np.float64), (M,))) for v in (A, x, abeta))
+        T = np.empty(M, dtype=np.float64)
+        ns = np.empty(M, dtype=np.int32)
+        _lib.check(self._L.bmx_ctx_eval_points(self._h, _lib.as_dp(A), _lib.as_dp(x), _lib.as_dp(abeta), _lib.as_dp(T),
+                                               _lib.as_ip(ns)))
+        return T, ns
+
+    def refine(self, min_clr=0.0):
+        """Refine the selected slot's last scan off the grid (windows with a grid result and CLR >= min_clr)."""
+        _lib.check(self._L.bmx_ctx_refine(self._h, float(min_clr)))
+
+    def fetch_refined(self):
+        """The last refinement: {'clr', 'A', 'x', 'abeta': f64[M], 'nsites', 'rounds': i32[M]} (rounds -1: not refined;
+        rows that did not improve carry the scan's values)."""
+        M = self.M
+        out = {k: np.empty(M, dtype=np.float64) for k in ('clr', 'A', 'x', 'abeta')}
+        out.update({k: np.empty(M, dtype=np.int32) for k in ('nsites', 'rounds')})
+        _lib.check(self._L.bmx_ctx_fetch_refined(self._h, _lib.as_dp(out['clr']), _lib.as_dp(out['A']), _lib.as_dp(out['x']),
+                                                 _lib.as_dp(out['abeta']), _lib.as_ip(out['nsites']), _lib.as_ip(out['rounds'])))
+        return out
+
     def surface(self, test_gen, win_lo, win_hi):
         """T[nA, nx, nab] (NaN where the window is empty) and nsites[nA] of one test site."""
         m = self.model

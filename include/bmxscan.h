@@ -248,6 +248,22 @@ enum { BMX_PL_A = 1, BMX_PL_X = 2, BMX_PL_ABETA = 4 };
 int bmx_ctx_set_profiles(bmx_ctx *c, int32_t which);
 int bmx_ctx_fetch_profile(bmx_ctx *c, int32_t which, double *out);
 
+/* ---- off-grid refinement of each window's maximum (opt-in; the CLI's --refine; ballermixplus_amd/refine.py) --------------
+ * A deterministic compass search in (ln A, x, ln alpha_beta) from the scan's argmax, on the exact T of the reference at
+ * arbitrary parameter values (the selection probabilities of each candidate are computed on the device as the table's are).
+ * A coordinate is free when the model's grid has two or more distinct values of it; the search stays inside the hull of the
+ * grid.  A refined row is reported only where its T is strictly greater than the scan's CLR, so the refined CLR is >= the
+ * scan's bit for bit.  Each window's result depends on that window alone.  A local polish, not a global optimiser. */
+/* T at a caller-given point per test site of the selected slot (the refinement's arithmetic): A/x/abeta[M], T_out[M]
+ * (-inf where the window at that A is empty), nsites_out[M] (may be NULL).  Blocks. */
+int bmx_ctx_eval_points(bmx_ctx *c, const double *A, const double *x, const double *abeta, double *T_out, int32_t *nsites_out);
+/* Refine the selected slot's last scan (windows with lin >= 0 and clr >= min_clr); asynchronous on the context's stream.
+ * BMX_E_STATE before a scan.  set_tests / set_sites / set_model drop the results. */
+int bmx_ctx_refine(bmx_ctx *c, double min_clr);
+/* M rows: clr, A, x, abeta, nsites of the refined (or unchanged) result; rounds[t] = -1 not refined, else rounds run.  Blocks.
+ * Rows without a grid result carry NaN in A, x and abeta.  Any pointer may be NULL. */
+int bmx_ctx_fetch_refined(bmx_ctx *c, double *clr, double *A, double *x, double *abeta, int32_t *nsites, int32_t *rounds);
+
 /* ---- the final gather over RCCL, inside the library (north_star: "only a final RCCL gather over xGMI") --
  * One process per GPU, each with its own context.  Rank 0 makes an id (bmx_comm_unique_id: 128 bytes) and hands it to the other
  * ranks by whatever channel the caller has (MPI, a file, a socket, torch's store); every rank then calls bmx_comm_create with
