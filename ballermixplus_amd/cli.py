@@ -18,12 +18,16 @@ Additions (do not change any reference command line):
                     next to each output file.
   --refine [--refineMin C]     off-grid refinement (ballermixplus_amd/refine.py): a compass search from each window's grid argmax
                     (windows with grid CLR >= C); writes <out>.refined.txt next to each output file, the main output's format.
+  --support [--supportDrop D] [--supportMin C]     with --refine: support intervals around each refined maximum
+                    (ballermixplus_amd/support.py): per free coordinate, the range where the profile T stays >= T* - D
+                    (windows with refined CLR >= C); writes <out>.support.txt next to each output file.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
 share GPU 0 with a CPU gather: a rehearsal of the multi-rank control flow on a 1-GPU box.
 """
 import argparse
+import math
 import os
 import sys
 from datetime import datetime
@@ -100,6 +104,16 @@ def build_parser():
                              'higher; default: off')
     parser.add_argument('--refineMin', dest='refineMin', type=float, default=None,
                         help='MI355X build only, with --refine: refine only the windows whose grid CLR is >= this value')
+    parser.add_argument('--support', dest='support', action='store_true', default=False,
+                        help='MI355X build only, with --refine: support intervals of x, s (alpha_beta) and A around each refined '
+                             'maximum -- where the profile of T stays within --supportDrop of it -- written to <out>.support.txt '
+                             'next to each output file; default: off')
+    parser.add_argument('--supportDrop', dest='supportDrop', type=float, default=None,
+                        help='MI355X build only, with --support: the drop D in T = 2 ln(likelihood ratio) that bounds the '
+                             'intervals; default: %r, the 0.95 quantile of chi-square(1)' % 3.841458820694124)
+    parser.add_argument('--supportMin', dest='supportMin', type=float, default=None,
+                        help='MI355X build only, with --support: only windows whose refined CLR is >= this value; '
+                             'default: --refineMin\'s value, or 0')
     return parser
 
 
@@ -121,9 +135,32 @@ def refine_refusal(opt):
 
 
 def write_refined(opt, ctx, outfile, ts):
-    """<outfile>.refined.txt of one file whose observed scan has just run on ctx's selected slot."""
+    """<outfile>.refined.txt (and with --support <outfile>.support.txt) of one file whose observed scan has just run on ctx's
+    selected slot."""
     from . import refine
     refine.refine_and_write(ctx, outfile, ts, opt.refineMin if opt.refineMin is not None else 0.0)
+    if opt.support:
+        from . import support
+        drop = opt.supportDrop if opt.supportDrop is not None else support.DROP
+        min_clr = opt.supportMin if opt.supportMin is not None else opt.refineMin if opt.refineMin is not None else 0.0
+        support.support_and_write(ctx, outfile, ts, drop, min_clr)
+
+
+def support_refusal(opt):
+    """The message that refuses a --support / --supportDrop / --supportMin command line, or None when it can run (or support
+    intervals are off).  --refine's own refusals come first (refine_refusal)."""
+    for flag, v in (('--supportDrop', opt.supportDrop), ('--supportMin', opt.supportMin)):
+        if v is not None and not opt.support:
+            return '%s needs --support.' % flag
+    if not opt.support:
+        return None
+    if not opt.refine:
+        return '--support needs --refine: the intervals are drawn around the refined maxima.'
+    if opt.supportDrop is not None and not (math.isfinite(opt.supportDrop) and opt.supportDrop > 0):
+        return '--supportDrop takes a finite number > 0.'
+    if opt.supportMin is not None and opt.supportMin != opt.supportMin:
+        return '--supportMin takes a number.'
+    return None
 
 
 def profiles_refusal(opt):
@@ -216,7 +253,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = null_refusal(opt) or profiles_refusal(opt) or refine_refusal(opt)
+    refused = null_refusal(opt) or profiles_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)

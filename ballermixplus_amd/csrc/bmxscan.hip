@@ -3787,6 +3787,320 @@ __global__ void refine_compact_kernel(const int32_t *flag, const int64_t *pre, i
     if (t < M && flag[t]) list[pre[t]] = (int32_t)t;
 }
 
+// ----------------------------------------------------------------------------- support intervals
+// Profile-likelihood support intervals around each refined maximum (bmx_ctx_support; the definition is
+// ballermixplus_amd/support.py).  One task per (window, free coordinate k, side): task id (t * 3 + k) * 2 + side, side 0 the
+// lower end.  One workgroup of REFINE_THREADS per task, grid-striding over a device-compacted task list, so the six tasks of a
+// window run in parallel.  A task is a sequence of nuisance searches -- refine_kernel's compass rounds with coordinate k held
+// (steps 1-4 of the refinement above, operation for operation: the same candidate layout, row list, R tables, site-aligned
+// sums and fixed-order reduction, so a witness's T is bmx_ctx_eval_points' T at its natural values bit for bit).  Between the
+// searches thread 0 runs the walk / bisection of support.py: search 0 evaluates T* at the centre (no free coordinate), then
+// each search is one profile P_k(t).  No atomics: a task's result is a function of its window alone.
+constexpr int SUPPORT_TASKS = 6;                // per window: (k, side)
+constexpr int SUPPORT_MAX_WALK = 64;
+constexpr int SUPPORT_ND = 11;                  // doubles per task: end, witness[3], witness T, outside[3], outside T, T*, T_best
+constexpr int SUPPORT_NI = 3;                   // int32 per task: censored, rounds (-1: not computed), profile evaluations
+
+struct SupportParams {
+    RefineParams P;                             // the model, sites, windows and workspace as refine_kernel has them
+    const int32_t *list; const int64_t *count;  // the tasks to run
+    const double *rA, *rx, *rab;                // the refinement's natural values (the centre)
+    double drop, end_tol[3];
+    double *o_d; int32_t *o_i;                  // [6 M][SUPPORT_ND], [6 M][SUPPORT_NI]
+};
+
+struct SupportTask {
+    int k, side, fr[3], stage, walk, censored, evals, rounds, done;
+    double h0[3], d, Tstar, L, tbest;
+    double in_c[3], in_n[3], in_T, out_c[3], out_n[3], out_T;
+};
+
+__global__ __launch_bounds__(REFINE_THREADS) void support_kernel(SupportParams Q) {
+    extern __shared__ __attribute__((aligned(16))) double lds_ws[];
+    __shared__ RefineState S;
+    __shared__ SupportTask U;
+    const RefineParams &P = Q.P;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
+    double *tab = (double *)ws;                                              // [REFINE_TABS][rows]
+    int32_t *list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
+    uint8_t *map = (uint8_t *)(list + P.rows);
+    const int64_t count = *Q.count;
+    for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
+        const int64_t task = Q.list[w];
+        const int64_t t = task / SUPPORT_TASKS;
+        if (tid == 0) {
+            U.k = (int)(task % SUPPORT_TASKS) / 2;
+            U.side = (int)(task % 2);
+            const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
+            const double g0[3] = {P.gA[iA], P.gx[ix], P.gab[ia]}, gc[3] = {P.cu[iA], P.gx[ix], P.cv[ia]};
+            S.nat0[0] = Q.rA[t]; S.nat0[1] = Q.rx[t]; S.nat0[2] = Q.rab[t];
+            for (int k = 0; k < 3; ++k) {
+                S.c0[k] = S.nat0[k] == g0[k] ? gc[k] : (k == 1 ? S.nat0[k] : log(S.nat0[k]));
+                S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k];
+                S.h[k] = 0.0;
+                U.fr[k] = 0;                // search 0: T* at the centre
+            }
+            U.h0[0] = P.h0u[iA]; U.h0[1] = P.h0x[ix]; U.h0[2] = P.h0v[ia];
+            U.d = U.h0[U.k];
+            U.stage = 0; U.walk = 0; U.censored = 0; U.evals = 0; U.rounds = 0; U.done = 0;
+            U.tbest = -INFINITY;
+            S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
+            S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
+            S.tg = P.test_gen[t];
+            S.wlo = max(P.win_lo[t], (int64_t)0);
+            S.whi = min(P.win_hi[t], P.N - 1);
+        }
+        __syncthreads();
+        const double tg = S.tg;
+        if (wave == 0) {            // first site at or right of the test position
+            const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
+            if (lane == 0) S.ctr = ctr;
+        }
+        for (;;) {
+            // ---- 1. the round's candidates (thread 0): refine_kernel's, over the task's free coordinates U.fr
+            if (tid == 0) {
+                for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
+                S.valid[0] = !S.have_c;
+                bool conv = true;
+                for (int k = 0; k < 3; ++k)
+                    if (U.fr[k] && !(S.h[k] < P.tol[k])) conv = false;
+                S.cand = S.rounds < P.max_rounds && !conv;
+                if (S.cand) {
+                    for (int d = 0; d < 6; ++d) {
+                        const int k = d >> 1;
+                        if (!U.fr[k]) continue;
+                        const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
+                        if (v == S.c[k]) continue;
+                        S.valid[d + 1] = 1;
+                        for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
+                        S.cc[d + 1][k] = v;
+                        S.cn[d + 1][k] = refine_nat(S, k, v);
+                    }
+                }
+                bool any = false;
+                for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
+                S.phase = any ? 1 : S.cand ? 2 : 0;
+                S.Aev[0] = S.nat[0];
+                S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
+                S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
+                S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
+                S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
+                for (int q = 1; q < REFINE_TABS; ++q) {
+                    S.need_tab[q] = S.valid[q + 2];
+                    S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
+                    S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
+                }
+            }
+            __syncthreads();
+            const int phase = S.phase;
+            if (phase == 0) {
+                // ---- the search has ended: P = S.Tc at S.c.  Walk / bisection (support.py), then the next search or the end
+                if (tid == 0) {
+                    const int k = U.k;
+                    const double Tr = S.Tc;
+                    bool bisect = false;
+                    if (U.stage == 0) {
+                        U.Tstar = Tr; U.L = Tr - Q.drop;
+                        for (int q = 0; q < 3; ++q) { U.in_c[q] = S.c[q]; U.in_n[q] = S.nat[q]; }
+                        U.in_T = Tr;
+                        U.stage = 1;
+                    } else {
+                        U.evals++;
+                        const bool inside = Tr >= U.L;
+                        if (inside) {
+                            for (int q = 0; q < 3; ++q) { U.in_c[q] = S.c[q]; U.in_n[q] = S.nat[q]; }
+                            U.in_T = Tr;
+                            if (U.stage == 1) U.d *= 2.0;
+                        } else {
+                            for (int q = 0; q < 3; ++q) { U.out_c[q] = S.c[q]; U.out_n[q] = S.nat[q]; }
+                            U.out_T = Tr;
+                            U.stage = 2;
+                        }
+                        bisect = U.stage == 2;
+                    }
+                    double v = 0.0;
+                    if (!bisect) {
+                        v = min(max(U.in_c[k] + (U.side ? U.d : -U.d), P.lo[k]), P.hi[k]);
+                        if (U.walk == SUPPORT_MAX_WALK || v == U.in_c[k]) { U.censored = 1; U.done = 1; }
+                        U.walk++;
+                    } else {
+                        if (!(fabs(U.out_c[k] - U.in_c[k]) >= Q.end_tol[k])) U.done = 1;
+                        v = U.in_c[k] + 0.5 * (U.out_c[k] - U.in_c[k]);
+                    }
+                    if (!U.done) {          // P_k(v), warm-started from the inside point with the grid-start steps
+                        for (int q = 0; q < 3; ++q) {
+                            S.c[q] = U.in_c[q]; S.nat[q] = U.in_n[q];
+                            S.h[q] = U.h0[q];
+                            U.fr[q] = P.fr[q] && q != k;
+                        }
+                        S.c[k] = v;
+                        S.nat[k] = refine_nat(S, k, v);
+                        S.Tc = -INFINITY; S.have_c = 0; S.rounds = 0;
+                    }
+                }
+                __syncthreads();
+                if (U.done) break;
+                continue;
+            }
+            if (phase == 2) {       // every candidate clamps onto the centre: halve
+                if (tid == 0) {
+                    for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+                    S.rounds++; U.rounds++;
+                }
+                __syncthreads();
+                continue;
+            }
+            // ---- the site range of the smallest A of the round, and the rows it references
+            double Amin = S.Aev[0];
+            if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
+            if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
+            if (Amin != S.rangeA) {
+                if (wave == 0) {
+                    const double zc = P.zcut;
+                    const int64_t ctr = S.ctr;
+                    const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
+                    const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
+                    if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
+                }
+                for (int r = tid; r < P.rows; r += REFINE_THREADS) map[r] = 0;
+                __syncthreads();
+                for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) map[P.row[i]] = 1;
+                __syncthreads();
+                int base = 0;
+                for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
+                    const int r = r0 + tid;
+                    const bool on = r < P.rows && map[r];
+                    const unsigned long long m = __ballot(on);
+                    if (lane == 0) S.wtot[wave] = __popcll(m);
+                    __syncthreads();
+                    int off = base;
+                    for (int q = 0; q < wave; ++q) off += S.wtot[q];
+                    if (on) list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+                    for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
+                    __syncthreads();
+                }
+                if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
+                __syncthreads();
+            }
+            // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
+            {
+                int qs[REFINE_TABS], nq = 0;
+                const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
+                for (int q = 0; q < REFINE_TABS; ++q)
+                    if (S.need_tab[q] && !(q == 0 && keep0)) qs[nq++] = q;
+                const int nu = S.nused;
+                for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
+                    const int q = qs[it / nu], r = list[it % nu];
+                    tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
+                }
+                __syncthreads();
+                if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
+            }
+            // ---- 3. the site sums, aligned to the site index
+            double acc[REFINE_EVALS];
+            int ns[3] = {0, 0, 0};
+            for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
+            {
+                int vmask = 0;
+                for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
+                const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
+                const int64_t lo = S.rlo, hi = S.rhi;
+                int64_t i = lo - (lo % REFINE_THREADS) + tid;
+                if (i < lo) i += REFINE_THREADS;
+                for (; i <= hi; i += REFINE_THREADS) {
+                    const double gi = P.genpos[i];
+                    const int r = P.row[i];
+                    const double d = fabs(gi - tg);
+                    const bool same = gi == tg;
+                    const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
+                    const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
+                    const double a0 = exp(-z0);
+                    ns[0] += in0; ns[1] += in1; ns[2] += in2;
+                    if (vmask & 1) { const double v = log1p(a0 * tab[r]); if (in0) acc[0] += v; }
+                    if (vmask & 2) { const double v = log1p(exp(-z1) * tab[r]); if (in1) acc[1] += v; }
+                    if (vmask & 4) { const double v = log1p(exp(-z2) * tab[r]); if (in2) acc[2] += v; }
+                    for (int q = 1; q < REFINE_TABS; ++q)
+                        if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += v; }
+                }
+            }
+            // ---- 4. fixed-order reduction, the decision
+            for (int off = 1; off < WAVE; off <<= 1) {
+                for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
+                for (int k = 0; k < 3; ++k) ns[k] += __shfl_xor(ns[k], off);
+            }
+            if (lane == 0) {
+                for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
+                for (int k = 0; k < 3; ++k) S.redn[wave][k] = ns[k];
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double T[REFINE_EVALS];
+                int nk[3];
+                for (int k = 0; k < 3; ++k) nk[k] = (S.redn[0][k] + S.redn[1][k]) + (S.redn[2][k] + S.redn[3][k]);
+                for (int e = 0; e < REFINE_EVALS; ++e) {
+                    const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
+                    const int n = nk[e == 1 ? 1 : e == 2 ? 2 : 0];
+                    const double v = 2.0 * s;
+                    T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
+                    if (S.valid[e] && T[e] > U.tbest) U.tbest = T[e];
+                }
+                if (S.valid[0]) { S.Tc = T[0]; S.nsc = nk[0]; S.have_c = 1; }
+                if (S.cand) {
+                    double best = S.Tc;
+                    int bi = -1;
+                    for (int e = 1; e < REFINE_EVALS; ++e)
+                        if (S.valid[e] && T[e] > best) { best = T[e]; bi = e; }
+                    if (bi >= 0) {
+                        for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
+                        S.Tc = best;
+                        S.nsc = nk[bi == 1 ? 1 : bi == 2 ? 2 : 0];
+                    } else {
+                        for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+                    }
+                    S.rounds++; U.rounds++;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            double *od = Q.o_d + (size_t)task * SUPPORT_ND;
+            int32_t *oi = Q.o_i + (size_t)task * SUPPORT_NI;
+            od[0] = U.in_n[U.k];
+            for (int q = 0; q < 3; ++q) { od[1 + q] = U.in_n[q]; od[5 + q] = U.censored ? NAN : U.out_n[q]; }
+            od[4] = U.in_T;
+            od[8] = U.censored ? NAN : U.out_T;
+            od[9] = U.Tstar;
+            od[10] = U.tbest;
+            oi[0] = U.censored; oi[1] = U.rounds; oi[2] = U.evals;
+        }
+        __syncthreads();
+    }
+}
+
+// Before the support kernel: every task not computed (NaN, rounds -1); flag[task] = 1 for the free coordinates of the windows
+// that were refined with a refined CLR >= min_clr.
+struct SupportInitParams {
+    const double *clr; const int32_t *rounds;     // the refinement
+    int fr[3];
+    int64_t M;
+    double min_clr;
+    int32_t *flag;
+    double *o_d; int32_t *o_i;
+};
+
+__global__ void support_init_kernel(SupportInitParams Q) {
+    const int64_t task = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= Q.M * SUPPORT_TASKS) return;
+    const int64_t t = task / SUPPORT_TASKS;
+    const int k = (int)(task % SUPPORT_TASKS) / 2;
+    Q.flag[task] = (Q.rounds[t] >= 0 && Q.clr[t] >= Q.min_clr && Q.fr[k]) ? 1 : 0;
+    for (int j = 0; j < SUPPORT_ND; ++j) Q.o_d[task * SUPPORT_ND + j] = NAN;
+    Q.o_i[task * SUPPORT_NI] = 0;
+    Q.o_i[task * SUPPORT_NI + 1] = -1;
+    Q.o_i[task * SUPPORT_NI + 2] = 0;
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -3946,12 +4260,22 @@ struct ChromSlot {
     DevBuf<int32_t> null_cnt;
     // refinement of the last scan (bmx_ctx_refine): clr, A, x, alpha_beta, nSites and rounds of every test site
     bool rf_have = false;
+    uint64_t rf_seq = 0;         // scan_seq of the scan that was refined
     DevBuf<double> rf_clr, rf_A, rf_x, rf_ab;
     DevBuf<int32_t> rf_ns, rf_rounds;
+    // support intervals around the refined maxima (bmx_ctx_support): per task, SUPPORT_ND doubles and SUPPORT_NI int32
+    bool sp_have = false;
+    DevBuf<double> sp_d;
+    DevBuf<int32_t> sp_i;
 
+    void release_support() {
+        sp_have = false;
+        sp_d.release(); sp_i.release();
+    }
     void release_refined() {
         rf_have = false;
         rf_clr.release(); rf_A.release(); rf_x.release(); rf_ab.release(); rf_ns.release(); rf_rounds.release();
+        release_support();
     }
     void release() {
         genpos.release(); rowmax.release(); rowthr.release(); row16.release(); row32.release(); kmom.release(); d_row_of_slot.release();
@@ -5292,8 +5616,8 @@ int refine_setup(bmx_ctx *c, ChromSlot *s, RefineParams &P, int max_rounds) {
     return BMX_OK;
 }
 
-// Workspace (LDS or slab) and launch of refine_kernel over `blocks` workgroups at most
-int refine_launch(bmx_ctx *c, RefineParams &P, int64_t work) {
+// Workspace (LDS or slab) of a launch of refine_kernel or support_kernel over `work` workgroups at most: the workgroups to launch
+int refine_workspace(bmx_ctx *c, RefineParams &P, int64_t work, int64_t &blocks_out) {
     const int64_t ws = ((int64_t)c->rows * (REFINE_TABS * 8 + 4 + 1) + 15) / 16 * 16;
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
@@ -5307,7 +5631,16 @@ int refine_launch(bmx_ctx *c, RefineParams &P, int64_t work) {
     } else {
         P.slab = nullptr;
     }
-    hipLaunchKernelGGL(refine_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), P.ws_lds ? (size_t)ws : 0, c->stream, P);
+    blocks_out = blocks;
+    return BMX_OK;
+}
+
+// ... and the launch of refine_kernel
+int refine_launch(bmx_ctx *c, RefineParams &P, int64_t work) {
+    int64_t blocks = 0;
+    int rc = refine_workspace(c, P, work, blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(refine_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), P.ws_lds ? (size_t)P.ws_bytes : 0, c->stream, P);
     HIP_TRY(hipGetLastError());
     return BMX_OK;
 }
@@ -5377,6 +5710,8 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     P.o_clr = s->rf_clr.p; P.o_A = s->rf_A.p; P.o_x = s->rf_x.p; P.o_ab = s->rf_ab.p; P.o_ns = s->rf_ns.p; P.o_rounds = s->rf_rounds.p;
     if ((rc = refine_launch(c, P, M))) return rc;
     s->rf_have = true;
+    s->rf_seq = s->scan_seq;
+    s->release_support();
     return BMX_OK;
 }
 
@@ -5393,6 +5728,91 @@ int bmx_ctx_fetch_refined(bmx_ctx *c, double *clr, double *A, double *x, double 
     if (abeta) HIP_TRY(hipMemcpy(abeta, s->rf_ab.p, M * sizeof(double), hipMemcpyDeviceToHost));
     if (nsites) HIP_TRY(hipMemcpy(nsites, s->rf_ns.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (rounds) HIP_TRY(hipMemcpy(rounds, s->rf_rounds.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BMX_OK;
+}
+
+int bmx_ctx_support(bmx_ctx *c, double drop, double min_clr) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_tests || !s->timed || !s->rf_have || s->rf_seq != s->scan_seq)
+        return fail(BMX_E_STATE, "support: no refinement of the slot's last scan (call bmx_ctx_refine after the scan)");
+    if (!(drop > 0.0) || !std::isfinite(drop)) return fail(BMX_E_INVALID, "support: drop must be finite and > 0");
+    if (min_clr != min_clr) return fail(BMX_E_INVALID, "support: min_clr is NaN");
+    const int64_t M = s->M, nt = M * SUPPORT_TASKS;
+    if (nt > INT32_MAX) return fail(BMX_E_LIMIT, "support: more than 2^31 tasks");
+    HIP_TRY(hipSetDevice(c->device));
+    SupportParams Q;
+    int rc = refine_setup(c, s, Q.P, 256);
+    if (rc) return rc;
+    const double tol[3] = {1e-3, 1e-4, 1e-3};       // support.py: NUIS_TOL, END_TOL
+    for (int k = 0; k < 3; k++) { Q.P.tol[k] = tol[k]; Q.end_tol[k] = tol[k]; }
+    Q.drop = drop;
+    HIP_TRY(s->sp_d.ensure((size_t)nt * SUPPORT_ND));
+    HIP_TRY(s->sp_i.ensure((size_t)nt * SUPPORT_NI));
+    HIP_TRY(c->rf_flag.ensure((size_t)nt));
+    HIP_TRY(c->rf_pre.ensure((size_t)nt + 1));
+    HIP_TRY(c->rf_list.ensure((size_t)nt));
+    SupportInitParams I;
+    I.clr = s->rf_clr.p; I.rounds = s->rf_rounds.p;
+    for (int k = 0; k < 3; k++) I.fr[k] = Q.P.fr[k];
+    I.M = M; I.min_clr = min_clr; I.flag = c->rf_flag.p; I.o_d = s->sp_d.p; I.o_i = s->sp_i.p;
+    const unsigned nb = (unsigned)((nt + 255) / 256);
+    hipLaunchKernelGGL(support_init_kernel, dim3(nb), dim3(256), 0, c->stream, I);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rf_flag.p, nt, c->rf_pre.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)c->rf_flag.p,
+                       (const int64_t *)c->rf_pre.p, nt, c->rf_list.p);
+    HIP_TRY(hipGetLastError());
+    Q.P.lin = s->lin.p; Q.P.clr = s->clr.p;
+    Q.list = c->rf_list.p; Q.count = c->rf_pre.p + nt;
+    Q.rA = s->rf_A.p; Q.rx = s->rf_x.p; Q.rab = s->rf_ab.p;
+    Q.o_d = s->sp_d.p; Q.o_i = s->sp_i.p;
+    int64_t blocks = 0;
+    if ((rc = refine_workspace(c, Q.P, nt, blocks))) return rc;
+    hipLaunchKernelGGL(support_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), Q.P.ws_lds ? (size_t)Q.P.ws_bytes : 0,
+                       c->stream, Q);
+    HIP_TRY(hipGetLastError());
+    s->sp_have = true;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_support(bmx_ctx *c, double *end, double *witness, double *witness_T, double *outside, double *outside_T,
+                          int32_t *censored, double *T_star, double *T_best, int32_t *rounds, int32_t *evals) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->sp_have) return fail(BMX_E_STATE, "no support intervals of the slot's test sites: call bmx_ctx_support after bmx_ctx_refine");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t M = (size_t)s->M, nt = M * SUPPORT_TASKS;
+    std::vector<double> d(nt * SUPPORT_ND);
+    std::vector<int32_t> iv(nt * SUPPORT_NI);
+    HIP_TRY(hipMemcpy(d.data(), s->sp_d.p, d.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(iv.data(), s->sp_i.p, iv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t q = 0; q < nt; q++) {
+        const double *od = &d[q * SUPPORT_ND];
+        const int32_t *oi = &iv[q * SUPPORT_NI];
+        if (end) end[q] = od[0];
+        for (int j = 0; j < 3; j++) {
+            if (witness) witness[q * 3 + j] = od[1 + j];
+            if (outside) outside[q * 3 + j] = od[5 + j];
+        }
+        if (witness_T) witness_T[q] = od[4];
+        if (outside_T) outside_T[q] = od[8];
+        if (censored) censored[q] = oi[0];
+        if (rounds) rounds[q] = oi[1];
+        if (evals) evals[q] = oi[2];
+    }
+    for (size_t t = 0; t < M; t++) {
+        double ts = NAN, tb = NAN;
+        for (size_t q = t * SUPPORT_TASKS; q < (t + 1) * SUPPORT_TASKS; q++) {
+            if (iv[q * SUPPORT_NI + 1] < 0) continue;
+            if (ts != ts) ts = d[q * SUPPORT_ND + 9];
+            if (tb != tb || d[q * SUPPORT_ND + 10] > tb) tb = d[q * SUPPORT_ND + 10];
+        }
+        if (T_star) T_star[t] = ts;
+        if (T_best) T_best[t] = tb;
+    }
     return BMX_OK;
 }
 

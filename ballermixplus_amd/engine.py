@@ -293,6 +293,28 @@ class Context:
                                                  _lib.as_dp(out['abeta']), _lib.as_ip(out['nsites']), _lib.as_ip(out['rounds'])))
         return out
 
+    def support(self, drop, min_clr=0.0):
+        """Support intervals (ballermixplus_amd/support.py) around the refined maxima of the selected slot's last refinement:
+        windows with a refined CLR >= min_clr, threshold T* - drop."""
+        _lib.check(self._L.bmx_ctx_support(self._h, float(drop), float(min_clr)))
+
+    def fetch_support(self):
+        """The last support intervals, per test site t, coordinate k (0: A, 1: x, 2: alpha_beta) and side (0: lo, 1: hi):
+        'end' f64[M, 3, 2] (natural units; 'lo' and 'hi' are its two sides), 'witness' / 'outside' f64[M, 3, 2, 3] (natural
+        A, x, alpha_beta), 'witness_T' / 'outside_T' f64[M, 3, 2], 'censored', 'rounds' (-1: not computed), 'evals' i32[M, 3, 2];
+        'T_star', 'T_best' f64[M].  NaN where not computed."""
+        M = self.M
+        out = {k: np.empty((M, 3, 2), dtype=np.float64) for k in ('end', 'witness_T', 'outside_T')}
+        out.update({k: np.empty((M, 3, 2, 3), dtype=np.float64) for k in ('witness', 'outside')})
+        out.update({k: np.empty((M, 3, 2), dtype=np.int32) for k in ('censored', 'rounds', 'evals')})
+        out.update({k: np.empty(M, dtype=np.float64) for k in ('T_star', 'T_best')})
+        d, i = _lib.as_dp, _lib.as_ip
+        _lib.check(self._L.bmx_ctx_fetch_support(self._h, d(out['end']), d(out['witness']), d(out['witness_T']), d(out['outside']),
+                                                 d(out['outside_T']), i(out['censored']), d(out['T_star']), d(out['T_best']),
+                                                 i(out['rounds']), i(out['evals'])))
+        out['lo'], out['hi'] = out['end'][:, :, 0], out['end'][:, :, 1]
+        return out
+
     def surface(self, test_gen, win_lo, win_hi):
         """T[nA, nx, nab] (NaN where the window is empty) and nsites[nA] of one test site."""
         m = self.model

@@ -264,6 +264,25 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr);
  * Rows without a grid result carry NaN in A, x and abeta.  Any pointer may be NULL. */
 int bmx_ctx_fetch_refined(bmx_ctx *c, double *clr, double *A, double *x, double *abeta, int32_t *nsites, int32_t *rounds);
 
+/* ---- support intervals around each refined maximum (opt-in; the CLI's --support; ballermixplus_amd/support.py) -----------
+ * Per window and free coordinate k (0: A, 1: x, 2: alpha_beta), the range over which the profile of T -- T maximised over the
+ * other free coordinates by the refinement's compass search with k held -- stays >= T* - drop, T* being T at the refined point.
+ * Each end is found by a doubling walk from the refined point and a bisection to a fixed tolerance.  Each window's result
+ * depends on that window alone.  The profile searches are local, so an interval may be narrower than the true one. */
+/* Support intervals of the windows of the selected slot's last refinement (bmx_ctx_refine after the last scan; else
+ * BMX_E_STATE) with a refined CLR >= min_clr; drop finite and > 0.  Asynchronous on the context's stream.  A new scan,
+ * refinement, set_tests / set_sites / set_model drop the results. */
+int bmx_ctx_support(bmx_ctx *c, double drop, double min_clr);
+/* Per task q = (t * 3 + k) * 2 + side (side 0: the lower end, 1: the upper end), M * 6 of each:
+ *   end[q] (natural units), witness[q * 3 + j] (the inside point at the end: A, x, alpha_beta) and witness_T[q] (its T),
+ *   outside[q * 3 + j] / outside_T[q] (the nearest point found outside; NaN when censored), censored[q] (1: the end sits on
+ *   the grid's hull), rounds[q] (compass rounds run; -1: not computed -- window not refined, below min_clr, or k fixed),
+ *   evals[q] (profile evaluations).
+ * Per test site t (M of each): T_star[t] (T at the refined point) and T_best[t] (the largest T any profile search of the window
+ * saw, T* included); NaN where nothing was computed.  Blocks.  Any pointer may be NULL. */
+int bmx_ctx_fetch_support(bmx_ctx *c, double *end, double *witness, double *witness_T, double *outside, double *outside_T,
+                          int32_t *censored, double *T_star, double *T_best, int32_t *rounds, int32_t *evals);
+
 /* ---- the final gather over RCCL, inside the library (north_star: "only a final RCCL gather over xGMI") --
  * One process per GPU, each with its own context.  Rank 0 makes an id (bmx_comm_unique_id: 128 bytes) and hands it to the other
  * ranks by whatever channel the caller has (MPI, a file, a socket, torch's store); every rank then calls bmx_comm_create with
