@@ -88,6 +88,10 @@ PROTOTYPES = {
     'bmx_ctx_fetch_refined': (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip, _ip]),
     'bmx_ctx_support': (C.c_int, [_vp, C.c_double, C.c_double]),
     'bmx_ctx_fetch_support': (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip]),
+    'bmx_ctx_eval_points_weighted': (C.c_int, [_vp, C.c_uint64, C.c_int64, _dp, _dp, _dp, _dp, _lp]),
+    'bmx_ctx_boot': (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, C.c_int64, C.c_double]),
+    'bmx_ctx_boot_count': (C.c_int, [_vp, _lp, _ip]),
+    'bmx_ctx_fetch_boot': (C.c_int, [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip]),
     'bmx_comm_unique_id': (C.c_int, [C.c_char_p]),
     'bmx_comm_create': (C.c_int, [C.POINTER(_vp), _vp, C.c_char_p, C.c_int32, C.c_int32]),
     'bmx_comm_destroy': (None, [_vp]),

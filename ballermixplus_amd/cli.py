@@ -21,6 +21,11 @@ Additions (do not change any reference command line):
   --support [--supportDrop D] [--supportMin C]     with --refine: support intervals around each refined maximum
                     (ballermixplus_amd/support.py): per free coordinate, the range where the profile T stays >= T* - D
                     (windows with refined CLR >= C); writes <out>.support.txt next to each output file.
+  --boot R [--bootSeed S] [--bootBlock B] [--bootLevel L] [--bootMin C] [--bootReps]     with --refine: a Poisson block
+                    bootstrap of each refined maximum (ballermixplus_amd/boot.py): R replicates re-weight the sites in blocks of
+                    B consecutive sites and repeat the search from the refined point (windows with refined CLR >= C); writes
+                    <out>.boot.txt (percentile ends at level L, standard deviations) and with --bootReps <out>.boot.reps.txt
+                    next to each output file.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -114,6 +119,25 @@ def build_parser():
     parser.add_argument('--supportMin', dest='supportMin', type=float, default=None,
                         help='MI355X build only, with --support: only windows whose refined CLR is >= this value; '
                              'default: --refineMin\'s value, or 0')
+    parser.add_argument('--boot', dest='boot', type=int, default=0,
+                        help='MI355X build only, with --refine: R >= 2 bootstrap replicates of every refined maximum.  Each replicate '
+                             'gives every block of --bootBlock consecutive sites a Poisson(1) weight and repeats the local search '
+                             'from the refined point; <out>.boot.txt holds percentile ends and standard deviations of x, s '
+                             '(alpha_beta) and A per window; default 0: off')
+    parser.add_argument('--bootSeed', dest='bootSeed', type=int, default=None,
+                        help='MI355X build only, with --boot: seed of the bootstrap weights (default 1; its stream is separate from '
+                             '--nullSeed\'s)')
+    parser.add_argument('--bootBlock', dest='bootBlock', type=int, default=None,
+                        help='MI355X build only, with --boot: sites per block (default 1).  B should span the linkage disequilibrium '
+                             'of the data; B = 1 resamples sites as if they were independent')
+    parser.add_argument('--bootLevel', dest='bootLevel', type=float, default=None,
+                        help='MI355X build only, with --boot: level L of the percentile ends and of dT_q, 0 < L < 1 (default 0.95)')
+    parser.add_argument('--bootMin', dest='bootMin', type=float, default=None,
+                        help='MI355X build only, with --boot: only windows whose refined CLR is >= this value; '
+                             'default: --refineMin\'s value, or 0')
+    parser.add_argument('--bootReps', dest='bootReps', action='store_true', default=False,
+                        help='MI355X build only, with --boot: also write every replicate of every bootstrapped window to '
+                             '<out>.boot.reps.txt')
     return parser
 
 
@@ -134,9 +158,9 @@ def refine_refusal(opt):
     return None
 
 
-def write_refined(opt, ctx, outfile, ts):
-    """<outfile>.refined.txt (and with --support <outfile>.support.txt) of one file whose observed scan has just run on ctx's
-    selected slot."""
+def write_refined(opt, ctx, outfile, ts, f=0):
+    """<outfile>.refined.txt (with --support <outfile>.support.txt, with --boot <outfile>.boot.txt) of one file (input-file
+    ordinal f) whose observed scan has just run on ctx's selected slot."""
     from . import refine
     refine.refine_and_write(ctx, outfile, ts, opt.refineMin if opt.refineMin is not None else 0.0)
     if opt.support:
@@ -144,6 +168,40 @@ def write_refined(opt, ctx, outfile, ts):
         drop = opt.supportDrop if opt.supportDrop is not None else support.DROP
         min_clr = opt.supportMin if opt.supportMin is not None else opt.refineMin if opt.refineMin is not None else 0.0
         support.support_and_write(ctx, outfile, ts, drop, min_clr)
+    if opt.boot:
+        from . import boot
+        min_clr = opt.bootMin if opt.bootMin is not None else opt.refineMin if opt.refineMin is not None else 0.0
+        boot.boot_and_write(ctx, outfile, ts, opt.boot, opt.bootSeed if opt.bootSeed is not None else 1,
+                            opt.bootBlock if opt.bootBlock is not None else 1,
+                            opt.bootLevel if opt.bootLevel is not None else boot.LEVEL, min_clr, f, opt.bootReps)
+
+
+def boot_refusal(opt):
+    """The message that refuses a --boot / --boot* command line, or None when it can run (or the bootstrap is off).  Asked
+    before refine_refusal, so that a command line with --boot is refused in --boot's name."""
+    for flag, v in (('--bootSeed', opt.bootSeed), ('--bootBlock', opt.bootBlock), ('--bootLevel', opt.bootLevel),
+                    ('--bootMin', opt.bootMin), ('--bootReps', opt.bootReps or None)):
+        if v is not None and not opt.boot:
+            return '%s needs --boot.' % flag
+    if not opt.boot:
+        return None
+    if opt.boot < 2:
+        return '--boot takes a number of replicates >= 2 (0: off).'
+    if opt.getSpec or opt.getConfig:
+        return '--boot scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if not opt.refine:
+        return '--boot needs --refine: the replicates start at the refined maxima.'
+    if not opt.outfile:
+        return '--boot needs -o: the bootstrap file is written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--boot runs in a single process; multi-rank launches are not supported.'
+    if opt.bootBlock is not None and opt.bootBlock < 1:
+        return '--bootBlock must be >= 1.'
+    if opt.bootLevel is not None and not (0.0 < opt.bootLevel < 1.0):
+        return '--bootLevel takes a number L with 0 < L < 1.'
+    if opt.bootMin is not None and opt.bootMin != opt.bootMin:
+        return '--bootMin takes a number.'
+    return None
 
 
 def support_refusal(opt):
@@ -253,7 +311,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = null_refusal(opt) or profiles_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
+    refused = null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -473,7 +531,7 @@ def main_many(opt, files, stamp=lambda what: None):
             if opt.nullPerm:
                 ctx.set_profiles(0)
         if opt.refine:
-            write_refined(opt, ctx, outfile, sc.test_sites)
+            write_refined(opt, ctx, outfile, sc.test_sites, i)
         if opt.nullPerm:
             # per-file permutations are independent (key of file ordinal i): only the host copies of this file's observed
             # CLR and counts stay until the genome-wide maxima are known

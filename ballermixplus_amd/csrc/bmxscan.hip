@@ -4101,6 +4101,279 @@ __global__ void support_init_kernel(SupportInitParams Q) {
     Q.o_i[task * SUPPORT_NI + 2] = 0;
 }
 
+// ----------------------------------------------------------------------------- block bootstrap
+// Block bootstrap of each refined maximum (bmx_ctx_boot / bmx_ctx_eval_points_weighted; the definition is
+// ballermixplus_amd/boot.py).  One task per (selected window, replicate), window-major: task q * R + r is replicate r of the
+// q-th selected window, so the R tasks of a window -- the same site range, the same first-round tables -- are neighbours in
+// dispatch order.  One workgroup of REFINE_THREADS per task, grid-striding over the tasks.  A task is refine_kernel's compass
+// search (steps 1-4 of the refinement, the same candidate layout, row list, R tables, site-aligned sums and fixed-order
+// reduction) from the refined point, with support_kernel's centre and the grid start's steps, on
+//     T_w = 2 * sum_i w_i log1p(alpha_i R_i),   w_i = boot_weight(key_r, i / B)
+// over the sites of T with w_i > 0.  The weight is computed in the loop: the block index advances with the site index
+// (i += REFINE_THREADS: b += REFINE_THREADS / B, carrying the remainder) so the loop has no division, and a site of weight
+// 0 skips its exp / log1p (a wave skips them where its 64 consecutive sites all have weight 0: whole blocks when B >= 64).
+// In place of nSites the sums carry the total weight of the sites inside each A's cut: T_w is -inf when it is 0.
+// No atomics: a task's result is a function of its window and its key alone.
+__device__ const uint64_t BOOT_THR[20] = {     // floor(2^64 * Poisson(1).cdf(k)), k = 0..19 (boot.py THR)
+    6786177901268885274ull, 13572355802537770549ull, 16965444753172213186ull, 18096474403383694065ull, 18379231815936564285ull,
+    18435783298447138329ull, 18445208545532234003ull, 18446555009401533385ull, 18446723317385195808ull, 18446742018272269410ull,
+    18446743888360976771ull, 18446744058369041076ull, 18446744072536379768ull, 18446744073626175052ull, 18446744073704017573ull,
+    18446744073709207074ull, 18446744073709531418ull, 18446744073709550497ull, 18446744073709551557ull, 18446744073709551613ull};
+
+// w(key, b) of boot.py: the number of thresholds at or below the hash (ascending table: stop at the first one above it)
+__device__ __forceinline__ int boot_weight(uint64_t key, uint64_t b) {
+    const uint64_t h = bmx_mix64(key ^ bmx_mix64(b));
+    int w = 0;
+    while (w < 20 && h >= BOOT_THR[w]) ++w;
+    return w;
+}
+
+struct BootParams {
+    RefineParams P;                             // the model, sites, windows and workspace as refine_kernel has them
+    const uint64_t *keys; int R;                // one key per replicate (point evaluation: one key, R = 1)
+    int64_t block;
+    const int32_t *list; const int64_t *count;  // the selected windows; nullptr: point evaluation of all M at P.pA/px/pab
+    const double *rA, *rx, *rab;                // the refinement's natural values (the centre)
+    double *o_A, *o_x, *o_ab, *o_T, *o_Tc;      // [n_sel R]; point evaluation: o_T[M]
+    int32_t *o_rounds;
+    int64_t *o_wsum;                            // point evaluation: [M] (may be nullptr)
+};
+
+struct BootTask {
+    double Tcentre;
+    long long wsc;                              // total weight at the centre's A
+    long long redw[REFINE_WAVES][3];
+};
+
+__global__ __launch_bounds__(REFINE_THREADS) void boot_kernel(BootParams Q) {
+    extern __shared__ __attribute__((aligned(16))) double lds_ws[];
+    __shared__ RefineState S;
+    __shared__ BootTask U;
+    const RefineParams &P = Q.P;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
+    double *tab = (double *)ws;                                              // [REFINE_TABS][rows]
+    int32_t *list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
+    uint8_t *map = (uint8_t *)(list + P.rows);
+    const int64_t count = Q.list ? *Q.count * Q.R : P.M;
+    const uint64_t B = (uint64_t)Q.block;
+    const uint64_t qB = REFINE_THREADS / B, rB = REFINE_THREADS % B;
+    for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
+        const int64_t t = Q.list ? (int64_t)Q.list[w / Q.R] : w;
+        const uint64_t key = Q.keys[Q.list ? w % Q.R : 0];
+        if (tid == 0) {
+            if (Q.list) {           // support_kernel's centre: the refined point, the grid start's own coordinates and steps
+                const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
+                const double g0[3] = {P.gA[iA], P.gx[ix], P.gab[ia]}, gc[3] = {P.cu[iA], P.gx[ix], P.cv[ia]};
+                S.nat0[0] = Q.rA[t]; S.nat0[1] = Q.rx[t]; S.nat0[2] = Q.rab[t];
+                for (int k = 0; k < 3; ++k) S.c0[k] = S.nat0[k] == g0[k] ? gc[k] : (k == 1 ? S.nat0[k] : log(S.nat0[k]));
+                S.h[0] = P.h0u[iA]; S.h[1] = P.h0x[ix]; S.h[2] = P.h0v[ia];
+            } else {
+                S.nat0[0] = P.pA[t]; S.nat0[1] = P.px[t]; S.nat0[2] = P.pab[t];
+                S.c0[0] = log(P.pA[t]); S.c0[1] = P.px[t]; S.c0[2] = log(P.pab[t]);
+                S.h[0] = S.h[1] = S.h[2] = 0.0;
+            }
+            for (int k = 0; k < 3; ++k) { S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k]; }
+            S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
+            S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
+            S.tg = P.test_gen[t];
+            S.wlo = max(P.win_lo[t], (int64_t)0);
+            S.whi = min(P.win_hi[t], P.N - 1);
+            U.Tcentre = -INFINITY; U.wsc = 0;
+        }
+        __syncthreads();
+        const double tg = S.tg;
+        if (wave == 0) {            // first site at or right of the test position
+            const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
+            if (lane == 0) S.ctr = ctr;
+        }
+        for (;;) {
+            // ---- 1. the round's candidates (thread 0): refine_kernel's
+            if (tid == 0) {
+                for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
+                S.valid[0] = !S.have_c;
+                bool conv = true;
+                for (int k = 0; k < 3; ++k)
+                    if (P.fr[k] && !(S.h[k] < P.tol[k])) conv = false;
+                S.cand = S.rounds < P.max_rounds && !conv;
+                if (S.cand) {
+                    for (int d = 0; d < 6; ++d) {
+                        const int k = d >> 1;
+                        if (!P.fr[k]) continue;
+                        const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
+                        if (v == S.c[k]) continue;
+                        S.valid[d + 1] = 1;
+                        for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
+                        S.cc[d + 1][k] = v;
+                        S.cn[d + 1][k] = refine_nat(S, k, v);
+                    }
+                }
+                bool any = false;
+                for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
+                S.phase = any ? 1 : S.cand ? 2 : 0;
+                S.Aev[0] = S.nat[0];
+                S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
+                S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
+                S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
+                S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
+                for (int q = 1; q < REFINE_TABS; ++q) {
+                    S.need_tab[q] = S.valid[q + 2];
+                    S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
+                    S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
+                }
+            }
+            __syncthreads();
+            const int phase = S.phase;
+            if (phase == 0) break;
+            if (phase == 2) {       // every candidate clamps onto the centre: halve
+                if (tid == 0) {
+                    for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+                    S.rounds++;
+                }
+                __syncthreads();
+                continue;
+            }
+            // ---- the site range of the smallest A of the round, and the rows it references
+            double Amin = S.Aev[0];
+            if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
+            if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
+            if (Amin != S.rangeA) {
+                if (wave == 0) {
+                    const double zc = P.zcut;
+                    const int64_t ctr = S.ctr;
+                    const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
+                    const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
+                    if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
+                }
+                for (int r = tid; r < P.rows; r += REFINE_THREADS) map[r] = 0;
+                __syncthreads();
+                for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) map[P.row[i]] = 1;
+                __syncthreads();
+                int base = 0;
+                for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
+                    const int r = r0 + tid;
+                    const bool on = r < P.rows && map[r];
+                    const unsigned long long m = __ballot(on);
+                    if (lane == 0) S.wtot[wave] = __popcll(m);
+                    __syncthreads();
+                    int off = base;
+                    for (int q = 0; q < wave; ++q) off += S.wtot[q];
+                    if (on) list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+                    for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
+                    __syncthreads();
+                }
+                if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
+                __syncthreads();
+            }
+            // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
+            {
+                int qmask = 0, nq = 0;          // the tables to build, as a bit set (an indexed array would live in scratch here)
+                const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
+                for (int q = 0; q < REFINE_TABS; ++q)
+                    if (S.need_tab[q] && !(q == 0 && keep0)) { qmask |= 1 << q; nq++; }
+                const int nu = S.nused;
+                for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
+                    int m = qmask;
+                    for (int j = it / nu; j > 0; --j) m &= m - 1;
+                    const int q = __ffs(m) - 1, r = list[it % nu];
+                    tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
+                }
+                __syncthreads();
+                if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
+            }
+            // ---- 3. the weighted site sums, aligned to the site index
+            double acc[REFINE_EVALS];
+            long long ws3[3] = {0, 0, 0};
+            for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
+            {
+                int vmask = 0;
+                for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
+                const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
+                const int64_t lo = S.rlo, hi = S.rhi;
+                int64_t i = lo - (lo % REFINE_THREADS) + tid;
+                if (i < lo) i += REFINE_THREADS;
+                uint64_t blk = 0, rem = 0;          // i / B and i % B, carried along with i
+                if (i <= hi) { blk = (uint64_t)i / B; rem = (uint64_t)i % B; }
+                for (; i <= hi; i += REFINE_THREADS) {
+                    const int wi = boot_weight(key, blk);
+                    blk += qB; rem += rB;
+                    if (rem >= B) { rem -= B; blk++; }
+                    if (wi == 0) continue;
+                    const double wd = (double)wi;
+                    const double gi = P.genpos[i];
+                    const int r = P.row[i];
+                    const double d = fabs(gi - tg);
+                    const bool same = gi == tg;
+                    const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
+                    const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
+                    const double a0 = exp(-z0);
+                    if (in0) ws3[0] += wi;
+                    if (in1) ws3[1] += wi;
+                    if (in2) ws3[2] += wi;
+                    if (vmask & 1) { const double v = log1p(a0 * tab[r]); if (in0) acc[0] += wd * v; }
+                    if (vmask & 2) { const double v = log1p(exp(-z1) * tab[r]); if (in1) acc[1] += wd * v; }
+                    if (vmask & 4) { const double v = log1p(exp(-z2) * tab[r]); if (in2) acc[2] += wd * v; }
+                    for (int q = 1; q < REFINE_TABS; ++q)
+                        if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += wd * v; }
+                }
+            }
+            // ---- 4. fixed-order reduction, the decision
+            for (int off = 1; off < WAVE; off <<= 1) {
+                for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
+                for (int k = 0; k < 3; ++k) ws3[k] += __shfl_xor(ws3[k], off);
+            }
+            if (lane == 0) {
+                for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
+                for (int k = 0; k < 3; ++k) U.redw[wave][k] = ws3[k];
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double T[REFINE_EVALS];
+                long long wk[3];
+                for (int k = 0; k < 3; ++k) wk[k] = (U.redw[0][k] + U.redw[1][k]) + (U.redw[2][k] + U.redw[3][k]);
+                for (int e = 0; e < REFINE_EVALS; ++e) {
+                    const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
+                    const long long n = e == 1 ? wk[1] : e == 2 ? wk[2] : wk[0];
+                    const double v = 2.0 * s;
+                    T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
+                }
+                if (S.valid[0]) { S.Tc = T[0]; U.wsc = wk[0]; S.have_c = 1; U.Tcentre = T[0]; }
+                if (S.cand) {
+                    double best = S.Tc;
+                    int bi = -1;
+                    for (int e = 1; e < REFINE_EVALS; ++e)
+                        if (S.valid[e] && T[e] > best) { best = T[e]; bi = e; }
+                    if (bi >= 0) {
+                        for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
+                        S.Tc = best;
+                        U.wsc = bi == 1 ? wk[1] : bi == 2 ? wk[2] : wk[0];
+                    } else {
+                        for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+                    }
+                    S.rounds++;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (Q.list) {
+                Q.o_A[w] = S.nat[0]; Q.o_x[w] = S.nat[1]; Q.o_ab[w] = S.nat[2];
+                Q.o_T[w] = S.Tc; Q.o_Tc[w] = U.Tcentre; Q.o_rounds[w] = S.rounds;
+            } else {
+                Q.o_T[t] = S.Tc;
+                if (Q.o_wsum) Q.o_wsum[t] = U.wsc;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Before the bootstrap: flag[t] = 1 for the windows that were refined with a refined CLR >= min_clr.
+__global__ void boot_init_kernel(const double *clr, const int32_t *rounds, int64_t M, double min_clr, int32_t *flag) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < M) flag[t] = (rounds[t] >= 0 && clr[t] >= min_clr) ? 1 : 0;
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -4268,14 +4541,28 @@ struct ChromSlot {
     DevBuf<double> sp_d;
     DevBuf<int32_t> sp_i;
 
+    // block bootstrap of the refined maxima (bmx_ctx_boot): the selected windows, and per (window, replicate) the final
+    // point, T_w there and at the centre, rounds
+    bool bt_have = false;
+    uint64_t bt_seq = 0;         // scan_seq of the scan whose refinement was bootstrapped
+    int64_t bt_nsel = 0;
+    int32_t bt_R = 0;
+    DevBuf<int32_t> bt_win, bt_rounds;
+    DevBuf<double> bt_A, bt_x, bt_ab, bt_T, bt_Tc;
+
     void release_support() {
         sp_have = false;
         sp_d.release(); sp_i.release();
+    }
+    void release_boot() {
+        bt_have = false;
+        bt_win.release(); bt_rounds.release(); bt_A.release(); bt_x.release(); bt_ab.release(); bt_T.release(); bt_Tc.release();
     }
     void release_refined() {
         rf_have = false;
         rf_clr.release(); rf_A.release(); rf_x.release(); rf_ab.release(); rf_ns.release(); rf_rounds.release();
         release_support();
+        release_boot();
     }
     void release() {
         genpos.release(); rowmax.release(); rowthr.release(); row16.release(); row32.release(); kmom.release(); d_row_of_slot.release();
@@ -4332,6 +4619,8 @@ struct bmx_ctx {
     DevBuf<int64_t> rf_pre;
     DevBuf<double> rf_grid, rf_pts, rf_pT;
     DevBuf<char> rf_slab;
+    DevBuf<uint64_t> bt_keys;    // bootstrap: the replicates' keys, and the weight sums of a weighted point evaluation
+    DevBuf<int64_t> bt_pws;
     std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
@@ -4485,6 +4774,7 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
+    c->bt_keys.release(); c->bt_pws.release();
     dfree(c->d_prof);
     dfree(c->d_status);
     for (int k = 0; k < 2; k++) {
@@ -5712,6 +6002,7 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     s->rf_have = true;
     s->rf_seq = s->scan_seq;
     s->release_support();
+    s->release_boot();
     return BMX_OK;
 }
 
@@ -5813,6 +6104,143 @@ int bmx_ctx_fetch_support(bmx_ctx *c, double *end, double *witness, double *witn
         if (T_star) T_star[t] = ts;
         if (T_best) T_best[t] = tb;
     }
+    return BMX_OK;
+}
+
+}  // extern "C"
+
+/* ---- block bootstrap (ballermixplus_amd/boot.py holds the definition: weights, objective, one replicate) ---- */
+
+namespace {
+
+int boot_launch(bmx_ctx *c, BootParams &Q, int64_t work) {
+    int64_t blocks = 0;
+    int rc = refine_workspace(c, Q.P, work, blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(boot_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), Q.P.ws_lds ? (size_t)Q.P.ws_bytes : 0, c->stream, Q);
+    HIP_TRY(hipGetLastError());
+    return BMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmx_ctx_eval_points_weighted(bmx_ctx *c, uint64_t key, int64_t block, const double *A, const double *x, const double *abeta,
+                                 double *T_out, int64_t *wsum_out) {
+    if (!c || !A || !x || !abeta || !T_out) return fail(BMX_E_INVALID, "NULL argument");
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_sites || !s->has_tests)
+        return fail(BMX_E_STATE, "model, sites and tests must be set before eval_points_weighted");
+    if (block < 1) return fail(BMX_E_INVALID, "eval_points_weighted: block must be >= 1");
+    const int64_t M = s->M;
+    for (int64_t t = 0; t < M; t++)
+        if (!(A[t] > 0.0) || !(x[t] > 0.0 && x[t] < 1.0) || !(abeta[t] > 0.0) || !std::isfinite(A[t]) || !std::isfinite(abeta[t]))
+            return fail(BMX_E_INVALID, "eval_points_weighted: A > 0, 0 < x < 1 and alpha_beta > 0 (finite) at every point");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    BootParams Q;
+    int rc = refine_setup(c, s, Q.P, 0);
+    if (rc) return rc;
+    HIP_TRY(c->rf_pts.ensure((size_t)3 * M));
+    HIP_TRY(hipMemcpyAsync(c->rf_pts.p, A, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + M, x, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + 2 * M, abeta, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->rf_pT.ensure((size_t)M));
+    HIP_TRY(c->bt_pws.ensure((size_t)M));
+    HIP_TRY(c->bt_keys.ensure(1));
+    HIP_TRY(hipMemcpyAsync(c->bt_keys.p, &key, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    Q.P.pA = c->rf_pts.p; Q.P.px = c->rf_pts.p + M; Q.P.pab = c->rf_pts.p + 2 * M;
+    Q.keys = c->bt_keys.p; Q.R = 1; Q.block = block;
+    Q.list = nullptr; Q.count = nullptr; Q.rA = Q.rx = Q.rab = nullptr;
+    Q.o_A = Q.o_x = Q.o_ab = Q.o_Tc = nullptr; Q.o_rounds = nullptr;
+    Q.o_T = c->rf_pT.p; Q.o_wsum = c->bt_pws.p;
+    if ((rc = boot_launch(c, Q, M))) return rc;
+    HIP_TRY(hipMemcpyAsync(T_out, c->rf_pT.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (wsum_out) HIP_TRY(hipMemcpyAsync(wsum_out, c->bt_pws.p, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));     // (also: `key` leaves scope here)
+    return BMX_OK;
+}
+
+int bmx_ctx_boot(bmx_ctx *c, const uint64_t *keys, int32_t R, int64_t block, double min_clr) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_tests || !s->timed || !s->rf_have || s->rf_seq != s->scan_seq)
+        return fail(BMX_E_STATE, "boot: no refinement of the slot's last scan (call bmx_ctx_refine after the scan)");
+    if (!keys || R < 1) return fail(BMX_E_INVALID, "boot: at least one replicate key is needed");
+    if (block < 1) return fail(BMX_E_INVALID, "boot: block must be >= 1");
+    if (min_clr != min_clr) return fail(BMX_E_INVALID, "boot: min_clr is NaN");
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t M = s->M;
+    s->release_boot();
+    BootParams Q;
+    int rc = refine_setup(c, s, Q.P, 256);
+    if (rc) return rc;
+    // the selection: its count is needed on the host to size the results (this waits for the refinement)
+    HIP_TRY(c->rf_flag.ensure((size_t)M));
+    HIP_TRY(c->rf_pre.ensure((size_t)M + 1));
+    HIP_TRY(s->bt_win.ensure((size_t)M));
+    const unsigned nb = (unsigned)((M + 255) / 256);
+    hipLaunchKernelGGL(boot_init_kernel, dim3(nb), dim3(256), 0, c->stream, (const double *)s->rf_clr.p,
+                       (const int32_t *)s->rf_rounds.p, M, min_clr, c->rf_flag.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rf_flag.p, M, c->rf_pre.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)c->rf_flag.p,
+                       (const int64_t *)c->rf_pre.p, M, s->bt_win.p);
+    HIP_TRY(hipGetLastError());
+    int64_t nsel = 0;
+    HIP_TRY(hipMemcpyAsync(&nsel, c->rf_pre.p + M, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (nsel * (int64_t)R > BMX_BOOT_MAX_RESULTS)
+        return fail(BMX_E_LIMIT, "boot: " + std::to_string(nsel) + " windows x " + std::to_string(R) + " replicates exceed " +
+                    std::to_string((long long)BMX_BOOT_MAX_RESULTS) + " results: raise --bootMin (min_clr) or lower the replicates");
+    const size_t nt = (size_t)nsel * (size_t)R;
+    HIP_TRY(s->bt_A.ensure(nt)); HIP_TRY(s->bt_x.ensure(nt)); HIP_TRY(s->bt_ab.ensure(nt));
+    HIP_TRY(s->bt_T.ensure(nt)); HIP_TRY(s->bt_Tc.ensure(nt)); HIP_TRY(s->bt_rounds.ensure(nt));
+    if ((rc = upload(c->bt_keys, keys, (size_t)R, c->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));       // the caller's keys may go away after the call
+    s->bt_nsel = nsel; s->bt_R = R; s->bt_seq = s->scan_seq;
+    if (nt) {
+        Q.P.lin = s->lin.p; Q.P.clr = s->clr.p;
+        Q.keys = c->bt_keys.p; Q.R = R; Q.block = block;
+        Q.list = s->bt_win.p; Q.count = c->rf_pre.p + M;
+        Q.rA = s->rf_A.p; Q.rx = s->rf_x.p; Q.rab = s->rf_ab.p;
+        Q.o_A = s->bt_A.p; Q.o_x = s->bt_x.p; Q.o_ab = s->bt_ab.p; Q.o_T = s->bt_T.p; Q.o_Tc = s->bt_Tc.p;
+        Q.o_rounds = s->bt_rounds.p; Q.o_wsum = nullptr;
+        if ((rc = boot_launch(c, Q, (int64_t)nt))) return rc;
+    }
+    s->bt_have = true;
+    return BMX_OK;
+}
+
+int bmx_ctx_boot_count(bmx_ctx *c, int64_t *n_sel, int32_t *R) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->bt_have || s->bt_seq != s->scan_seq)
+        return fail(BMX_E_STATE, "no bootstrap of the slot's last scan: call bmx_ctx_boot after bmx_ctx_refine");
+    if (n_sel) *n_sel = s->bt_nsel;
+    if (R) *R = s->bt_R;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double *abeta, double *T, double *T_centre,
+                       int32_t *rounds) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->bt_have || s->bt_seq != s->scan_seq)
+        return fail(BMX_E_STATE, "no bootstrap of the slot's last scan: call bmx_ctx_boot after bmx_ctx_refine");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)s->bt_nsel, nt = n * (size_t)s->bt_R;
+    if (!nt) return BMX_OK;
+    if (window) HIP_TRY(hipMemcpy(window, s->bt_win.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (A) HIP_TRY(hipMemcpy(A, s->bt_A.p, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (x) HIP_TRY(hipMemcpy(x, s->bt_x.p, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (abeta) HIP_TRY(hipMemcpy(abeta, s->bt_ab.p, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (T) HIP_TRY(hipMemcpy(T, s->bt_T.p, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_centre) HIP_TRY(hipMemcpy(T_centre, s->bt_Tc.p, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (rounds) HIP_TRY(hipMemcpy(rounds, s->bt_rounds.p, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BMX_OK;
 }
 

@@ -102,6 +102,7 @@ class Context:
     def set_model(self, model, As):
         A = _lib.f64(As)
         self.model, self.nA = model, len(A)
+        self.As = A.copy()
         self._slot_M = {}
         self.M = 0
         _lib.check(self._L.bmx_ctx_set_model(self._h, C.byref(model.c), _lib.as_dp(A), len(A)))
@@ -313,6 +314,37 @@ class Context:
                                                  d(out['outside_T']), i(out['censored']), d(out['T_star']), d(out['T_best']),
                                                  i(out['rounds']), i(out['evals'])))
         out['lo'], out['hi'] = out['end'][:, :, 0], out['end'][:, :, 1]
+        return out
+
+    def eval_points_weighted(self, key, block, A, x, abeta):
+        """T_w (f64[M], -inf where no site of the window has a positive weight) and the sum of the weights of the window's
+        sites at that A (i64[M]) of every test site of the selected slot at the point (A[t], x[t], abeta[t]), under the
+        block-bootstrap weights of (key, block) -- the bootstrap's arithmetic (ballermixplus_amd/boot.py).  Scalars broadcast."""
+        M = self.M
+        A, x, abeta = (_lib.f64(np.broadcast_to(np.asarray(v, dtype=np.float64), (M,))) for v in (A, x, abeta))
+        T = np.empty(M, dtype=np.float64)
+        ws = np.empty(M, dtype=np.int64)
+        _lib.check(self._L.bmx_ctx_eval_points_weighted(self._h, C.c_uint64(int(key) & ((1 << 64) - 1)), int(block), _lib.as_dp(A),
+                                                        _lib.as_dp(x), _lib.as_dp(abeta), _lib.as_dp(T), _lib.as_lp(ws)))
+        return T, ws
+
+    def boot(self, keys, block=1, min_clr=0.0):
+        """Block bootstrap (ballermixplus_amd/boot.py) of the refined maxima of the selected slot's last refinement: one
+        replicate per key (boot.replicate_key) for every window with a refined CLR >= min_clr."""
+        k = np.array([int(v) & ((1 << 64) - 1) for v in keys], dtype=np.uint64)
+        _lib.check(self._L.bmx_ctx_boot(self._h, k.ctypes.data_as(C.POINTER(C.c_uint64)), len(k), int(block), float(min_clr)))
+
+    def fetch_boot(self):
+        """The last bootstrap: 'window' i32[n_sel] (the bootstrapped test sites, ascending), 'A', 'x', 'abeta', 'T',
+        'T_centre' f64[n_sel, R] and 'rounds' i32[n_sel, R]; T = -inf: the replicate is not ok."""
+        n, R = C.c_int64(), C.c_int32()
+        _lib.check(self._L.bmx_ctx_boot_count(self._h, C.byref(n), C.byref(R)))
+        n, R = n.value, R.value
+        out = {'window': np.empty(n, dtype=np.int32), 'rounds': np.empty((n, R), dtype=np.int32)}
+        out.update({k: np.empty((n, R), dtype=np.float64) for k in ('A', 'x', 'abeta', 'T', 'T_centre')})
+        d = _lib.as_dp
+        _lib.check(self._L.bmx_ctx_fetch_boot(self._h, _lib.as_ip(out['window']), d(out['A']), d(out['x']), d(out['abeta']),
+                                              d(out['T']), d(out['T_centre']), _lib.as_ip(out['rounds'])))
         return out
 
     def surface(self, test_gen, win_lo, win_hi):

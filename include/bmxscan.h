@@ -283,6 +283,35 @@ int bmx_ctx_support(bmx_ctx *c, double drop, double min_clr);
 int bmx_ctx_fetch_support(bmx_ctx *c, double *end, double *witness, double *witness_T, double *outside, double *outside_T,
                           int32_t *censored, double *T_star, double *T_best, int32_t *rounds, int32_t *evals);
 
+/* ---- block bootstrap of each refined maximum (opt-in; the CLI's --boot; ballermixplus_amd/boot.py) ----------------------
+ * Replicate r re-weights the sites in blocks of `block` consecutive sites (block b = site index / block) with Poisson(1)
+ * weights w(key_r, b) in 0..20 drawn from a counter-based hash by integer comparisons, and repeats the refinement's compass
+ * search from the refined point on T_w = 2 * sum_i w_i log1p(alpha_i R_i) over the sites of T that have w_i > 0 (-inf: no such
+ * site, or a sum that is not finite).  Centre, initial steps, tolerances, rounds, free coordinates and hull are those of the
+ * support intervals' centre and of the refinement.  One workgroup per (window, replicate); a result depends on its window
+ * and its key alone.  A local search: a replicate does not find a higher maximum elsewhere on its surface. */
+/* T_w at a caller-given point per test site of the selected slot under the weights of (key, block): A/x/abeta[M], T_out[M],
+ * wsum_out[M] (may be NULL) = the sum of the weights of the window's sites at that A.  block >= 1, else BMX_E_INVALID.
+ * Blocks. */
+int bmx_ctx_eval_points_weighted(bmx_ctx *c, uint64_t key, int64_t block, const double *A, const double *x, const double *abeta,
+                                 double *T_out, int64_t *wsum_out);
+/* Bootstrap the windows of the selected slot's last refinement (bmx_ctx_refine after the last scan; else BMX_E_STATE) that were
+ * refined and have a refined CLR >= min_clr: R replicates each, replicate r under keys[r].  R < 1, block < 1 or a NaN min_clr:
+ * BMX_E_INVALID.  At most BMX_BOOT_MAX_RESULTS (window, replicate) results (44 bytes each on the device): more is BMX_E_LIMIT,
+ * to be met with a higher min_clr (the CLI's --bootMin) or fewer replicates.  The call waits for the refinement to learn the
+ * number of selected windows; the bootstrap itself is asynchronous on the context's stream.  A new scan, refinement,
+ * set_tests / set_sites / set_model drop the results. */
+#define BMX_BOOT_MAX_RESULTS (1LL << 26)
+int bmx_ctx_boot(bmx_ctx *c, const uint64_t *keys, int32_t R, int64_t block, double min_clr);
+/* *n_sel (may be NULL) = the number of windows of the last bootstrap, *R (may be NULL) = its replicates.  BMX_E_STATE
+ * without one. */
+int bmx_ctx_boot_count(bmx_ctx *c, int64_t *n_sel, int32_t *R);
+/* window[n_sel]: the bootstrapped test sites, ascending.  Per (window q, replicate r) at q * R + r, n_sel * R of each: the final
+ * point A, x, abeta (natural units), T (T_w there; -inf: the replicate is not ok), T_centre (T_w at the refined point, the
+ * search's first evaluation) and rounds (compass rounds run).  Blocks.  Any pointer may be NULL. */
+int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double *abeta, double *T, double *T_centre,
+                       int32_t *rounds);
+
 /* ---- the final gather over RCCL, inside the library (north_star: "only a final RCCL gather over xGMI") --
  * One process per GPU, each with its own context.  Rank 0 makes an id (bmx_comm_unique_id: 128 bytes) and hands it to the other
  * ranks by whatever channel the caller has (MPI, a file, a socket, torch's store); every rank then calls bmx_comm_create with
