@@ -92,6 +92,12 @@ PROTOTYPES = {
     'bmx_ctx_boot': (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, C.c_int64, C.c_double]),
     'bmx_ctx_boot_count': (C.c_int, [_vp, _lp, _ip]),
     'bmx_ctx_fetch_boot': (C.c_int, [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip]),
+    'bmx_ctx_peaks': (C.c_int, [_vp, C.c_double, C.c_double, C.c_double]),
+    'bmx_ctx_peaks_track': (C.c_int, [_vp, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_double]),
+    'bmx_ctx_peak_count': (C.c_int, [_vp, _lp, _lp]),
+    'bmx_ctx_fetch_peaks': (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    'bmx_ctx_peaks_ms': (C.c_int, [_vp, _dp]),
+    'bmx_ctx_refine_at_peaks': (C.c_int, [_vp, C.c_int32]),
     'bmx_comm_unique_id': (C.c_int, [C.c_char_p]),
     'bmx_comm_create': (C.c_int, [C.POINTER(_vp), _vp, C.c_char_p, C.c_int32, C.c_int32]),
     'bmx_comm_destroy': (None, [_vp]),

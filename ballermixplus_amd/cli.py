@@ -26,6 +26,12 @@ Additions (do not change any reference command line):
                     B consecutive sites and repeat the search from the refined point (windows with refined CLR >= C); writes
                     <out>.boot.txt (percentile ends at level L, standard deviations) and with --bootReps <out>.boot.reps.txt
                     next to each output file.
+  --peaks G [--peakMin C] [--peakExtent F] [--atPeaks]     peaks of the CLR track (ballermixplus_amd/peaks.py): the rows that no row
+                    within distance G beats (CLR >= C), each with its extent (rows with CLR >= F * apex CLR, inside the saddles
+                    to its neighbours); writes <out>.peaks.txt next to each output file (several files: also <dir>/peaks.txt or
+                    the -o pattern with `peaks`, genome-wide).  --atPeaks (with --refine): refine only the apexes, and so compute
+                    --support / --boot for them only.  `python -m ballermixplus_amd.peaks OUT.txt --peaks G` calls peaks again on
+                    an existing output.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -138,7 +144,62 @@ def build_parser():
     parser.add_argument('--bootReps', dest='bootReps', action='store_true', default=False,
                         help='MI355X build only, with --boot: also write every replicate of every bootstrapped window to '
                              '<out>.boot.reps.txt')
+    parser.add_argument('--peaks', dest='peaks', type=float, default=None,
+                        help='MI355X build only: call peaks on the CLR track with separation G, in the units the scan measures '
+                             'distance in (the genPos column): a row is an apex when no row within G has a higher CLR.  Writes '
+                             '<out>.peaks.txt next to each output file: one row per apex with its extent, the CLR at the saddles '
+                             'to its neighbours and, with --nullPerm, its p-values.  No default: G states what "one locus" means; '
+                             'a window at A_hat reaches 18.42 / A_hat')
+    parser.add_argument('--peakMin', dest='peakMin', type=float, default=None,
+                        help='MI355X build only, with --peaks: only apexes with CLR >= this value (default 0)')
+    parser.add_argument('--peakExtent', dest='peakExtent', type=float, default=None,
+                        help='MI355X build only, with --peaks: a peak extends over the rows around its apex with CLR >= F * apex '
+                             'CLR, 0 < F <= 1 (default 0.5: the width at half maximum)')
+    parser.add_argument('--atPeaks', dest='atPeaks', action='store_true', default=False,
+                        help='MI355X build only, with --peaks and --refine: refine only the apexes (--refineMin still applies); '
+                             '--support and --boot follow, as they only touch refined windows')
     return parser
+
+
+def peaks_refusal(opt):
+    """The message that refuses a --peaks / --peakMin / --peakExtent / --atPeaks command line, or None when it can run (or peak
+    calling is off).  Asked before the other refusals, so that a command line with --peaks is refused in this feature's name."""
+    for flag, v in (('--peakMin', opt.peakMin), ('--peakExtent', opt.peakExtent), ('--atPeaks', opt.atPeaks or None)):
+        if v is not None and opt.peaks is None:
+            return '%s needs --peaks.' % flag
+    if opt.peaks is None:
+        return None
+    from . import peaks
+    refused = peaks.value_refusal(opt.peaks, opt.peakMin, opt.peakExtent)
+    if refused:
+        return refused
+    if opt.getSpec or opt.getConfig:
+        return '--peaks scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if not opt.outfile:
+        return '--peaks needs -o: the peak file is written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--peaks runs in a single process; multi-rank launches are not supported.'
+    if opt.atPeaks and not opt.refine:
+        return '--atPeaks needs --refine: it restricts the refinement to the apexes.'
+    return None
+
+
+def call_peaks(opt, ctx, ts):
+    """The peaks of one file whose observed scan has just run on ctx's selected slot (before anything scans the slot again):
+    (peaks, line of every track row in the main output or None for line t + 1)."""
+    from . import peaks
+    if len(ts) == 0:
+        return peaks.empty(), None
+    pk = ctx.peaks(opt.peaks, opt.peakMin if opt.peakMin is not None else 0.0,
+                   opt.peakExtent if opt.peakExtent is not None else peaks.FRAC)
+    return pk, (np.asarray(ts.order, dtype=np.int64) + 1 if ts.na_rows else None)
+
+
+def write_peaks(outfile, called, with_null):
+    """<outfile>.peaks.txt, once all its columns are known (with the null: after its p-value file).  Returns its rows."""
+    from . import peaks
+    pk, line_of_row = called
+    return peaks.write_peaks(peaks.output_name(outfile), outfile, pk, line_of_row, outfile + '.pval.txt' if with_null else None)
 
 
 def refine_refusal(opt):
@@ -311,7 +372,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
+    refused = peaks_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -400,6 +461,10 @@ def main(argv=None):
         write_profiles(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites)
         Sel_Probs.ctx.set_profiles(0)
         stamp('profiles')
+    if opt.peaks is not None:
+        called = call_peaks(opt, Sel_Probs.ctx, sc.test_sites)
+        Sel_Probs.ctx.refine_at_peaks(opt.atPeaks)
+        stamp('peaks')
     if opt.refine:
         write_refined(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites)
         stamp('refine')
@@ -407,6 +472,9 @@ def main(argv=None):
         got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
         finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
         stamp('permutation null')
+    if opt.peaks is not None:
+        n = len(write_peaks(opt.outfile, called, bool(opt.nullPerm)))
+        say(f'\n{datetime.now()}. Peaks: {n} (separation {opt.peaks!r}) -> {opt.outfile}.peaks.txt')
     world.finish()
     say(f'\n{datetime.now()}. Pipeline finished.')
 
@@ -505,6 +573,9 @@ def main_many(opt, files, stamp=lambda what: None):
     tables = 0
     kernel_ms = 0.0
     null_files = []
+    peak_files = []
+    if opt.peaks is not None:
+        ctx.refine_at_peaks(opt.atPeaks)
     for i, (infile, outfile) in enumerate(zip(files, outs)):
         th.join()
         got = nxt.pop(i)
@@ -530,6 +601,8 @@ def main_many(opt, files, stamp=lambda what: None):
             write_profiles(opt, ctx, sel, outfile, sc.test_sites)
             if opt.nullPerm:
                 ctx.set_profiles(0)
+        if opt.peaks is not None:
+            peak_files.append((infile, outfile, call_peaks(opt, ctx, sc.test_sites)))
         if opt.refine:
             write_refined(opt, ctx, outfile, sc.test_sites, i)
         if opt.nullPerm:
@@ -539,6 +612,12 @@ def main_many(opt, files, stamp=lambda what: None):
             stamp('file %d of %d: permutation null' % (i + 1, len(files)))
     if opt.nullPerm:
         finish_null(opt, null_files, null_name(opt.outfile, 'null'), say)
+    if opt.peaks is not None:
+        # (a few arrays per apex were kept per file; the tables wait for the null's p-value files)
+        from . import peaks
+        ptabs = [(os.path.basename(infile), write_peaks(outfile, called, bool(opt.nullPerm))) for infile, outfile, called in peak_files]
+        peaks.write_genome(null_name(opt.outfile, 'peaks'), ptabs)
+        say(f'\n{datetime.now()}. Peaks: {sum(len(r) for _, r in ptabs)} (separation {opt.peaks!r}) -> {null_name(opt.outfile, "peaks")}')
     world.finish()
     say(f'\n{datetime.now()}. Pipeline finished: {len(files)} files, selection table built {tables} time(s), '
         f'scan kernels {kernel_ms / 1e3:.2f} s.')

@@ -3753,9 +3753,11 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(RefineParams P) 
 }
 
 // Before a refinement: every window's row is the scan's (A, x, alpha_beta of its lin; NaN without a grid result), rounds -1,
-// and flag[t] = 1 for the windows to refine (lin >= 0, clr >= min_clr).
+// and flag[t] = 1 for the windows to refine (lin >= 0, clr >= min_clr and, under bmx_ctx_refine_at_peaks, an apex of the slot's
+// peak call: apex != nullptr).
 struct RefineInitParams {
     const double *clr; const int32_t *lin, *nsites;
+    const int32_t *apex;
     const double *gA, *gx, *gab;
     int npairs, nab;
     int64_t M;
@@ -3770,7 +3772,7 @@ __global__ void refine_init_kernel(RefineInitParams Q) {
     if (t >= Q.M) return;
     const int L = Q.lin[t];
     const double clr = Q.clr[t];
-    Q.flag[t] = (L >= 0 && clr >= Q.min_clr) ? 1 : 0;
+    Q.flag[t] = (L >= 0 && clr >= Q.min_clr && (!Q.apex || Q.apex[t])) ? 1 : 0;
     Q.o_clr[t] = clr;
     Q.o_ns[t] = Q.nsites[t];
     Q.o_rounds[t] = -1;
@@ -4374,6 +4376,185 @@ __global__ void boot_init_kernel(const double *clr, const int32_t *rounds, int64
     if (t < M) flag[t] = (rounds[t] >= 0 && clr[t] >= min_clr) ? 1 : 0;
 }
 
+// ----------------------------------------------------------------------------- peaks
+// Peak calling on a CLR track (bmx_ctx_peaks / bmx_ctx_peaks_track; the definition is ballermixplus_amd/peaks.py): rows
+// t = 0 .. M-1 with non-decreasing positions g and values c.  Every comparison is an exact FP64 comparison and the only
+// arithmetic is the two subtractions of the radius predicate and the one multiplication of the extent's threshold, so the
+// host restatement and these kernels agree exactly.
+//   peak_tile_kernel     per tile of PEAK_TILE = 64 consecutive rows (one wave): its maximum and the first row that attains it
+//   peak_apex_kernel     per row with c > 0 and c >= min_clr: its index range [lo, hi] by two binary searches on g with the exact
+//                        predicate, then "is any row of the range ahead of me" -- (larger c, or equal c and a lower row) -- against
+//                        the tile maxima of the tiles wholly inside the range and row by row in the two partial tiles at its ends
+//   prefix_kernel + refine_compact_kernel     the apex rows in row order
+//   peak_saddle_kernel   per gap between consecutive apexes (one workgroup, grid-stride): the first row of smallest c strictly inside
+//   peak_extent_kernel   per apex (one wave): the run of rows with c >= frac * c_apex around it, cut inside the saddles
+// Gaps and extents are very uneven in length (a chromosome has long quiet stretches): a workgroup strides over its gap and a
+// wave over its extent 64 rows at a time; the imbalance between workgroups is accepted.
+constexpr int PEAK_TILE = 64;
+constexpr int PEAK_THREADS = 256;             // 4 tiles per workgroup
+constexpr int PEAK_LDS_TILES = 1024;          // tile maxima a workgroup stages (12 KiB): 65536 rows around its own
+
+// (value, row): `a` is ahead of `b` when its value is larger, or equal with a lower row
+__device__ __forceinline__ bool peak_ahead(double av, int32_t ai, double bv, int32_t bi) { return av > bv || (av == bv && ai < bi); }
+
+__global__ __launch_bounds__(PEAK_THREADS) void peak_tile_kernel(const double *__restrict__ c, int64_t M, double *__restrict__ tmax,
+                                                                  int32_t *__restrict__ tfirst) {
+    const int64_t t = (int64_t)blockIdx.x * PEAK_THREADS + threadIdx.x;
+    double v = t < M ? c[t] : -INFINITY;
+    int32_t i = t < M ? (int32_t)t : INT32_MAX;
+    for (int off = WAVE / 2; off; off >>= 1) {
+        const double ov = __shfl_xor(v, off, WAVE);
+        const int32_t oi = __shfl_xor(i, off, WAVE);
+        if (peak_ahead(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0 && t < M) { tmax[t / PEAK_TILE] = v; tfirst[t / PEAK_TILE] = i; }
+}
+
+struct PeakParams {
+    const double *g, *c;
+    int64_t M;
+    double sep, min_clr;
+    const double *tmax; const int32_t *tfirst;
+    int32_t *flag;
+};
+
+__global__ __launch_bounds__(PEAK_THREADS) void peak_apex_kernel(PeakParams Q) {
+    __shared__ double s_max[PEAK_LDS_TILES];
+    __shared__ int32_t s_first[PEAK_LDS_TILES];
+    __shared__ int s_lo, s_hi;
+    const int tid = threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * PEAK_THREADS + tid;
+    const int64_t M = Q.M;
+    if (tid == 0) { s_lo = INT32_MAX; s_hi = -1; }
+    __syncthreads();
+    double ct = 0.0;
+    bool cand = false;
+    if (t < M) {
+        ct = Q.c[t];
+        cand = ct > 0.0 && ct >= Q.min_clr;
+    }
+    int64_t lo = t, hi = t;
+    int f0 = 0, f1 = -1;            // the tiles wholly inside [lo, hi]
+    if (cand) {
+        const double gt = Q.g[t];
+        int64_t a = 0, b = t;       // lo: the lowest row s <= t with g_t - g_s <= sep (t itself qualifies: sep >= 0)
+        while (a < b) {
+            const int64_t mid = (a + b) >> 1;
+            if (gt - Q.g[mid] <= Q.sep) b = mid; else a = mid + 1;
+        }
+        lo = a;
+        a = t; b = M - 1;           // hi: the highest row s >= t with g_s - g_t <= sep
+        while (a < b) {
+            const int64_t mid = (a + b + 1) >> 1;
+            if (Q.g[mid] - gt <= Q.sep) a = mid; else b = mid - 1;
+        }
+        hi = a;
+        f0 = (int)((lo + PEAK_TILE - 1) / PEAK_TILE);
+        f1 = hi == M - 1 ? (int)((M - 1) / PEAK_TILE) : (int)((hi + 1) / PEAK_TILE) - 1;     // the last tile ends at row M - 1
+        if (f0 <= f1) { atomicMin(&s_lo, f0); atomicMax(&s_hi, f1); }
+    }
+    __syncthreads();
+    // the tile maxima the workgroup's rows share go through LDS: the tiles its ranges cover, at most PEAK_LDS_TILES of them
+    // around its own four; what lies beyond is read from memory
+    const bool any = s_hi >= 0;
+    const int w0 = any ? max(s_lo, (int)blockIdx.x * (PEAK_THREADS / PEAK_TILE) - PEAK_LDS_TILES / 2) : 0;
+    const int w1 = any ? min(s_hi, w0 + PEAK_LDS_TILES - 1) : -1;
+    for (int T = w0 + tid; T <= w1; T += PEAK_THREADS) { s_max[T - w0] = Q.tmax[T]; s_first[T - w0] = Q.tfirst[T]; }
+    __syncthreads();
+    if (t >= M) return;
+    int apex = 0;
+    if (cand) {
+        const int32_t ti = (int32_t)t;
+        bool beaten = false;
+        // whole tiles, outwards from the row's own: a tile's maximum beats the row unless it is the row itself -- equal
+        // values count only from a lower row, which is why the tiles keep the FIRST row of their maximum
+        int dn = min(max((int)(t / PEAK_TILE), f0), f1), up = dn + 1;
+        while (!beaten && (dn >= f0 || up <= f1)) {
+            if (dn >= f0) {
+                const bool in = dn >= w0 && dn <= w1;
+                beaten = peak_ahead(in ? s_max[dn - w0] : Q.tmax[dn], in ? s_first[dn - w0] : Q.tfirst[dn], ct, ti);
+                --dn;
+            }
+            if (!beaten && up <= f1) {
+                const bool in = up >= w0 && up <= w1;
+                beaten = peak_ahead(in ? s_max[up - w0] : Q.tmax[up], in ? s_first[up - w0] : Q.tfirst[up], ct, ti);
+                ++up;
+            }
+        }
+        // the partial tiles at the two ends (the whole range when it holds no whole tile: fewer than 127 rows)
+        const int64_t e0 = f0 <= f1 ? (int64_t)f0 * PEAK_TILE - 1 : hi;
+        for (int64_t s = lo; !beaten && s <= e0; ++s) beaten = s != t && peak_ahead(Q.c[s], (int32_t)s, ct, ti);
+        if (f0 <= f1)
+            for (int64_t s = (int64_t)(f1 + 1) * PEAK_TILE; !beaten && s <= hi; ++s) beaten = s != t && peak_ahead(Q.c[s], (int32_t)s, ct, ti);
+        apex = beaten ? 0 : 1;
+    }
+    Q.flag[t] = apex;
+}
+
+// sad[0] = sad[K] = -1; sad[i + 1] = the saddle between apex i and apex i + 1 (-1: adjacent rows)
+__global__ __launch_bounds__(PEAK_THREADS) void peak_saddle_kernel(const double *__restrict__ c, const int32_t *__restrict__ row, int64_t K,
+                                                                    int32_t *__restrict__ sad) {
+    __shared__ double s_v[PEAK_THREADS / WAVE];
+    __shared__ int32_t s_i[PEAK_THREADS / WAVE];
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0 && tid == 0) { sad[0] = -1; sad[K] = -1; }
+    for (int64_t i = blockIdx.x; i + 1 < K; i += gridDim.x) {
+        const int64_t a = row[i], b = row[i + 1];
+        double v = 0.0;
+        int32_t idx = -1;           // -1: no row seen
+        for (int64_t s = a + 1 + tid; s < b; s += PEAK_THREADS) {
+            const double cs = c[s];
+            if (idx < 0 || cs < v) { v = cs; idx = (int32_t)s; }
+        }
+        for (int off = WAVE / 2; off; off >>= 1) {
+            const double ov = __shfl_xor(v, off, WAVE);
+            const int32_t oi = __shfl_xor(idx, off, WAVE);
+            if (oi >= 0 && (idx < 0 || ov < v || (ov == v && oi < idx))) { v = ov; idx = oi; }
+        }
+        if ((tid & (WAVE - 1)) == 0) { s_v[tid / WAVE] = v; s_i[tid / WAVE] = idx; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < PEAK_THREADS / WAVE; w++) {
+                const double ov = s_v[w];
+                const int32_t oi = s_i[w];
+                if (oi >= 0 && (idx < 0 || ov < v || (ov == v && oi < idx))) { v = ov; idx = oi; }
+            }
+            sad[i + 1] = idx;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(PEAK_THREADS) void peak_extent_kernel(const double *__restrict__ c, int64_t M, const int32_t *__restrict__ row,
+                                                                    const int32_t *__restrict__ sad, int64_t K, double frac,
+                                                                    int32_t *__restrict__ o_lo, int32_t *__restrict__ o_hi) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t i = (int64_t)blockIdx.x * (PEAK_THREADS / WAVE) + threadIdx.x / WAVE;       // wave-uniform
+    if (i >= K) return;
+    const int64_t a = row[i];
+    const double thr = frac * c[a];
+    // the region stays strictly inside the saddles; adjacent apexes have none between them and end at their own rows
+    const int64_t lim_lo = i == 0 ? 0 : (sad[i] >= 0 ? (int64_t)sad[i] + 1 : (int64_t)row[i - 1] + 1);
+    const int64_t lim_hi = i == K - 1 ? M - 1 : (sad[i + 1] >= 0 ? (int64_t)sad[i + 1] - 1 : (int64_t)row[i + 1] - 1);
+    int64_t hi = a;
+    for (int64_t pos = a + 1;; pos += WAVE) {
+        const int64_t s = pos + lane;
+        const unsigned long long ok = __ballot(s <= lim_hi && c[s <= lim_hi ? s : a] >= thr);
+        if (ok == ~0ULL) { hi = pos + WAVE - 1; continue; }
+        hi = pos + __builtin_ctzll(~ok) - 1;
+        break;
+    }
+    int64_t lo = a;
+    for (int64_t pos = a - 1;; pos -= WAVE) {
+        const int64_t s = pos - lane;
+        const unsigned long long ok = __ballot(s >= lim_lo && c[s >= lim_lo ? s : a] >= thr);
+        if (ok == ~0ULL) { lo = pos - WAVE + 1; continue; }
+        lo = pos - __builtin_ctzll(~ok) + 1;
+        break;
+    }
+    if (lane == 0) { o_lo[i] = (int32_t)lo; o_hi[i] = (int32_t)hi; }
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -4550,6 +4731,18 @@ struct ChromSlot {
     DevBuf<int32_t> bt_win, bt_rounds;
     DevBuf<double> bt_A, bt_x, bt_ab, bt_T, bt_Tc;
 
+    // peaks of the last peak call on this slot (bmx_ctx_peaks / bmx_ctx_peaks_track): apex flags of the track's pk_M rows, and per
+    // apex, in row order, its row, extent and (pk_sad[i], pk_sad[i + 1]) the saddles on either side
+    bool pk_have = false;
+    bool pk_scan = false;        // the track was the slot's scan (bmx_ctx_peaks), whose scan_seq was ...
+    uint64_t pk_seq = 0;
+    int64_t pk_M = 0, pk_K = 0;
+    DevBuf<int32_t> pk_flag, pk_row, pk_lo, pk_hi, pk_sad;
+
+    void release_peaks() {
+        pk_have = false;
+        pk_flag.release(); pk_row.release(); pk_lo.release(); pk_hi.release(); pk_sad.release();
+    }
     void release_support() {
         sp_have = false;
         sp_d.release(); sp_i.release();
@@ -4572,6 +4765,7 @@ struct ChromSlot {
         blob_units.release(); blob_prefix.release();
         for (auto &b : pl_out) b.release();
         release_refined();
+        release_peaks();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         ev0 = ev1 = nullptr;
@@ -4621,6 +4815,13 @@ struct bmx_ctx {
     DevBuf<char> rf_slab;
     DevBuf<uint64_t> bt_keys;    // bootstrap: the replicates' keys, and the weight sums of a weighted point evaluation
     DevBuf<int64_t> bt_pws;
+    // peak calling (bmx_ctx_peaks*): the tile maxima, an uploaded track, the events around the last call, and the switch that
+    // restricts bmx_ctx_refine to the apexes (bmx_ctx_refine_at_peaks)
+    DevBuf<double> pk_tmax, pk_track;
+    DevBuf<int32_t> pk_tfirst;
+    hipEvent_t pk_ev0 = nullptr, pk_ev1 = nullptr;
+    double pk_ms = -1.0;
+    bool rf_at_peaks = false;
     std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
@@ -4645,6 +4846,7 @@ void drop_tests(ChromSlot *s) {
     s->null_ok = false;     // the observed CLR and the counts belong to those test sites
     s->pl_have = 0;         // ... and so do the profiles
     s->release_refined();   // ... and the refinement
+    s->pk_have = false;     // ... and the peaks
 }
 void drop_sites(ChromSlot *s) {
     s->has_sites = false;
@@ -4775,6 +4977,9 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
     c->bt_keys.release(); c->bt_pws.release();
+    c->pk_tmax.release(); c->pk_track.release(); c->pk_tfirst.release();
+    if (c->pk_ev0) (void)hipEventDestroy(c->pk_ev0);
+    if (c->pk_ev1) (void)hipEventDestroy(c->pk_ev1);
     dfree(c->d_prof);
     dfree(c->d_status);
     for (int k = 0; k < 2; k++) {
@@ -5972,6 +6177,9 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     ChromSlot *s = c->cur;
     if (!c->has_model || !s->has_tests || !s->timed) return fail(BMX_E_STATE, "refine: no scan results (scan the slot first)");
     if (min_clr != min_clr) return fail(BMX_E_INVALID, "refine: min_clr is NaN");
+    if (c->rf_at_peaks && !(s->pk_have && s->pk_scan && s->pk_seq == s->scan_seq && s->pk_M == s->M))
+        return fail(BMX_E_INVALID, "refine: restricted to the apexes (bmx_ctx_refine_at_peaks), but the slot has no peak call on its last scan: "
+                                   "call bmx_ctx_peaks after the scan");
     HIP_TRY(hipSetDevice(c->device));
     const int64_t M = s->M;
     RefineParams P;
@@ -5984,6 +6192,7 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     HIP_TRY(c->rf_list.ensure((size_t)M));
     RefineInitParams Q;
     Q.clr = s->clr.p; Q.lin = s->lin.p; Q.nsites = s->nsites.p;
+    Q.apex = c->rf_at_peaks ? s->pk_flag.p : nullptr;
     Q.gA = c->d_A; Q.gx = c->d_x; Q.gab = c->d_abeta; Q.npairs = c->npairs; Q.nab = c->nab;
     Q.M = M; Q.min_clr = min_clr; Q.flag = c->rf_flag.p;
     Q.o_clr = s->rf_clr.p; Q.o_A = s->rf_A.p; Q.o_x = s->rf_x.p; Q.o_ab = s->rf_ab.p; Q.o_ns = s->rf_ns.p; Q.o_rounds = s->rf_rounds.p;
@@ -6241,6 +6450,150 @@ int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double
     if (T) HIP_TRY(hipMemcpy(T, s->bt_T.p, nt * sizeof(double), hipMemcpyDeviceToHost));
     if (T_centre) HIP_TRY(hipMemcpy(T_centre, s->bt_Tc.p, nt * sizeof(double), hipMemcpyDeviceToHost));
     if (rounds) HIP_TRY(hipMemcpy(rounds, s->bt_rounds.p, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BMX_OK;
+}
+
+}  // extern "C"
+
+/* ---- peaks (ballermixplus_amd/peaks.py holds the definition: apex, saddle, extent) ---- */
+
+namespace {
+
+int peaks_check(const char *who, double sep, double min_clr, double frac) {
+    if (sep != sep || min_clr != min_clr || frac != frac) return fail(BMX_E_INVALID, std::string(who) + ": NaN argument");
+    if (!(sep >= 0.0)) return fail(BMX_E_INVALID, std::string(who) + ": the separation must be >= 0");
+    if (!(frac > 0.0 && frac <= 1.0)) return fail(BMX_E_INVALID, std::string(who) + ": the extent fraction must lie in (0, 1]");
+    return BMX_OK;
+}
+
+// The peak call on a device-resident track (g, clr: M rows, positions non-decreasing) into the slot's peak state.  Blocks.
+int peaks_run(bmx_ctx *c, ChromSlot *s, const double *g, const double *clr, int64_t M, double sep, double min_clr, double frac) {
+    if (M > 0x7fffff00LL) return fail(BMX_E_LIMIT, "peaks: more than 2^31 rows");
+    s->pk_have = false;
+    if (!c->pk_ev0) {
+        HIP_TRY(hipEventCreate(&c->pk_ev0));
+        HIP_TRY(hipEventCreate(&c->pk_ev1));
+    }
+    int64_t K = 0;
+    HIP_TRY(hipEventRecord(c->pk_ev0, c->stream));
+    if (M > 0) {
+        const int64_t tiles = (M + PEAK_TILE - 1) / PEAK_TILE;
+        HIP_TRY(c->pk_tmax.ensure((size_t)tiles));
+        HIP_TRY(c->pk_tfirst.ensure((size_t)tiles));
+        HIP_TRY(s->pk_flag.ensure((size_t)M));
+        HIP_TRY(c->rf_pre.ensure((size_t)M + 1));
+        const unsigned nb = (unsigned)((M + PEAK_THREADS - 1) / PEAK_THREADS);
+        hipLaunchKernelGGL(peak_tile_kernel, dim3(nb), dim3(PEAK_THREADS), 0, c->stream, clr, M, c->pk_tmax.p, c->pk_tfirst.p);
+        HIP_TRY(hipGetLastError());
+        PeakParams Q;
+        Q.g = g; Q.c = clr; Q.M = M; Q.sep = sep; Q.min_clr = min_clr;
+        Q.tmax = c->pk_tmax.p; Q.tfirst = c->pk_tfirst.p; Q.flag = s->pk_flag.p;
+        hipLaunchKernelGGL(peak_apex_kernel, dim3(nb), dim3(PEAK_THREADS), 0, c->stream, Q);
+        HIP_TRY(hipGetLastError());
+        // the apexes in row order: the order is part of the result, so a prefix sum and not an atomic counter
+        hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)s->pk_flag.p, M, c->rf_pre.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&K, c->rf_pre.p + M, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));       // the number of apexes sizes their arrays
+        HIP_TRY(s->pk_row.ensure((size_t)K)); HIP_TRY(s->pk_lo.ensure((size_t)K)); HIP_TRY(s->pk_hi.ensure((size_t)K));
+        HIP_TRY(s->pk_sad.ensure((size_t)K + 1));
+        if (K > 0) {
+            hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)s->pk_flag.p,
+                               (const int64_t *)c->rf_pre.p, M, s->pk_row.p);
+            HIP_TRY(hipGetLastError());
+            const unsigned ng = (unsigned)std::min<int64_t>(std::max<int64_t>(K - 1, 1), 1 << 20);
+            hipLaunchKernelGGL(peak_saddle_kernel, dim3(ng), dim3(PEAK_THREADS), 0, c->stream, clr, (const int32_t *)s->pk_row.p, K, s->pk_sad.p);
+            HIP_TRY(hipGetLastError());
+            const int per = PEAK_THREADS / WAVE;
+            hipLaunchKernelGGL(peak_extent_kernel, dim3((unsigned)((K + per - 1) / per)), dim3(PEAK_THREADS), 0, c->stream, clr, M,
+                               (const int32_t *)s->pk_row.p, (const int32_t *)s->pk_sad.p, K, frac, s->pk_lo.p, s->pk_hi.p);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipEventRecord(c->pk_ev1, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->pk_ev0, c->pk_ev1));
+    c->pk_ms = (double)ms;
+    s->pk_M = M; s->pk_K = K;
+    s->pk_have = true;
+    s->pk_scan = false;
+    return BMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmx_ctx_peaks(bmx_ctx *c, double sep, double min_clr, double frac) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    int rc = peaks_check("peaks", sep, min_clr, frac);
+    if (rc) return rc;
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_tests || !s->timed) return fail(BMX_E_INVALID, "peaks: no scan results (scan the slot first)");
+    if (!s->tests_sorted) return fail(BMX_E_INVALID, "peaks: the slot's test positions are not non-decreasing");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = peaks_run(c, s, s->test_gen.p, s->clr.p, s->M, sep, min_clr, frac))) return rc;
+    s->pk_scan = true;
+    s->pk_seq = s->scan_seq;
+    return BMX_OK;
+}
+
+int bmx_ctx_peaks_track(bmx_ctx *c, int64_t M, const double *gen, const double *clr, double sep, double min_clr, double frac) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    int rc = peaks_check("peaks_track", sep, min_clr, frac);
+    if (rc) return rc;
+    if (M < 0 || (M > 0 && (!gen || !clr))) return fail(BMX_E_INVALID, "peaks_track: M >= 0 rows of positions and values are needed");
+    for (int64_t t = 0; t < M; t++) {
+        if (clr[t] != clr[t] || !std::isfinite(gen[t])) return fail(BMX_E_INVALID, "peaks_track: NaN value or non-finite position at row " + std::to_string(t));
+        if (t && !(gen[t] >= gen[t - 1])) return fail(BMX_E_INVALID, "peaks_track: positions are not non-decreasing at row " + std::to_string(t));
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(c->pk_track.ensure((size_t)2 * (size_t)M));
+    if (M) {
+        HIP_TRY(hipMemcpyAsync(c->pk_track.p, gen, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->pk_track.p + M, clr, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));       // the caller's arrays may go away; the call's timing starts after the upload
+    }
+    return peaks_run(c, c->cur, c->pk_track.p, c->pk_track.p + M, M, sep, min_clr, frac);
+}
+
+int bmx_ctx_peak_count(bmx_ctx *c, int64_t *n_peaks, int64_t *M) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->pk_have) return fail(BMX_E_STATE, "no peak call on the slot: call bmx_ctx_peaks after a scan, or bmx_ctx_peaks_track");
+    if (n_peaks) *n_peaks = s->pk_K;
+    if (M) *M = s->pk_M;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_peaks(bmx_ctx *c, int32_t *row, int32_t *lo, int32_t *hi, int32_t *saddle_lo, int32_t *saddle_hi) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->pk_have) return fail(BMX_E_STATE, "no peak call on the slot: call bmx_ctx_peaks after a scan, or bmx_ctx_peaks_track");
+    const size_t K = (size_t)s->pk_K;
+    if (!K) return BMX_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (row) HIP_TRY(hipMemcpy(row, s->pk_row.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (lo) HIP_TRY(hipMemcpy(lo, s->pk_lo.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (hi) HIP_TRY(hipMemcpy(hi, s->pk_hi.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (saddle_lo) HIP_TRY(hipMemcpy(saddle_lo, s->pk_sad.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (saddle_hi) HIP_TRY(hipMemcpy(saddle_hi, s->pk_sad.p + 1, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BMX_OK;
+}
+
+int bmx_ctx_peaks_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    if (c->pk_ms < 0) return fail(BMX_E_STATE, "no peak call yet");
+    *ms = c->pk_ms;
+    return BMX_OK;
+}
+
+int bmx_ctx_refine_at_peaks(bmx_ctx *c, int32_t on) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    c->rf_at_peaks = on != 0;
     return BMX_OK;
 }
 

@@ -347,6 +347,42 @@ class Context:
                                               d(out['T']), d(out['T_centre']), _lib.as_ip(out['rounds'])))
         return out
 
+    def peaks(self, sep, min_clr=0.0, frac=0.5):
+        """Call peaks (ballermixplus_amd/peaks.py) on the selected slot's last scan: separation sep in the units of the test
+        positions, floor min_clr, extent fraction frac.  Returns fetch_peaks()."""
+        _lib.check(self._L.bmx_ctx_peaks(self._h, float(sep), float(min_clr), float(frac)))
+        return self.fetch_peaks()
+
+    def peaks_track(self, gen, clr, sep, min_clr=0.0, frac=0.5):
+        """The same kernels on a track given by the caller (positions gen non-decreasing, values clr); needs no model."""
+        g, c = _lib.f64(gen), _lib.f64(clr)
+        if g.shape != c.shape or g.ndim != 1:
+            raise ValueError('one position per value is needed')
+        _lib.check(self._L.bmx_ctx_peaks_track(self._h, len(g), _lib.as_dp(g), _lib.as_dp(c), float(sep), float(min_clr),
+                                               float(frac)))
+        return self.fetch_peaks()
+
+    def fetch_peaks(self):
+        """The selected slot's last peak call, per apex in row order: {'row', 'lo', 'hi', 'saddle_lo', 'saddle_hi': i32[K]}
+        (lo .. hi: the extent; saddle rows -1 where there is none)."""
+        n = C.c_int64()
+        _lib.check(self._L.bmx_ctx_peak_count(self._h, C.byref(n), None))
+        out = {k: np.empty(n.value, dtype=np.int32) for k in ('row', 'lo', 'hi', 'saddle_lo', 'saddle_hi')}
+        i = _lib.as_ip
+        _lib.check(self._L.bmx_ctx_fetch_peaks(self._h, i(out['row']), i(out['lo']), i(out['hi']), i(out['saddle_lo']),
+                                               i(out['saddle_hi'])))
+        return out
+
+    def peaks_ms(self):
+        """Device milliseconds of the context's last peak call."""
+        ms = C.c_double()
+        _lib.check(self._L.bmx_ctx_peaks_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def refine_at_peaks(self, on=True):
+        """Later refine() calls take only the apexes of their slot's peaks() call on the same scan (min_clr still applies)."""
+        _lib.check(self._L.bmx_ctx_refine_at_peaks(self._h, 1 if on else 0))
+
     def surface(self, test_gen, win_lo, win_hi):
         """T[nA, nx, nab] (NaN where the window is empty) and nsites[nA] of one test site."""
         m = self.model

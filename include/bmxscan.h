@@ -312,6 +312,33 @@ int bmx_ctx_boot_count(bmx_ctx *c, int64_t *n_sel, int32_t *R);
 int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double *abeta, double *T, double *T_centre,
                        int32_t *rounds);
 
+/* ---- peaks of the CLR track (opt-in; the CLI's --peaks; ballermixplus_amd/peaks.py holds the definition) ------------------
+ * The track: rows t = 0 .. M-1 with non-decreasing positions g and values c.  Row t is an APEX iff c_t > 0, c_t >= min_clr and no
+ * other row s with g_t - g_s <= sep and g_s - g_t <= sep has c_s > c_t, or c_s == c_t and s < t (a local-maximum rule, not greedy
+ * clumping).  Between consecutive apexes the SADDLE is the first row of smallest c strictly between them (none when they are
+ * adjacent rows).  The EXTENT of an apex a is the maximal run of rows around it with c >= frac * c_a, cut strictly inside the
+ * saddles on either side (adjacent apexes end at their own rows).  Exact FP64 comparisons throughout: the host restatement in
+ * peaks.py gives the same rows.  Errors of this group: a NaN argument, sep < 0, frac outside (0, 1], no scan yet, unsorted
+ * positions, and a refinement restricted to apexes without a peak call on the slot's last scan are all BMX_E_INVALID. */
+/* Peaks of the selected slot's last scan: g = its test positions, c = its CLR.  Blocks. */
+int bmx_ctx_peaks(bmx_ctx *c, double sep, double min_clr, double frac);
+/* The same kernels on a track given by the caller: gen[M], clr[M] (M >= 0; no NaN value, finite non-decreasing positions).
+ * Needs neither model nor sites; the result replaces the selected slot's peak call.  Blocks. */
+int bmx_ctx_peaks_track(bmx_ctx *c, int64_t M, const double *gen, const double *clr, double sep, double min_clr, double frac);
+/* *n_peaks (may be NULL) = the number of apexes of the selected slot's last peak call, *M (may be NULL) = the rows of its track.
+ * BMX_E_STATE without one; set_tests / set_sites / set_model drop it. */
+int bmx_ctx_peak_count(bmx_ctx *c, int64_t *n_peaks, int64_t *M);
+/* Per apex, in row order, n_peaks of each: its row, the first and last row of its extent, and the saddle rows below and above it
+ * (-1: none -- the end of the track, or the neighbouring apex is the adjacent row).  Any pointer may be NULL. */
+int bmx_ctx_fetch_peaks(bmx_ctx *c, int32_t *row, int32_t *lo, int32_t *hi, int32_t *saddle_lo, int32_t *saddle_hi);
+/* Milliseconds of the context's last peak call on the device, first kernel to last (HIP events on the context's stream; the
+ * eight-byte read-back of the apex count that sizes the results lies in between). */
+int bmx_ctx_peaks_ms(bmx_ctx *c, double *ms);
+/* on != 0: later bmx_ctx_refine calls of this context refine only the windows that are apexes of their slot's peak call, which must
+ * be a bmx_ctx_peaks on the slot's last scan (else the refinement fails with BMX_E_INVALID); min_clr applies on top.  Support
+ * intervals and bootstrap follow, as they only touch refined windows.  Off by default. */
+int bmx_ctx_refine_at_peaks(bmx_ctx *c, int32_t on);
+
 /* ---- the final gather over RCCL, inside the library (north_star: "only a final RCCL gather over xGMI") --
  * One process per GPU, each with its own context.  Rank 0 makes an id (bmx_comm_unique_id: 128 bytes) and hands it to the other
  * ranks by whatever channel the caller has (MPI, a file, a socket, torch's store); every rank then calls bmx_comm_create with
