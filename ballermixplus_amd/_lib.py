@@ -76,6 +76,8 @@ PROTOTYPES = {
     'bmx_ctx_plan': (C.c_int, [_vp, _ip, _ip, _ip, _lp]),
     'bmx_ctx_launch_ranges': (C.c_int, [_vp, _lp, C.c_int32, _ip]),
     'bmx_ctx_surface': (C.c_int, [_vp, C.c_double, C.c_int64, C.c_int64, _dp, _ip]),
+    'bmx_ctx_surfaces': (C.c_int, [_vp, C.c_int64, _ip, _dp, _ip]),
+    'bmx_ctx_surfaces_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_permute_rows': (C.c_int, [_vp, C.c_uint64, C.c_int64]),
     'bmx_ctx_restore_rows': (C.c_int, [_vp]),
     'bmx_ctx_null_begin': (C.c_int, [_vp]),

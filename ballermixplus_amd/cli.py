@@ -32,6 +32,11 @@ Additions (do not change any reference command line):
                     the -o pattern with `peaks`, genome-wide).  --atPeaks (with --refine): refine only the apexes, and so compute
                     --support / --boot for them only.  `python -m ballermixplus_amd.peaks OUT.txt --peaks G` calls peaks again on
                     an existing output.
+  --surfaces [--surfaceMin C] [--surfaceMax N]     likelihood surfaces of selected windows (ballermixplus_amd/surfaces.py): T at
+                    every grid point (A, x, alpha_beta) of the observed scan's windows with CLR >= C -- with --peaks only the apexes
+                    among them -- at most N of them (default 1000: the N highest CLR); needs --peaks or --surfaceMin.  Writes
+                    <out>.surfaces.txt next to each output file: per window a block of rows physPos, genPos, A, x, abeta, T, nSites
+                    with the grids ascending.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -158,7 +163,54 @@ def build_parser():
     parser.add_argument('--atPeaks', dest='atPeaks', action='store_true', default=False,
                         help='MI355X build only, with --peaks and --refine: refine only the apexes (--refineMin still applies); '
                              '--support and --boot follow, as they only touch refined windows')
+    parser.add_argument('--surfaces', dest='surfaces', action='store_true', default=False,
+                        help='MI355X build only: write the likelihood surface T(A, x, alpha_beta) of selected windows of the observed '
+                             'scan -- every grid point, not only the maximum -- to <out>.surfaces.txt next to each output file '
+                             '(columns physPos, genPos, A, x, abeta, T, nSites; one block per window, grids ascending).  The windows: '
+                             'with --peaks the apexes, with --surfaceMin those at or above it, with both the apexes at or above it; '
+                             'one of the two is required; default: off')
+    parser.add_argument('--surfaceMin', dest='surfaceMin', type=float, default=None,
+                        help='MI355X build only, with --surfaces: only windows with CLR >= this value (default 0)')
+    parser.add_argument('--surfaceMax', dest='surfaceMax', type=int, default=None,
+                        help='MI355X build only, with --surfaces: at most N windows per file, the N with the highest CLR '
+                             '(default 1000)')
     return parser
+
+
+def surfaces_refusal(opt):
+    """The message that refuses a --surfaces / --surfaceMin / --surfaceMax command line, or None when it can run (or surfaces
+    are off)."""
+    for flag, v in (('--surfaceMin', opt.surfaceMin), ('--surfaceMax', opt.surfaceMax)):
+        if v is not None and not opt.surfaces:
+            return '%s needs --surfaces.' % flag
+    if not opt.surfaces:
+        return None
+    from . import surfaces
+    refused = surfaces.value_refusal(opt.surfaceMin, opt.surfaceMax)
+    if refused:
+        return refused
+    if opt.peaks is None and opt.surfaceMin is None:
+        return ('--surfaces needs --peaks G (the surfaces of the apexes) or --surfaceMin C (of the windows with CLR >= C): '
+                'the surface of every window of a chromosome is never what is meant.')
+    if opt.getSpec or opt.getConfig:
+        return '--surfaces scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if not opt.outfile:
+        return '--surfaces needs -o: the surfaces file is written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--surfaces runs in a single process; multi-rank launches are not supported.'
+    return None
+
+
+def write_surfaces(opt, ctx, sel, outfile, ts, called, say):
+    """<outfile>.surfaces.txt of one file whose observed scan (and peak call: `called`, or None without --peaks) has just run
+    on ctx's selected slot."""
+    from . import surfaces
+    n, dropped = surfaces.surfaces_and_write(ctx, outfile, ts, sel, opt.surfaceMin if opt.surfaceMin is not None else 0.0,
+                                             opt.surfaceMax if opt.surfaceMax is not None else surfaces.MAX_WINDOWS,
+                                             called[0]['row'] if called is not None else None)
+    say(f'\n{datetime.now()}. Surfaces: {n} window/s -> {surfaces.output_name(outfile)}')
+    if dropped:
+        say(f'--surfaceMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
 
 
 def peaks_refusal(opt):
@@ -372,7 +424,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = peaks_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
+    refused = peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -465,6 +517,9 @@ def main(argv=None):
         called = call_peaks(opt, Sel_Probs.ctx, sc.test_sites)
         Sel_Probs.ctx.refine_at_peaks(opt.atPeaks)
         stamp('peaks')
+    if opt.surfaces:
+        write_surfaces(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites, called if opt.peaks is not None else None, say)
+        stamp('surfaces')
     if opt.refine:
         write_refined(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites)
         stamp('refine')
@@ -603,6 +658,8 @@ def main_many(opt, files, stamp=lambda what: None):
                 ctx.set_profiles(0)
         if opt.peaks is not None:
             peak_files.append((infile, outfile, call_peaks(opt, ctx, sc.test_sites)))
+        if opt.surfaces:
+            write_surfaces(opt, ctx, sel, outfile, sc.test_sites, peak_files[-1][2] if opt.peaks is not None else None, say)
         if opt.refine:
             write_refined(opt, ctx, outfile, sc.test_sites, i)
         if opt.nullPerm:

@@ -9,6 +9,7 @@
 //                                     tests), and the path for tables of 4 GiB and more
 //       locate_kernel / finalize_kernel: test-site positions, per-slice argmax merge + nSites
 //       surface_kernel             <- the full T[A,x,alpha] surface of one site (v1:449-450 wish)
+//       surfaces_kernel            <- the same surfaces for a list of test sites in one launch (bmx_ctx_surfaces)
 //
 // The shipped library reads ONE environment variable, BMX_TRACE (stage messages on stderr, no effect on results).
 // Tuning knobs for A/B runs (BMX_LDS_PAD, BMX_DENSE_GAP, BMX_SOLO_GAP, BMX_FORCE_J, BMX_FAR_EPS, BMX_MOM_SLOTS, BMX_SPB,
@@ -4555,6 +4556,77 @@ __global__ __launch_bounds__(PEAK_THREADS) void peak_extent_kernel(const double 
     if (lane == 0) { o_lo[i] = (int32_t)lo; o_hi[i] = (int32_t)hi; }
 }
 
+// ----------------------------------------------------------------------------- surfaces of a list of test sites
+// surface_kernel's T[iA][pair] for a LIST of test sites of the slot in one launch (bmx_ctx_surfaces; the definition and the
+// CLI's selection rule are ballermixplus_amd/surfaces.py).  One workgroup of SURFS_THREADS per (listed window q, iA, slice of
+// SURFS_THREADS pairs); thread tid owns pair p = slice * SURFS_THREADS + tid.
+//   1. wave 0 finds the inclusive site range of this A inside the window -- A |g_i - tg| <= zcut, monotone in |g_i - tg| on
+//      either side of the first site at or right of tg -- with wave_first_true, as refine_kernel does: a window at A = 1e8
+//      reads a few dozen positions, not the chromosome.  The range goes to the workgroup through LDS.
+//   2. the range is walked in tiles of SURFS_THREADS sites: thread tid computes (alpha, row, in) of site base + tid into LDS
+//      (row -1: not `in`), the barrier counts the `in` sites, and every thread then adds log1p(alpha_s R[row_s][p]) over the
+//      tile's `in` sites IN INCREASING SITE INDEX: same-address LDS reads, R reads coalesced across p.
+// Each pair's sum therefore runs over surface_kernel's sites in surface_kernel's order with surface_kernel's expression (the
+// sites outside the range are exactly those it skips), so T and nSites are bitwise what bmx_ctx_surface returns for the
+// window.  No atomics: a window's result is a function of that window alone.
+constexpr int SURFS_THREADS = 256;
+
+struct SurfsParams {
+    const double *genpos; RowArray row; int64_t N;
+    const double *Rt; int NP, npairs, nslices;      // nslices: slices of SURFS_THREADS pairs
+    const double *A; int nA;
+    const double *test_gen; const int64_t *win_lo, *win_hi;
+    const int32_t *tests;                            // the listed test sites of this launch
+    double zcut;
+    double *T;        // [n][nA][npairs]
+    int32_t *ns;      // [n][nA]
+};
+
+__global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) {
+    __shared__ double s_alpha[SURFS_THREADS];
+    __shared__ int s_row[SURFS_THREADS];
+    __shared__ int64_t s_range[2];
+    const int tid = threadIdx.x;
+    const int slice = blockIdx.x % S.nslices;
+    const int iA = (blockIdx.x / S.nslices) % S.nA;
+    const int64_t q = blockIdx.x / S.nslices / S.nA;
+    const int p = slice * SURFS_THREADS + tid;
+    const bool live = p < S.npairs;                 // (p may lie beyond the padded row of R: an idle thread reads nothing)
+    const int64_t t = S.tests[q];
+    const double A = S.A[iA], tg = S.test_gen[t], zc = S.zcut;
+    if (tid < WAVE) {
+        const int64_t wlo = max(S.win_lo[t], (int64_t)0), whi = min(S.win_hi[t], S.N - 1);
+        const int64_t ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return S.genpos[i] >= tg; });
+        const int64_t a = wave_first_true(wlo, ctr, [&](int64_t i) { return A * fabs(S.genpos[i] - tg) <= zc; });
+        const int64_t b = wave_first_true(ctr, whi + 1, [&](int64_t i) { return !(A * fabs(S.genpos[i] - tg) <= zc); });
+        if (tid == 0) { s_range[0] = a; s_range[1] = b - 1; }
+    }
+    __syncthreads();
+    const int64_t rlo = s_range[0], rhi = s_range[1];
+    double sum = 0.0;
+    int ns = 0;
+    for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
+        const int64_t i = base + tid;
+        const bool valid = i <= rhi;
+        const double g = valid ? S.genpos[i] : tg;
+        const double z = A * fabs(g - tg);
+        const bool in = valid && z <= zc && g != tg;
+        s_alpha[tid] = in ? exp(-z) : 0.0;
+        s_row[tid] = in ? (int)S.row[i] : -1;
+        ns += __syncthreads_count(in);
+        if (live) {
+            const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
+            for (int s = 0; s < cnt; ++s) {
+                const int r_s = s_row[s];
+                if (r_s >= 0) sum += log1p(s_alpha[s] * S.Rt[(size_t)r_s * S.NP + p]);
+            }
+        }
+        __syncthreads();
+    }
+    if (live) S.T[((size_t)q * S.nA + iA) * S.npairs + p] = ns ? 2.0 * sum : NAN;
+    if (slice == 0 && tid == 0) S.ns[(size_t)q * S.nA + iA] = ns;
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -4575,11 +4647,14 @@ void dfree(T *&p) {
 }  // namespace
 
 // -DBMX_DEVICE_PROBE=<kernel instantiation>: device code of that ONE kernel and nothing else (register / spill counts and the
-// assembly of a kernel under work in seconds instead of a minute; `make probe K='clr_scan_prepared_kernel<16, true>'`)
+// assembly of a kernel under work in seconds instead of a minute; `make probe K='clr_scan_prepared_kernel<16, true>'`).  A kernel
+// that is no template is always compiled: the Makefile passes -DBMX_DEVICE_PROBE_PLAIN for it and picks its lines of the report.
 #ifdef BMX_DEVICE_PROBE
+#ifndef BMX_DEVICE_PROBE_PLAIN
 namespace {
 template __global__ void BMX_DEVICE_PROBE(ScanParams, PrepView);
 }
+#endif
 #else
 
 // bmx_io.cpp: rows [0, n) formatted into `out` (<= 512 bytes per row); grid indices either as (ix, ia, iA) or as the
@@ -4802,6 +4877,11 @@ struct bmx_ctx {
     int *d_status = nullptr;     // ... and its error bits
     DevBuf<double> surf_T;
     DevBuf<int32_t> surf_ns;
+    // surfaces of a list of test sites (bmx_ctx_surfaces): the list, one chunk's output, the events around a chunk's kernel
+    DevBuf<double> sfs_T;
+    DevBuf<int32_t> sfs_ns, sfs_list;
+    hipEvent_t sfs_ev0 = nullptr, sfs_ev1 = nullptr;
+    double sfs_ms = -1.0;
     DevBuf<int64_t> gap_sample;
     // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
     int pl_which = 0;
@@ -4973,6 +5053,9 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->slots.clear();
     c->part_T.release(); c->part_lin.release(); c->part_ns.release(); c->arena.release(); c->gap_sample.release();
     c->surf_T.release(); c->surf_ns.release();
+    c->sfs_T.release(); c->sfs_ns.release(); c->sfs_list.release();
+    if (c->sfs_ev0) (void)hipEventDestroy(c->sfs_ev0);
+    if (c->sfs_ev1) (void)hipEventDestroy(c->sfs_ev1);
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
@@ -6057,6 +6140,64 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
     HIP_TRY(hipMemcpyAsync(T_out, c->surf_T.p, (size_t)c->nA * c->npairs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out, c->surf_ns.p, (size_t)c->nA * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return BMX_OK;
+}
+
+int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out, int32_t *nsites_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (n < 0) return fail(BMX_E_INVALID, "surfaces: n < 0");
+    ChromSlot *s = c->cur;
+    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before surfaces");
+    if (n == 0) return BMX_OK;
+    if (!tests || !T_out) return fail(BMX_E_INVALID, "surfaces: NULL argument");
+    for (int64_t q = 0; q < n; q++)
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "surfaces: test site index out of range at entry " + std::to_string(q));
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->sfs_ev0) {
+        HIP_TRY(hipEventCreate(&c->sfs_ev0));
+        HIP_TRY(hipEventCreate(&c->sfs_ev1));
+    }
+    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one window's surface
+    const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / (per * sizeof(double)), 1);
+    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
+    // a launch holds fewer than 2^32 threads, i.e. fewer than 2^24 workgroups of SURFS_THREADS: a chunk's workgroups must fit
+    // (set_model bounds nA * npairs below 2^31, so one window's always do)
+    const int64_t fit = std::max<int64_t>((0xffffffffLL / SURFS_THREADS) / ((int64_t)c->nA * nsl), 1);
+    const int64_t step = std::min(chunk, fit);
+    HIP_TRY(c->sfs_list.ensure((size_t)n));
+    HIP_TRY(c->sfs_T.ensure((size_t)std::min<int64_t>(step, n) * per));
+    HIP_TRY(c->sfs_ns.ensure((size_t)std::min<int64_t>(step, n) * c->nA));
+    HIP_TRY(hipMemcpyAsync(c->sfs_list.p, tests, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    SurfsParams S;
+    S.genpos = s->genpos.p; S.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; S.N = s->N;
+    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    S.test_gen = s->test_gen.p; S.win_lo = s->win_lo.p; S.win_hi = s->win_hi.p; S.zcut = c->zcut;
+    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p;
+    double total = 0.0;
+    for (int64_t q0 = 0; q0 < n; q0 += step) {
+        const int64_t m = std::min(step, n - q0);
+        S.tests = c->sfs_list.p + q0;
+        HIP_TRY(hipEventRecord(c->sfs_ev0, c->stream));
+        hipLaunchKernelGGL(surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->sfs_ev1, c->stream));
+        // each chunk goes back before the next is launched: one device buffer serves the whole list
+        HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (nsites_out)
+            HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->sfs_ev0, c->sfs_ev1));
+        total += (double)ms;
+    }
+    c->sfs_ms = total;
+    return BMX_OK;
+}
+
+int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    if (c->sfs_ms < 0) return fail(BMX_E_STATE, "no surfaces call yet");
+    *ms = c->sfs_ms;
     return BMX_OK;
 }
 

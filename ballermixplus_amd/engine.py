@@ -392,6 +392,24 @@ class Context:
                                            _lib.as_ip(ns)))
         return T, ns
 
+    def surfaces(self, tests):
+        """T[n, nA, nx, nab] (NaN where the window is empty at that A) and nsites[n, nA] of the listed test sites of the
+        selected slot (indices into its test sites: any order, repeats allowed), each bitwise surface()'s."""
+        m = self.model
+        t = _lib.i32(tests)
+        if t.ndim != 1:
+            raise ValueError('a flat list of test site indices is needed')
+        T = np.empty((len(t), self.nA, len(m.x), len(m.abeta)), dtype=np.float64)
+        ns = np.empty((len(t), self.nA), dtype=np.int32)
+        _lib.check(self._L.bmx_ctx_surfaces(self._h, len(t), _lib.as_ip(t), _lib.as_dp(T), _lib.as_ip(ns)))
+        return T, ns
+
+    def surfaces_ms(self):
+        """Device milliseconds of the kernels of the context's last surfaces() call."""
+        ms = C.c_double()
+        _lib.check(self._L.bmx_ctx_surfaces_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def fetch_lut(self):
         m = self.model
         shape = (len(m.x), len(m.abeta), m.rows)

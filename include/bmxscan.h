@@ -127,7 +127,7 @@ int bmx_scan_multi(const bmx_model *m, const double *A, int32_t nA, int64_t N, c
  * arrays, test sites and results: the reference runs one input file per process (BalLeRMix+_v1.py:777-799); a
  * whole-genome run here selects slot k, sets chromosome k's sites and test sites, and scans the slots back to back on
  * the context's stream with the table built once.  Slot 0 exists from creation and is selected; set_sites, set_tests,
- * scan, fetch*, records, result_ptrs, last_scan_ms, scan_write, surface and plan act on the selected slot. */
+ * scan, fetch*, records, result_ptrs, last_scan_ms, scan_write, surface, surfaces and plan act on the selected slot. */
 typedef struct bmx_ctx bmx_ctx;
 
 int bmx_ctx_create(bmx_ctx **out, int device);
@@ -182,6 +182,21 @@ int bmx_ctx_fetch_lut(bmx_ctx *c, double *psel_out, double *R_out);
  * log1p(alpha*R), independently of the scan kernels' product form. */
 int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi, double *T_out,
                     int32_t *nsites_out);
+/* Surfaces of n test sites of the selected slot (indices into its M test sites, any order, repeats allowed):
+ * T_out[n][nA][nx][nab] in the model's grid iteration order (NaN where the window at that A is empty),
+ * nsites_out[n][nA] (may be NULL).  Each window bitwise what bmx_ctx_surface gives for its
+ * (test_gen, win_lo, win_hi).  Needs model, sites and test sites (else BMX_E_STATE), no scan; an index outside
+ * [0, M) or a NULL tests/T_out with n > 0 is BMX_E_INVALID; n == 0 succeeds and writes nothing.  Leaves scan
+ * results, profiles, refinement, support, bootstrap, peak and null state of every slot untouched.  Blocks.
+ * The list is processed in chunks of as many windows as keep the device output buffer at or below
+ * BMX_SURFACES_CHUNK_BYTES (one window where a single surface is larger); each chunk is copied back before the
+ * next is launched, so the device memory held does not grow with n.
+ * These two entry points arrived without a bump of BMX_ABI_VERSION_MINOR (as the profile, refinement, support, bootstrap and
+ * peak groups did): version 1.5 does not say whether a binary has them; look the symbol up (dlsym) to find out. */
+#define BMX_SURFACES_CHUNK_BYTES (256LL << 20)
+int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out, int32_t *nsites_out);
+/* Milliseconds the last bmx_ctx_surfaces spent in its kernels (HIP events on the context's stream). */
+int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms);
 /* Choose the scan kernel variant (0 = default). For A/B measurements only. */
 int bmx_ctx_set_variant(bmx_ctx *c, int variant);
 /* Select (creating it on first use) chromosome slot `slot`, 0 <= slot < 4096. */
