@@ -113,6 +113,7 @@ def test_config4_every_chromosome_against_the_oracle():
     print('config 4 vs C oracle (own table): %d windows on 22 chromosomes, %d launch-range cuts covered, worst rel dCLR %.3e, '
           'worst abs %.3e, %d rounding-noise ties' % (total, ncuts, worst, worst_abs, ties))
     assert worst < 1e-6
+    assert ties == 0
 
 
 def test_config5_every_contig_against_the_oracle():
@@ -155,6 +156,7 @@ def test_config5_every_contig_against_the_oracle():
     print('config 5 vs C oracle (own table): %d windows on 8 contigs, worst rel dCLR %.3e, worst abs %.3e, %d rounding-noise ties'
           % (total, worst, worst_abs, ties))
     assert worst < 1e-6
+    assert ties == 0
 
 
 def _native_rccl_gather_checks():
