@@ -3130,8 +3130,17 @@ __global__ __launch_bounds__(SITE_THREADS) void clr_scan_solo_kernel(ScanParams 
                         f[2 * k + 1] = fma(e.y, R0, 1.0);
                     }
                     if (since + 8 > lim) { renorm_fx(acc, E); since = 0; }
-                    acc *= ((f[0] * f[1]) * (f[2] * f[3])) * ((f[4] * f[5]) * (f[6] * f[7]));
-                    since += 8;
+                    if (lim < 8) {
+                        // span_hi >= 126: eight factors of up to 2^span_hi each do not fit between two exponent extractions (from
+                        // 2^128 on their product alone leaves the double range) -- four, an extraction, four; lim >= 4 (set_model)
+                        acc *= (f[0] * f[1]) * (f[2] * f[3]);
+                        renorm_fx(acc, E);
+                        acc *= (f[4] * f[5]) * (f[6] * f[7]);
+                        since = 4;
+                    } else {
+                        acc *= ((f[0] * f[1]) * (f[2] * f[3])) * ((f[4] * f[5]) * (f[6] * f[7]));
+                        since += 8;
+                    }
                     pos += 4;
                 }
                 // the other rows: (E, row offset) per broadcast read, R from the LDS slice (or L2), four entries per step
@@ -5196,7 +5205,9 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
     }
     if (!(fmax < 1e300)) return fail(BMX_E_INVALID, "selection table overflows (a neutral probability g is 0 or tiny)");
     c->span_hi = std::max(1, (int)std::ceil(std::log2(fmax)));
-    if (c->span_hi > 240)     // four factors are multiplied between exponent extractions
+    // no kernel multiplies fewer than four factors between two exponent extractions (the per-site kernel always four; the solo
+    // kernel eight of the most frequent row, split four + four once renorm_every < 8): 4 x 240 bits on a mantissa below 2
+    if (c->span_hi > 240)
         return fail(BMX_E_LIMIT, "selection table spans more than 2^240 (a neutral probability of ~1e-70?)");
     c->rmax = fmax - 1.0;
     {   // per slice and row: the largest |R| over the slice's pairs (grouped kernel's far-field test)

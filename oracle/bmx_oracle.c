@@ -358,3 +358,31 @@ int orc_scan(int nx, int nab, int rows, const double *R, const double *A, int nA
     }
     return 0;
 }
+
+/* The sums behind orc_scan, kept per grid point: S[t][iA][p] = sum_{i in win(A)} log1p(alpha_i * R[p][row_i]) over ALL the sites
+ * given whose position lies in [gmin[t], gmax[t]] (an index window of sorted, distinct positions, stated by position so that the
+ * sites may be given in parts: the sums of the parts add up), and ns[t][iA] = |win(A)|.  T = 2 S.  Tests use it to measure how
+ * far a window's winner is from its runner-up. */
+int orc_surface_sums(int nx, int nab, int rows, const double *R, const double *A, int nA, int64_t N,
+                     const double *genpos, const int32_t *row, int64_t M, const double *test_gen, const double *gmin, const double *gmax,
+                     double *S, int32_t *ons) {
+    int np_ = nx * nab;
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t t = 0; t < M; t++) {
+        double tg = test_gen[t];
+        for (int iA = 0; iA < nA; iA++) {
+            double *ac = S + ((size_t)t * nA + iA) * np_;
+            for (int p = 0; p < np_; p++) ac[p] = 0.0;
+            int ns = 0;
+            for (int64_t i = 0; i < N; i++) {
+                double al = exp(-A[iA] * fabs(genpos[i] - tg));
+                if (!(al >= 1e-8) || genpos[i] == tg || genpos[i] < gmin[t] || genpos[i] > gmax[t]) continue;
+                ns++;
+                const double *Rr = R + row[i];
+                for (int p = 0; p < np_; p++) ac[p] += log1p(al * Rr[(size_t)p * rows]);
+            }
+            ons[(size_t)t * nA + iA] = ns;
+        }
+    }
+    return 0;
+}
