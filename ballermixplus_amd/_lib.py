@@ -94,6 +94,11 @@ PROTOTYPES = {
     'bmx_ctx_boot': (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, C.c_int64, C.c_double]),
     'bmx_ctx_boot_count': (C.c_int, [_vp, _lp, _ip]),
     'bmx_ctx_fetch_boot': (C.c_int, [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip]),
+    'bmx_ctx_resample_sites': (C.c_int, [_vp, C.c_int32, C.c_uint64, C.c_int64, _lp]),
+    'bmx_ctx_fetch_sites': (C.c_int, [_vp, _dp, _ip]),
+    'bmx_ctx_locate_begin': (C.c_int, [_vp, C.c_int32, _ip, _ip, C.c_int32]),
+    'bmx_ctx_locate_accumulate': (C.c_int, [_vp, C.c_int32]),
+    'bmx_ctx_fetch_locate': (C.c_int, [_vp, _ip, _dp]),
     'bmx_ctx_peaks': (C.c_int, [_vp, C.c_double, C.c_double, C.c_double]),
     'bmx_ctx_peaks_track': (C.c_int, [_vp, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_double]),
     'bmx_ctx_peak_count': (C.c_int, [_vp, _lp, _lp]),

@@ -37,6 +37,13 @@ Additions (do not change any reference command line):
                     among them -- at most N of them (default 1000: the N highest CLR); needs --peaks or --surfaceMin.  Writes
                     <out>.surfaces.txt next to each output file: per window a block of rows physPos, genPos, A, x, abeta, T, nSites
                     with the grids ascending.
+  --locate R [--locateSeed S] [--locateBlock B] [--locateSpan H] [--locateLevel L] [--locateMin C] [--locateReps]     with
+                    --peaks: a block-bootstrap interval for the POSITION of every apex (ballermixplus_amd/locate.py): R replicates
+                    resample the sites in blocks of B consecutive sites on the device, repeat the grid scan at the test positions
+                    within H of the apexes (default H = G) and record where each peak's maximum falls; writes <out>.locate.txt
+                    (percentile ends at level L as rows of the main output, the spread, the share of replicates at the apex and
+                    at the ends of the range) and with --locateReps <out>.locate.reps.txt next to each output file.  Default
+                    window mode only (no -w, no --fixWinSize).
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -174,7 +181,71 @@ def build_parser():
     parser.add_argument('--surfaceMax', dest='surfaceMax', type=int, default=None,
                         help='MI355X build only, with --surfaces: at most N windows per file, the N with the highest CLR '
                              '(default 1000)')
+    parser.add_argument('--locate', dest='locate', type=int, default=0,
+                        help='MI355X build only, with --peaks: R >= 2 bootstrap replicates of the grid scan around every apex.  Each '
+                             'replicate gives every block of --locateBlock consecutive sites a Poisson(1) weight, scans the '
+                             'resampled chromosome at the test positions within --locateSpan of the apexes and records where each '
+                             'peak\'s maximum falls; <out>.locate.txt holds, per apex, the percentile interval of that position (as '
+                             'rows of the main output), its standard deviation, the share of replicates at the apex and at the ends '
+                             'of the range, and the percentile ends of the replicate maxima; default 0: off')
+    parser.add_argument('--locateSeed', dest='locateSeed', type=int, default=None,
+                        help='MI355X build only, with --locate: seed of the weights (default 1; its stream is separate from '
+                             '--bootSeed\'s and --nullSeed\'s)')
+    parser.add_argument('--locateBlock', dest='locateBlock', type=int, default=None,
+                        help='MI355X build only, with --locate: sites per block (default 1).  B should span the linkage disequilibrium '
+                             'of the data; B = 1 resamples sites as if they were independent and gives intervals as narrow as that')
+    parser.add_argument('--locateSpan', dest='locateSpan', type=float, default=None,
+                        help='MI355X build only, with --locate: half-width H of the search range around every apex, in the units '
+                             '--peaks measures in (default: --peaks\' G).  A large p_edge says H was too small')
+    parser.add_argument('--locateLevel', dest='locateLevel', type=float, default=None,
+                        help='MI355X build only, with --locate: level L of the percentile ends, 0 < L < 1 (default 0.95)')
+    parser.add_argument('--locateMin', dest='locateMin', type=float, default=None,
+                        help='MI355X build only, with --locate: only apexes with CLR >= this value (default: all apexes)')
+    parser.add_argument('--locateReps', dest='locateReps', action='store_true', default=False,
+                        help='MI355X build only, with --locate: also write the argmax of every replicate of every peak to '
+                             '<out>.locate.reps.txt')
     return parser
+
+
+def locate_refusal(opt):
+    """The message that refuses a --locate / --locate* command line, or None when it can run (or the position bootstrap is
+    off).  Asked before every other refusal, so that a command line with --locate is refused in --locate's name."""
+    for flag, v in (('--locateSeed', opt.locateSeed), ('--locateBlock', opt.locateBlock), ('--locateSpan', opt.locateSpan),
+                    ('--locateLevel', opt.locateLevel), ('--locateMin', opt.locateMin), ('--locateReps', opt.locateReps or None)):
+        if v is not None and not opt.locate:
+            return '%s needs --locate.' % flag
+    if not opt.locate:
+        return None
+    from . import locate
+    refused = locate.value_refusal(opt.locate, opt.locateBlock, opt.locateSpan, opt.locateLevel, opt.locateMin)
+    if refused:
+        return refused
+    if opt.getSpec or opt.getConfig:
+        return '--locate scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if opt.peaks is None:
+        return '--locate needs --peaks G: the intervals are drawn around the apexes of the peak call.'
+    if opt.w != 0 or opt.size:
+        return ('--locate needs the default window mode (no -w, no --fixWinSize): windows that count sites or nucleotides are '
+                'not defined on a resampled site array.')
+    if not opt.outfile:
+        return '--locate needs -o: the locate file is written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--locate runs in a single process; multi-rank launches are not supported.'
+    return None
+
+
+def write_locate(opt, ctx, outfile, ts, called, say, f=0):
+    """<outfile>.locate.txt (with --locateReps <outfile>.locate.reps.txt) of one file (input-file ordinal f) whose observed scan
+    and peak call (`called`) have just run on ctx's selected slot."""
+    from . import locate
+    n, empty = locate.locate_and_write(ctx, outfile, ts, called, opt.locate, opt.locateSeed if opt.locateSeed is not None else 1,
+                                       opt.locateBlock if opt.locateBlock is not None else 1,
+                                       opt.locateSpan if opt.locateSpan is not None else opt.peaks,
+                                       opt.locateLevel if opt.locateLevel is not None else locate.LEVEL, opt.locateMin, f,
+                                       opt.locateReps)
+    say(f'\n{datetime.now()}. Position bootstrap: {n} peak/s, {opt.locate} replicates -> {locate.output_name(outfile)}')
+    if empty:
+        say(f'--locate: {empty} replicate/s drew weight 0 for every site and have no track.')
 
 
 def surfaces_refusal(opt):
@@ -424,7 +495,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
+    refused = locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -523,6 +594,9 @@ def main(argv=None):
     if opt.refine:
         write_refined(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites)
         stamp('refine')
+    if opt.locate:
+        write_locate(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites, called, say)
+        stamp('locate')
     if opt.nullPerm:
         got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
         finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
@@ -654,7 +728,7 @@ def main_many(opt, files, stamp=lambda what: None):
         stamp('file %d of %d' % (i + 1, len(files)))
         if pnames:
             write_profiles(opt, ctx, sel, outfile, sc.test_sites)
-            if opt.nullPerm:
+            if opt.nullPerm or opt.locate:
                 ctx.set_profiles(0)
         if opt.peaks is not None:
             peak_files.append((infile, outfile, call_peaks(opt, ctx, sc.test_sites)))
@@ -662,6 +736,8 @@ def main_many(opt, files, stamp=lambda what: None):
             write_surfaces(opt, ctx, sel, outfile, sc.test_sites, peak_files[-1][2] if opt.peaks is not None else None, say)
         if opt.refine:
             write_refined(opt, ctx, outfile, sc.test_sites, i)
+        if opt.locate:
+            write_locate(opt, ctx, outfile, sc.test_sites, peak_files[-1][2], say, i)
         if opt.nullPerm:
             # per-file permutations are independent (key of file ordinal i): only the host copies of this file's observed
             # CLR and counts stay until the genome-wide maxima are known

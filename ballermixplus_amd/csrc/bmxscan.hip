@@ -4386,6 +4386,149 @@ __global__ void boot_init_kernel(const double *clr, const int32_t *rounds, int64
     if (t < M) flag[t] = (rounds[t] >= 0 && clr[t] >= min_clr) ? 1 : 0;
 }
 
+// ----------------------------------------------------------------------------- resampled sites, position bootstrap
+// bmx_ctx_resample_sites / bmx_ctx_locate_* (the definition is ballermixplus_amd/locate.py).  An integer-weighted composite
+// likelihood is the plain one of the site array in which site i stands w_i times: the scan kernels run unchanged on the array
+// these kernels build from a source slot's sites, with the bootstrap's weights w_i = boot_weight(key, i / B).
+//   resample_count_kernel    per tile of RS_TILE consecutive source sites (one workgroup): the sum of its weights
+//   prefix_kernel            the exclusive prefix of the tile sums (its last entry: N', the length of the resampled array)
+//   resample_expand_kernel   per tile again: the weights once more (integer comparisons: the same), an exclusive scan of them
+//                            inside the workgroup, and every site written w_i times from tile prefix + scan on; the copies of
+//                            every table row are counted in an LDS histogram per workgroup (tables of up to RS_HIST_MAX rows;
+//                            larger ones count with global atomics) that is added to the global counts once per workgroup
+// Three launches on one stream, no workgroup waits for another.  A thread takes RS_PER consecutive sites, so the order of the
+// sites is kept and a thread's block index advances without a division per site.
+constexpr int RS_THREADS = 256;
+constexpr int RS_PER = 4;
+constexpr int RS_TILE = RS_THREADS * RS_PER;
+constexpr int RS_HIST_MAX = 8192;             // rows of a workgroup's LDS histogram (32 KiB)
+constexpr int RS_BLOCKS_MAX = 2048;           // workgroups of the expansion (each strides over the tiles)
+
+// the weights of sites i0 .. i0 + RS_PER - 1 (0 past the end of the array); returns their sum
+__device__ __forceinline__ int rs_weights(uint64_t key, int64_t B, int64_t N, int64_t i0, int w[RS_PER]) {
+    int64_t b = i0 / B, rem = i0 - b * B;
+    int wb = boot_weight(key, (uint64_t)b), sum = 0;
+#pragma unroll
+    for (int k = 0; k < RS_PER; k++) {
+        w[k] = i0 + k < N ? wb : 0;
+        sum += w[k];
+        if (++rem == B) { rem = 0; ++b; wb = boot_weight(key, (uint64_t)b); }
+    }
+    return sum;
+}
+
+// inclusive scan of v over the workgroup's RS_THREADS threads (wave shuffles, then the wave totals through LDS); *total = the sum
+__device__ __forceinline__ int rs_block_scan(int v, int *total) {
+    __shared__ int wtot[RS_THREADS / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const int u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+    }
+    __syncthreads();                          // the previous tile's readers of wtot are done
+    if (lane == WAVE - 1) wtot[wv] = v;
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int k = 0; k < RS_THREADS / WAVE; k++) {
+        if (k < wv) before += wtot[k];
+        all += wtot[k];
+    }
+    *total = all;
+    return v + before;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void resample_count_kernel(uint64_t key, int64_t B, int64_t N, int64_t ntiles,
+                                                                    int32_t *__restrict__ tile_sum) {
+    __shared__ int wsum[RS_THREADS / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        int w[RS_PER];
+        int s = rs_weights(key, B, N, tile * RS_TILE + (int64_t)threadIdx.x * RS_PER, w);
+        for (int o = WAVE / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        __syncthreads();                      // the previous tile's sum has been read
+        if (lane == 0) wsum[wv] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int total = 0;
+            for (int k = 0; k < RS_THREADS / WAVE; k++) total += wsum[k];
+            tile_sum[tile] = total;
+        }
+    }
+}
+
+struct ResampleParams {
+    uint64_t key;
+    int64_t B, N, ntiles, N_out;
+    const double *src_gen;
+    const void *src_row;
+    double *dst_gen;
+    void *dst_row;
+    const int64_t *tile_pre;                  // [ntiles + 1]
+    int32_t *cnt;                             // [rows] copies per table row (zeroed before the launch)
+    int rows, use_hist;
+};
+
+template <class T>
+__global__ __launch_bounds__(RS_THREADS) void resample_expand_kernel(ResampleParams Q) {
+    extern __shared__ int rs_hist[];          // [rows] when use_hist
+    const T *__restrict__ src_row = (const T *)Q.src_row;
+    T *__restrict__ dst_row = (T *)Q.dst_row;
+    if (Q.use_hist) {
+        for (int r = threadIdx.x; r < Q.rows; r += RS_THREADS) rs_hist[r] = 0;
+        __syncthreads();
+    }
+    for (int64_t tile = blockIdx.x; tile < Q.ntiles; tile += gridDim.x) {
+        const int64_t i0 = tile * RS_TILE + (int64_t)threadIdx.x * RS_PER;
+        int w[RS_PER], total;
+        const int s = rs_weights(Q.key, Q.B, Q.N, i0, w);
+        int64_t o = Q.tile_pre[tile] + (rs_block_scan(s, &total) - s);
+#pragma unroll
+        for (int k = 0; k < RS_PER; k++) {
+            if (w[k] == 0) continue;          // (also every index past the end of the source)
+            const double g = Q.src_gen[i0 + k];
+            const T r = src_row[i0 + k];
+            for (int j = 0; j < w[k] && o < Q.N_out; j++, o++) {       // (o < N_out always holds: the prefix is of these weights)
+                Q.dst_gen[o] = g;
+                dst_row[o] = r;
+            }
+            if ((int)r < Q.rows) {
+                if (Q.use_hist) atomicAdd(&rs_hist[(int)r], w[k]);
+                else atomicAdd(&Q.cnt[(int)r], w[k]);
+            }
+        }
+    }
+    if (Q.use_hist) {
+        __syncthreads();
+        for (int r = threadIdx.x; r < Q.rows; r += RS_THREADS)
+            if (rs_hist[r]) atomicAdd(&Q.cnt[r], rs_hist[r]);
+    }
+}
+
+// After a replicate's scan: per peak k (one wave), the row of its range [lo[k], hi[k]] of the slot's test sites with the largest
+// CLR among the rows with a grid result (lin >= 0), the earliest such row on ties; -1 (and CLR 0) when no row has one.  Exact FP64
+// comparisons; the lanes stride over the range and keep their first best, then a butterfly in which both partners apply the
+// same rule.  A row is one wave's alone: no atomics.
+constexpr int LOCATE_THREADS = 256;
+__global__ __launch_bounds__(LOCATE_THREADS) void locate_reduce_kernel(const double *__restrict__ clr, const int32_t *__restrict__ lin,
+                                                                       const int32_t *__restrict__ lo, const int32_t *__restrict__ hi, int K,
+                                                                       int32_t *__restrict__ row_out, double *__restrict__ clr_out) {
+    const int k = blockIdx.x * (LOCATE_THREADS / WAVE) + threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    if (k >= K) return;
+    int32_t best = -1;
+    double bv = 0.0;
+    for (int64_t t = (int64_t)lo[k] + lane, e = hi[k]; t <= e; t += WAVE) {
+        if (lin[t] < 0) continue;
+        const double v = clr[t];
+        if (best < 0 || v > bv) { best = (int32_t)t; bv = v; }
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const int32_t ob = __shfl_xor(best, o);
+        const double ov = __shfl_xor(bv, o);
+        if (ob >= 0 && (best < 0 || ov > bv || (ov == bv && ob < best))) { best = ob; bv = ov; }
+    }
+    if (lane == 0) { row_out[k] = best; clr_out[k] = best >= 0 ? bv : 0.0; }
+}
+
 // ----------------------------------------------------------------------------- peaks
 // Peak calling on a CLR track (bmx_ctx_peaks / bmx_ctx_peaks_track; the definition is ballermixplus_amd/peaks.py): rows
 // t = 0 .. M-1 with non-decreasing positions g and values c.  Every comparison is an exact FP64 comparison and the only
@@ -4823,6 +4966,16 @@ struct ChromSlot {
     int64_t pk_M = 0, pk_K = 0;
     DevBuf<int32_t> pk_flag, pk_row, pk_lo, pk_hi, pk_sad;
 
+    // position bootstrap (bmx_ctx_locate_*): the peaks' ranges into this slot's test sites and, per (replicate, peak), the argmax
+    // row and its CLR.  Every replicate sets the slot's sites and test sites anew, so this state outlives them: locate_begin
+    // starts it, a new model ends it.
+    bool lc_ok = false;
+    uint64_t lc_seq = 0;         // scan_seq at locate_begin / the last accumulate
+    int32_t lc_K = 0, lc_R = 0;
+    int64_t lc_M = 0;            // 1 + the highest row any range names
+    DevBuf<int32_t> lc_lo, lc_hi, lc_row;
+    DevBuf<double> lc_clr;
+
     void release_peaks() {
         pk_have = false;
         pk_flag.release(); pk_row.release(); pk_lo.release(); pk_hi.release(); pk_sad.release();
@@ -4850,6 +5003,8 @@ struct ChromSlot {
         for (auto &b : pl_out) b.release();
         release_refined();
         release_peaks();
+        lc_ok = false;
+        lc_lo.release(); lc_hi.release(); lc_row.release(); lc_clr.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         ev0 = ev1 = nullptr;
@@ -4911,6 +5066,9 @@ struct bmx_ctx {
     hipEvent_t pk_ev0 = nullptr, pk_ev1 = nullptr;
     double pk_ms = -1.0;
     bool rf_at_peaks = false;
+    // resampled sites (bmx_ctx_resample_sites): the tile sums of the weights, their prefix, the copies per table row
+    DevBuf<int32_t> rs_tsum, rs_cnt;
+    DevBuf<int64_t> rs_tpre;
     std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
@@ -4998,6 +5156,97 @@ int select_slot(bmx_ctx *c, int slot) {
     return BMX_OK;
 }
 
+// What set_sites derives from the per-row site counts, the number of sites and the first and last position: the frequency ranking
+// of the rows (moment slots), kmom, rowmax and rowthr of slot s, uploaded on the context's stream.  Shared by bmx_ctx_set_sites
+// (counts from the host's validation pass) and bmx_ctx_resample_sites (counts from the device); returns with the stream idle.
+int derive_row_tables(bmx_ctx *c, ChromSlot *s, const std::vector<int64_t> &cnt, int64_t N, double g_first, double g_last) {
+    int rc;
+    // Moment slots for the far field: rank the rows by how many sites carry them.
+    // Slot s pays at a given A when the ~23 instructions saved per far site of that row outweigh
+    // the ~30 instructions its term costs at the end of each zone; the expected number of far sites
+    // per zone follows from the mean site density (a performance heuristic only: any choice is exact).
+    // The prepared group kernels have a cheaper place than the product for a far site without a slot
+    // (series entries, ~11 instructions less than the product): a second table with that gain for them
+    // (measured optimum 10-12, flat: profiles/r03_series_entries.txt).
+    std::vector<int> order((size_t)c->rows);
+    for (int r = 0; r < c->rows; r++) order[(size_t)r] = r;
+    const size_t ns = std::min((size_t)MOM_SLOTS, order.size());
+    std::partial_sort(order.begin(), order.begin() + ns, order.end(),
+                      [&](int a, int b) { return cnt[(size_t)a] != cnt[(size_t)b] ? cnt[(size_t)a] > cnt[(size_t)b] : a < b; });
+    std::vector<uint8_t> slot((size_t)c->rows, 255);
+    int nslots = 0;
+    for (size_t k = 0; k < ns; k++) {
+        if (cnt[(size_t)order[k]] == 0) break;
+        slot[(size_t)order[k]] = (uint8_t)k;
+        s->row_of_slot[k] = order[k];
+        nslots = (int)k + 1;
+    }
+    for (int k = nslots; k < MOM_SLOTS; k++) s->row_of_slot[k] = nslots ? s->row_of_slot[0] : 0;
+    s->nslots = nslots;
+    const int kcap = diag_env("BMX_MOM_SLOTS") ? std::min(std::max(atoi(diag_env("BMX_MOM_SLOTS")), 0), MOM_SLOTS) : MOM_SLOTS;
+    const double range = g_last - g_first;
+    std::vector<uint8_t> km(2 * (size_t)c->nA, 0);            // [0, nA): solo / round-2 kernels; [nA, 2 nA): prepared group kernels
+    s->kmom_max = 0;
+    s->kmom_max_ser = 0;
+    for (int t = 0; t < 2; t++) {
+        const double gain = diag_env("BMX_KMOM_GAIN") ? atof(diag_env("BMX_KMOM_GAIN")) : t ? 11.0 : 23.0;      // (threshold experiments)
+        for (int a = 0; a < c->nA; a++) {
+            const double nfar = range > 0 ? 0.8 * (double)(N - 1) / range * c->zcut / c->h_A[(size_t)a] : (double)N;
+            int k = 0;
+            while (k < nslots && k < kcap && (double)cnt[(size_t)s->row_of_slot[k]] / (double)N * nfar * gain > 30.0) k++;
+            km[(size_t)t * c->nA + a] = (uint8_t)k;
+            (t ? s->kmom_max_ser : s->kmom_max) = std::max(t ? s->kmom_max_ser : s->kmom_max, k);
+        }
+    }
+    // the kernel reads max |R| and the slot of a row with one load: the slot sits in the low mantissa
+    // byte of the (rounded up) maximum; +inf becomes NaN, which never compares as far
+    std::vector<double> packed(c->h_rowmax.size());
+    // BMX_ROWMAX_GLOBAL (diagnostic builds): one far threshold per row for all slices (its max |R| over the whole grid) -- what a
+    // classification shared by the slices would have to use; measures how many more near sites that costs
+    std::vector<double> rm_src(c->h_rowmax);
+    if (diag_env("BMX_ROWMAX_GLOBAL")) {
+        const size_t R_ = (size_t)c->rows, S_ = rm_src.size() / R_;
+        for (size_t r = 0; r < R_; r++) {
+            double m = 0.0;
+            bool nan = false;
+            for (size_t sl = 0; sl < S_; sl++) { const double v = rm_src[sl * R_ + r]; if (v != v) nan = true; else m = std::max(m, v); }
+            for (size_t sl = 0; sl < S_; sl++) if (!nan) rm_src[sl * R_ + r] = m;
+        }
+    }
+    for (size_t k = 0; k < packed.size(); k++) {
+        uint64_t bits;
+        memcpy(&bits, &rm_src[k], sizeof bits);
+        bits = ((bits & ~0xffull) + 0x100ull) | slot[k % (size_t)c->rows];
+        memcpy(&packed[k], &bits, sizeof bits);
+    }
+    if ((rc = upload(s->rowmax, (const double *)packed.data(), packed.size(), c->stream))) return rc;
+    if ((rc = upload(s->kmom, (const uint8_t *)km.data(), km.size(), c->stream))) return rc;
+    // prepared pipeline: ONE far threshold per row for all slices, in the exponent domain -- a site of the row at
+    // z = A d >= thr has alpha max_grid|R| <= far_eps (log rounded up, the low mantissa byte replaced by the row's slot
+    // after rounding up once more).  Rows with max|R| <= far_eps / e are far at any distance (thr = -1); rows absent from
+    // the helper file (max|R| = inf) get NaN, which never compares as far.
+    const double eps = P_EPS;
+    std::vector<double> thr((size_t)c->rows);
+    const size_t R_ = (size_t)c->rows, S_ = c->h_rowmax.size() / std::max<size_t>(R_, 1);
+    for (size_t r = 0; r < R_; r++) {
+        double m = 0.0;
+        for (size_t sl = 0; sl < S_; sl++) {
+            const double v = c->h_rowmax[sl * R_ + r];
+            m = (v != v || m != m) ? NAN : std::max(m, v);
+        }
+        double t = (m != m) ? INFINITY : (m <= eps * 0.36) ? -1.0 : std::log(m / eps) * (1.0 + 1e-12) + 1e-9;
+        if (t < 0.0 && t != -1.0) t = std::max(t, -1.0);
+        uint64_t bits;
+        memcpy(&bits, &t, sizeof bits);
+        if (t > 0.0) bits = ((bits & ~0xffull) + 0x100ull) | slot[r];     // rounds the threshold up; +inf becomes NaN
+        else bits = (bits & ~0xffull) | slot[r];                            // negative: far at any distance either way
+        memcpy(&thr[r], &bits, sizeof bits);
+    }
+    if ((rc = upload(s->rowthr, (const double *)thr.data(), thr.size(), c->stream))) return rc;
+    if ((rc = upload(s->d_row_of_slot, (const int *)s->row_of_slot, (size_t)MOM_SLOTS, c->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));     // the staging vectors go out of scope here
+    return BMX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -5070,6 +5319,7 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
     c->bt_keys.release(); c->bt_pws.release();
     c->pk_tmax.release(); c->pk_track.release(); c->pk_tfirst.release();
+    c->rs_tsum.release(); c->rs_cnt.release(); c->rs_tpre.release();
     if (c->pk_ev0) (void)hipEventDestroy(c->pk_ev0);
     if (c->pk_ev1) (void)hipEventDestroy(c->pk_ev1);
     dfree(c->d_prof);
@@ -5113,7 +5363,7 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_model(c);
     for (ChromSlot *s : c->slots)
-        if (s) drop_sites(s);      // row indices and the moment slots belong to the model they were set under
+        if (s) { drop_sites(s); s->lc_ok = false; }      // row indices and the moment slots belong to the model they were set under
     c->stat = m->stat; c->min_count = m->min_count; c->n_sizes = m->n_sizes;
     c->rows = m->row_off[m->n_sizes]; c->nx = m->nx; c->nab = m->nab; c->nA = nA;
     c->npairs = m->nx * m->nab;
@@ -5257,92 +5507,7 @@ int bmx_ctx_set_sites(bmx_ctx *c, int64_t N, const double *genpos, const int32_t
         if ((rc = upload(s->row16, (const uint16_t *)r16.data(), (size_t)N, c->stream))) return rc;
     }
     s->wide_rows = wide;
-    {
-        // Moment slots for the far field: rank the rows by how many sites carry them.
-        // Slot s pays at a given A when the ~23 instructions saved per far site of that row outweigh
-        // the ~30 instructions its term costs at the end of each zone; the expected number of far sites
-        // per zone follows from the mean site density (a performance heuristic only: any choice is exact).
-        // The prepared group kernels have a cheaper place than the product for a far site without a slot
-        // (series entries, ~11 instructions less than the product): a second table with that gain for them
-        // (measured optimum 10-12, flat: profiles/r03_series_entries.txt).
-        std::vector<int> order((size_t)c->rows);
-        for (int r = 0; r < c->rows; r++) order[(size_t)r] = r;
-        const size_t ns = std::min((size_t)MOM_SLOTS, order.size());
-        std::partial_sort(order.begin(), order.begin() + ns, order.end(),
-                          [&](int a, int b) { return cnt[(size_t)a] != cnt[(size_t)b] ? cnt[(size_t)a] > cnt[(size_t)b] : a < b; });
-        std::vector<uint8_t> slot((size_t)c->rows, 255);
-        int nslots = 0;
-        for (size_t k = 0; k < ns; k++) {
-            if (cnt[(size_t)order[k]] == 0) break;
-            slot[(size_t)order[k]] = (uint8_t)k;
-            s->row_of_slot[k] = order[k];
-            nslots = (int)k + 1;
-        }
-        for (int k = nslots; k < MOM_SLOTS; k++) s->row_of_slot[k] = nslots ? s->row_of_slot[0] : 0;
-        s->nslots = nslots;
-        const int kcap = diag_env("BMX_MOM_SLOTS") ? std::min(std::max(atoi(diag_env("BMX_MOM_SLOTS")), 0), MOM_SLOTS) : MOM_SLOTS;
-        const double range = genpos[N - 1] - genpos[0];
-        std::vector<uint8_t> km(2 * (size_t)c->nA, 0);            // [0, nA): solo / round-2 kernels; [nA, 2 nA): prepared group kernels
-        s->kmom_max = 0;
-        s->kmom_max_ser = 0;
-        for (int t = 0; t < 2; t++) {
-            const double gain = diag_env("BMX_KMOM_GAIN") ? atof(diag_env("BMX_KMOM_GAIN")) : t ? 11.0 : 23.0;      // (threshold experiments)
-            for (int a = 0; a < c->nA; a++) {
-                const double nfar = range > 0 ? 0.8 * (double)(N - 1) / range * c->zcut / c->h_A[(size_t)a] : (double)N;
-                int k = 0;
-                while (k < nslots && k < kcap && (double)cnt[(size_t)s->row_of_slot[k]] / (double)N * nfar * gain > 30.0) k++;
-                km[(size_t)t * c->nA + a] = (uint8_t)k;
-                (t ? s->kmom_max_ser : s->kmom_max) = std::max(t ? s->kmom_max_ser : s->kmom_max, k);
-            }
-        }
-        // the kernel reads max |R| and the slot of a row with one load: the slot sits in the low mantissa
-        // byte of the (rounded up) maximum; +inf becomes NaN, which never compares as far
-        std::vector<double> packed(c->h_rowmax.size());
-        // BMX_ROWMAX_GLOBAL (diagnostic builds): one far threshold per row for all slices (its max |R| over the whole grid) -- what a
-        // classification shared by the slices would have to use; measures how many more near sites that costs
-        std::vector<double> rm_src(c->h_rowmax);
-        if (diag_env("BMX_ROWMAX_GLOBAL")) {
-            const size_t R_ = (size_t)c->rows, S_ = rm_src.size() / R_;
-            for (size_t r = 0; r < R_; r++) {
-                double m = 0.0;
-                bool nan = false;
-                for (size_t sl = 0; sl < S_; sl++) { const double v = rm_src[sl * R_ + r]; if (v != v) nan = true; else m = std::max(m, v); }
-                for (size_t sl = 0; sl < S_; sl++) if (!nan) rm_src[sl * R_ + r] = m;
-            }
-        }
-        for (size_t k = 0; k < packed.size(); k++) {
-            uint64_t bits;
-            memcpy(&bits, &rm_src[k], sizeof bits);
-            bits = ((bits & ~0xffull) + 0x100ull) | slot[k % (size_t)c->rows];
-            memcpy(&packed[k], &bits, sizeof bits);
-        }
-        if ((rc = upload(s->rowmax, (const double *)packed.data(), packed.size(), c->stream))) return rc;
-        if ((rc = upload(s->kmom, (const uint8_t *)km.data(), km.size(), c->stream))) return rc;
-        // prepared pipeline: ONE far threshold per row for all slices, in the exponent domain -- a site of the row at
-        // z = A d >= thr has alpha max_grid|R| <= far_eps (log rounded up, the low mantissa byte replaced by the row's slot
-        // after rounding up once more).  Rows with max|R| <= far_eps / e are far at any distance (thr = -1); rows absent from
-        // the helper file (max|R| = inf) get NaN, which never compares as far.
-        const double eps = P_EPS;
-        std::vector<double> thr((size_t)c->rows);
-        const size_t R_ = (size_t)c->rows, S_ = c->h_rowmax.size() / std::max<size_t>(R_, 1);
-        for (size_t r = 0; r < R_; r++) {
-            double m = 0.0;
-            for (size_t sl = 0; sl < S_; sl++) {
-                const double v = c->h_rowmax[sl * R_ + r];
-                m = (v != v || m != m) ? NAN : std::max(m, v);
-            }
-            double t = (m != m) ? INFINITY : (m <= eps * 0.36) ? -1.0 : std::log(m / eps) * (1.0 + 1e-12) + 1e-9;
-            if (t < 0.0 && t != -1.0) t = std::max(t, -1.0);
-            uint64_t bits;
-            memcpy(&bits, &t, sizeof bits);
-            if (t > 0.0) bits = ((bits & ~0xffull) + 0x100ull) | slot[r];     // rounds the threshold up; +inf becomes NaN
-            else bits = (bits & ~0xffull) | slot[r];                            // negative: far at any distance either way
-            memcpy(&thr[r], &bits, sizeof bits);
-        }
-        if ((rc = upload(s->rowthr, (const double *)thr.data(), thr.size(), c->stream))) return rc;
-        if ((rc = upload(s->d_row_of_slot, (const int *)s->row_of_slot, (size_t)MOM_SLOTS, c->stream))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));     // the staging vectors go out of scope here
+    if ((rc = derive_row_tables(c, s, cnt, N, genpos[0], genpos[N - 1]))) return rc;
     s->N = N;
     s->has_sites = true;
     return BMX_OK;
@@ -6602,6 +6767,152 @@ int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double
     if (T) HIP_TRY(hipMemcpy(T, s->bt_T.p, nt * sizeof(double), hipMemcpyDeviceToHost));
     if (T_centre) HIP_TRY(hipMemcpy(T_centre, s->bt_Tc.p, nt * sizeof(double), hipMemcpyDeviceToHost));
     if (rounds) HIP_TRY(hipMemcpy(rounds, s->bt_rounds.p, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BMX_OK;
+}
+
+/* ---- resampled sites and the position bootstrap (ballermixplus_amd/locate.py holds the definition) ---- */
+
+int bmx_ctx_resample_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int64_t block, int64_t *N_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (!c->has_model) return fail(BMX_E_STATE, "set_model must precede resample_sites");
+    if (src_slot < 0 || src_slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
+    if (src_slot == c->cur_index) return fail(BMX_E_INVALID, "resample_sites: the source slot must not be the selected slot");
+    if (block < 1) return fail(BMX_E_INVALID, "resampling block size must be >= 1");
+    ChromSlot *src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot] : nullptr;
+    if (!src || !src->has_sites) return fail(BMX_E_STATE, "resample_sites: the source slot has no sites");
+    ChromSlot *s = c->cur;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_sites(s);
+    if (N_out) *N_out = 0;
+    const int64_t N = src->N, ntiles = (N + RS_TILE - 1) / RS_TILE;
+    HIP_TRY(c->rs_tsum.ensure((size_t)ntiles));
+    HIP_TRY(c->rs_tpre.ensure((size_t)ntiles + 1));
+    HIP_TRY(c->rs_cnt.ensure((size_t)c->rows));
+    const unsigned blocks = (unsigned)std::min<int64_t>(ntiles, RS_BLOCKS_MAX);
+    hipLaunchKernelGGL(resample_count_kernel, dim3(blocks), dim3(RS_THREADS), 0, c->stream, key, block, N, ntiles, c->rs_tsum.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rs_tsum.p, ntiles, c->rs_tpre.p);
+    HIP_TRY(hipGetLastError());
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, c->rs_tpre.p + ntiles, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (total >= 0x7fffffffLL) return fail(BMX_E_LIMIT, "resample_sites: more than 2^31 resampled sites");
+    if (total < 1) return BMX_OK;             // every weight is 0: the slot stays without sites
+    const bool wide = src->wide_rows;
+    HIP_TRY(s->genpos.ensure((size_t)total));
+    if (wide) HIP_TRY(s->row32.ensure((size_t)total));
+    else HIP_TRY(s->row16.ensure((size_t)total));
+    HIP_TRY(hipMemsetAsync(c->rs_cnt.p, 0, (size_t)c->rows * sizeof(int32_t), c->stream));
+    ResampleParams Q;
+    Q.key = key; Q.B = block; Q.N = N; Q.ntiles = ntiles; Q.N_out = total;
+    Q.src_gen = src->genpos.p;
+    Q.src_row = wide ? (const void *)src->row32.p : (const void *)src->row16.p;
+    Q.dst_gen = s->genpos.p;
+    Q.dst_row = wide ? (void *)s->row32.p : (void *)s->row16.p;
+    Q.tile_pre = c->rs_tpre.p;
+    Q.cnt = c->rs_cnt.p;
+    Q.rows = c->rows;
+    Q.use_hist = c->rows <= RS_HIST_MAX ? 1 : 0;
+    const size_t lds = Q.use_hist ? (size_t)c->rows * sizeof(int) : 0;
+    if (wide) hipLaunchKernelGGL(resample_expand_kernel<uint32_t>, dim3(blocks), dim3(RS_THREADS), lds, c->stream, Q);
+    else hipLaunchKernelGGL(resample_expand_kernel<uint16_t>, dim3(blocks), dim3(RS_THREADS), lds, c->stream, Q);
+    HIP_TRY(hipGetLastError());
+    // the per-row counts and the two end positions come back; everything set_sites derives from them follows on the host
+    std::vector<int32_t> cnt32((size_t)c->rows);
+    double ends[2] = {0.0, 0.0};
+    HIP_TRY(hipMemcpyAsync(cnt32.data(), c->rs_cnt.p, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[0], s->genpos.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[1], s->genpos.p + (total - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> cnt(cnt32.begin(), cnt32.end());
+    s->wide_rows = wide;
+    int rc;
+    if ((rc = derive_row_tables(c, s, cnt, total, ends[0], ends[1]))) return rc;
+    s->N = total;
+    s->has_sites = true;
+    if (N_out) *N_out = total;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_sites(bmx_ctx *c, double *genpos_out, int32_t *row_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_sites) return fail(BMX_E_STATE, "fetch_sites: the selected slot has no sites");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t N = (size_t)s->N;
+    if (genpos_out) HIP_TRY(hipMemcpy(genpos_out, s->genpos.p, N * sizeof(double), hipMemcpyDeviceToHost));
+    if (row_out) {
+        if (s->wide_rows) {
+            HIP_TRY(hipMemcpy(row_out, s->row32.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        } else {
+            std::vector<uint16_t> r16(N);
+            HIP_TRY(hipMemcpy(r16.data(), s->row16.p, N * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < N; i++) row_out[i] = (int32_t)r16[i];
+        }
+    }
+    return BMX_OK;
+}
+
+int bmx_ctx_locate_begin(bmx_ctx *c, int32_t K, const int32_t *lo, const int32_t *hi, int32_t R) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (K < 1 || R < 1 || !lo || !hi) return fail(BMX_E_INVALID, "locate_begin: K >= 1 ranges and R >= 1 replicates are needed");
+    if ((int64_t)K * R > BMX_LOCATE_MAX_RESULTS) return fail(BMX_E_LIMIT, "locate_begin: more than 2^26 (peak, replicate) results");
+    int64_t top = 0;
+    for (int32_t k = 0; k < K; k++) {
+        if (lo[k] < 0 || hi[k] < lo[k]) return fail(BMX_E_INVALID, "locate_begin: a range must have 0 <= lo <= hi");
+        top = std::max<int64_t>(top, (int64_t)hi[k] + 1);
+    }
+    ChromSlot *s = c->cur;
+    HIP_TRY(hipSetDevice(c->device));
+    s->lc_ok = false;
+    const size_t n = (size_t)K * (size_t)R;
+    int rc;
+    if ((rc = upload(s->lc_lo, lo, (size_t)K, c->stream))) return rc;
+    if ((rc = upload(s->lc_hi, hi, (size_t)K, c->stream))) return rc;
+    HIP_TRY(s->lc_row.ensure(n));
+    HIP_TRY(s->lc_clr.ensure(n));
+    HIP_TRY(hipMemsetAsync(s->lc_row.p, 0xff, n * sizeof(int32_t), c->stream));      // -1: no argmax (a replicate never accumulated)
+    HIP_TRY(hipMemsetAsync(s->lc_clr.p, 0, n * sizeof(double), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));       // lo / hi are the caller's
+    s->lc_ok = true;
+    s->lc_K = K;
+    s->lc_R = R;
+    s->lc_M = top;
+    s->lc_seq = s->scan_seq;
+    return BMX_OK;
+}
+
+int bmx_ctx_locate_accumulate(bmx_ctx *c, int32_t r) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->lc_ok) return fail(BMX_E_STATE, "locate_begin must precede locate_accumulate");
+    if (r < 0 || r >= s->lc_R) return fail(BMX_E_INVALID, "locate_accumulate: replicate index outside [0, R)");
+    if (!s->has_tests || !s->timed || s->scan_seq == s->lc_seq)
+        return fail(BMX_E_STATE, "locate_accumulate needs a new scan (one per replicate)");
+    if (s->M < s->lc_M) return fail(BMX_E_INVALID, "locate_accumulate: a range reaches past the slot's test sites");
+    HIP_TRY(hipSetDevice(c->device));
+    const int per = LOCATE_THREADS / WAVE;
+    hipLaunchKernelGGL(locate_reduce_kernel, dim3((unsigned)((s->lc_K + per - 1) / per)), dim3(LOCATE_THREADS), 0, c->stream,
+                       (const double *)s->clr.p, (const int32_t *)s->lin.p, (const int32_t *)s->lc_lo.p, (const int32_t *)s->lc_hi.p,
+                       (int)s->lc_K, s->lc_row.p + (size_t)r * s->lc_K, s->lc_clr.p + (size_t)r * s->lc_K);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int st = check_status(c)) return st;      // the replicate's scan must have been sound
+    s->lc_seq = s->scan_seq;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_locate(bmx_ctx *c, int32_t *row_out, double *clr_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->lc_ok) return fail(BMX_E_STATE, "locate_begin must precede fetch_locate");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)s->lc_K * (size_t)s->lc_R;
+    if (row_out) HIP_TRY(hipMemcpy(row_out, s->lc_row.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (clr_out) HIP_TRY(hipMemcpy(clr_out, s->lc_clr.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return BMX_OK;
 }
 

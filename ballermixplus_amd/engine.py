@@ -347,6 +347,50 @@ class Context:
                                               d(out['T']), d(out['T_centre']), _lib.as_ip(out['rounds'])))
         return out
 
+    def slot_count(self):
+        """Number of slot indices in use (highest selected slot + 1)."""
+        return int(self._L.bmx_ctx_slot_count(self._h))
+
+    def resample_sites(self, src_slot, key, block=1):
+        """The selected slot receives the resampled sites of slot src_slot under the block-bootstrap weights of (key, block)
+        (ballermixplus_amd/locate.py: np.repeat of positions and rows by boot.site_weights), built on the device; the slot is
+        then as after set_sites of those arrays.  Returns the number of resampled sites (0: the slot has no sites)."""
+        n = C.c_int64()
+        self.M = 0
+        self._slot_M.pop(self.slot, None)
+        _lib.check(self._L.bmx_ctx_resample_sites(self._h, int(src_slot), C.c_uint64(int(key) & ((1 << 64) - 1)), int(block),
+                                                  C.byref(n)))
+        self.N = n.value
+        return n.value
+
+    def fetch_sites(self, N=None):
+        """(genpos f64[N], rows i32[N]) of the selected slot as the device holds them; N: the slot's number of sites (default:
+        that of the last set_sites / resample_sites call of this wrapper)."""
+        N = int(self.N if N is None else N)
+        g, r = np.empty(N, dtype=np.float64), np.empty(N, dtype=np.int32)
+        _lib.check(self._L.bmx_ctx_fetch_sites(self._h, _lib.as_dp(g), _lib.as_ip(r)))
+        return g, r
+
+    def locate_begin(self, lo, hi, R):
+        """Start the position bootstrap's reduction on the selected slot: one inclusive range [lo[k], hi[k]] into its test
+        sites per peak, R replicates."""
+        lo, hi = _lib.i32(lo), _lib.i32(hi)
+        if lo.shape != hi.shape or lo.ndim != 1:
+            raise ValueError('one (lo, hi) pair per peak is needed')
+        self._locate_shape = (int(R), len(lo))
+        _lib.check(self._L.bmx_ctx_locate_begin(self._h, len(lo), _lib.as_ip(lo), _lib.as_ip(hi), int(R)))
+
+    def locate_accumulate(self, r):
+        """After the scan of replicate r: per peak, the argmax row of its range and the CLR there."""
+        _lib.check(self._L.bmx_ctx_locate_accumulate(self._h, int(r)))
+
+    def fetch_locate(self):
+        """(row i32[R, K], clr f64[R, K]) of the reduction begun by locate_begin: row -1 where a replicate has no argmax."""
+        R, K = self._locate_shape
+        row, clr = np.empty((R, K), dtype=np.int32), np.empty((R, K), dtype=np.float64)
+        _lib.check(self._L.bmx_ctx_fetch_locate(self._h, _lib.as_ip(row), _lib.as_dp(clr)))
+        return row, clr
+
     def peaks(self, sep, min_clr=0.0, frac=0.5):
         """Call peaks (ballermixplus_amd/peaks.py) on the selected slot's last scan: separation sep in the units of the test
         positions, floor min_clr, extent fraction frac.  Returns fetch_peaks()."""

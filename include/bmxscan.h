@@ -327,6 +327,43 @@ int bmx_ctx_boot_count(bmx_ctx *c, int64_t *n_sel, int32_t *R);
 int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double *abeta, double *T, double *T_centre,
                        int32_t *rounds);
 
+/* ---- resampled sites and the position bootstrap (opt-in; the CLI's --locate; ballermixplus_amd/locate.py) ----------------
+ * An integer-weighted composite likelihood is the plain one of the site array in which site i stands w_i times, at its position
+ * and with its table row.  So a bootstrap replicate of the whole grid scan -- a global argmax per test position, not a local
+ * search -- is bmx_ctx_scan on a resampled site array: the scan kernels run unchanged (they already handle runs of sites at one
+ * position, test positions that are no site, and exclude every site at the test position).  These entry points build that
+ * array on the device and reduce each replicate's track to one argmax per peak.  They arrived without a bump of
+ * BMX_ABI_VERSION_MINOR, as the groups above did: look the symbols up to find out whether a binary has them. */
+/* The SELECTED slot receives the resampled sites of slot src_slot: site i of src_slot w(key, i / block) times (the bootstrap's
+ * weights, 0..20), order kept, weight-0 sites dropped -- np.repeat(genpos, w), np.repeat(row, w).  Built on the device (tile
+ * sums of the weights, a prefix of the sums, an expansion that also counts the copies per table row; no workgroup waits for
+ * another); the counts and the two end positions come back to the host, which derives from them what bmx_ctx_set_sites derives
+ * from the host arrays.  Afterwards the selected slot is in exactly the state bmx_ctx_set_sites leaves for the expanded arrays
+ * (its test sites are discarded); src_slot is read only and keeps its sites, test sites, results and every other state.  The
+ * rows taken are the ones src_slot holds now (a permutation by bmx_ctx_permute_rows included).  *N_out (may be NULL) = the
+ * number of resampled sites N'.  N' == 0 is BMX_OK and leaves the selected slot without sites; N' >= 2^31 - 1 is BMX_E_LIMIT
+ * (the slot is left without sites); src_slot == the selected slot, a slot index out of range or block < 1 is BMX_E_INVALID; a
+ * source without sites is BMX_E_STATE.  Blocks. */
+int bmx_ctx_resample_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int64_t block, int64_t *N_out);
+/* The selected slot's site arrays as the device holds them: genpos_out[N], row_out[N] (table rows as int32); either may be
+ * NULL.  BMX_E_STATE without sites.  Blocks. */
+int bmx_ctx_fetch_sites(bmx_ctx *c, double *genpos_out, int32_t *row_out);
+/* The position bootstrap's reduction, on the selected slot (the replicates' slot).  locate_begin: K >= 1 peaks with inclusive
+ * ranges lo[k] <= hi[k] into the slot's test sites (ranges may overlap), R >= 1 replicates; every result starts as (row -1,
+ * CLR 0).  At most BMX_LOCATE_MAX_RESULTS (peak, replicate) results (12 bytes each on the device), else BMX_E_LIMIT.  Every
+ * replicate sets the slot's sites and test sites anew, so this state outlives set_sites / resample_sites / set_tests; a new
+ * locate_begin or a new model ends it.
+ * locate_accumulate: after the scan of replicate r (0 <= r < R), one wave per peak reduces the scan's results over the peak's
+ * range to (row, CLR): the row with the largest CLR among the rows with a grid result (lin >= 0), the earliest such row on
+ * equality, exact FP64 comparisons; (-1, 0) when no row of the range has a grid result.  BMX_E_STATE without locate_begin or
+ * when no scan was launched since locate_begin / the previous accumulate; BMX_E_INVALID when a range reaches past the slot's
+ * test sites.  Blocks, and checks the scan's device status as null_accumulate does.
+ * fetch_locate: row_out[R][K] (indices into the slot's test sites) and clr_out[R][K]; either may be NULL.  Blocks. */
+#define BMX_LOCATE_MAX_RESULTS (1LL << 26)
+int bmx_ctx_locate_begin(bmx_ctx *c, int32_t K, const int32_t *lo, const int32_t *hi, int32_t R);
+int bmx_ctx_locate_accumulate(bmx_ctx *c, int32_t r);
+int bmx_ctx_fetch_locate(bmx_ctx *c, int32_t *row_out, double *clr_out);
+
 /* ---- peaks of the CLR track (opt-in; the CLI's --peaks; ballermixplus_amd/peaks.py holds the definition) ------------------
  * The track: rows t = 0 .. M-1 with non-decreasing positions g and values c.  Row t is an APEX iff c_t > 0, c_t >= min_clr and no
  * other row s with g_t - g_s <= sep and g_s - g_t <= sep has c_s > c_t, or c_s == c_t and s < t (a local-maximum rule, not greedy
