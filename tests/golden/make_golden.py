@@ -215,6 +215,13 @@ E2E = {
                                     '--fixAlpha', '7', '--listA', '250,1e3,77.5', '-s', '5'], None),
     'ex1_B2maf_s20': (['-i', REF_TEST + '/Example1_fullSweep_200kya_MAF.txt', '--spect',
                        REF_TEST + '/HC_CEU_Neut_MAF_spect_for_B2maf.txt', '--MAF', '-s', '20'], None),
+    # the two one-coordinate grids of the CLI: --fixX alone (1 x 51 pairs), --fixAlpha alone (10 x 1 pairs), every 5th site.  (With -s 2
+    # the --fixAlpha run meets two windows whose CLR is 2.9e-8: the reference resolves its T to 1e-16 absolute there, 5e-9 of
+    # that CLR, which no other arithmetic can reproduce to the 1e-9 relative the oracle tests ask of a golden file.)
+    'ex1_B2_fixX': (['-i', REF_TEST + '/Example1_fullSweep_200kya_DAF.txt', '--spect',
+                     REF_TEST + '/HC_CEU_Neut_DAF_spect_for_B2.txt', '--fixX', '0.3', '-s', '5'], None),
+    'ex1_B2_fixAlpha': (['-i', REF_TEST + '/Example1_fullSweep_200kya_DAF.txt', '--spect',
+                         REF_TEST + '/HC_CEU_Neut_DAF_spect_for_B2.txt', '--fixAlpha', '7', '-s', '5'], None),
 }
 
 
