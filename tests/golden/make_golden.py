@@ -7,7 +7,7 @@ imported by path and driven through its own classes/functions; nothing of its
 source is copied.  Each sub-command writes small data files (inputs + expected
 outputs) next to this script.
 
-    python tests/golden/make_golden.py lut        # NormalizedBetaBinom tables
+    python tests/golden/make_golden.py lut [NAME ...]   # NormalizedBetaBinom tables (all, or lut_B2_n24x40_bal_min8 ...)
     python tests/golden/make_golden.py setorder   # list(set(grid)) iteration orders
     python tests/golden/make_golden.py surface    # per-site T[A,x,a] surfaces
     python tests/golden/make_golden.py helpers    # --getSpect / --getConfig outputs
@@ -58,7 +58,7 @@ def grid_of(ref, kind):
 
 
 # ----------------------------------------------------------------------------- lut
-def cmd_lut():
+def cmd_lut(only=()):
     """normProbs[(x,a)] for every admissible k, per statistic / n / minCount."""
     ref = load_ref()
     tmp = '/tmp/bmx_golden_lut.txt'
@@ -69,19 +69,29 @@ def cmd_lut():
     cases += [('B2', 50, 'default', 2), ('B2maf', 50, 'bal', 2), ('B2', 200, 'bal', 1),
               ('B0maf', 50, 'default', 3), ('B1', 50, 'default', 1), ('B2', 7, 'default', 1),
               ('B2maf', 9, 'default', 1), ('B2maf', 8, 'bal', 1)]
+    # Tables past the pairwise-summation threshold (8 or more excluded counts) and with several sample sizes, on the --findBal grid.
+    # Several sizes: n is a tuple, the rows of every size go into the one input file, and the file name joins the sizes with 'x'
+    # (lut_B2_n24x40_bal_min8.npz), so that the statistic stays the first '_' field of the name.
+    cases += [('B2maf', 50, 'bal', 5), ('B0maf', 50, 'bal', 8), ('B2', (24, 40), 'bal', 8), ('B0', 41, 'bal', 7),
+              ('B2maf', (33, 40), 'bal', 8), ('B1', (12, 50), 'bal', 1)]
+
+    def ks_of(stat, n, minc):
+        if stat == 'B1':
+            return [0, 1]
+        if stat.endswith('maf'):
+            lo = 0 if not stat.startswith('B0') else minc
+            return [k for k in range(lo, n // 2 + 1) if k == 0 or k >= minc]
+        return list(range(minc, (n - 1 if stat.startswith('B0') else n) + 1))
+
     for stat, n, gkind, minc in cases:
+        sizes = n if isinstance(n, tuple) else (n,)
+        tag = 'x'.join(str(v) for v in sizes)
+        if only and 'lut_%s_n%s_%s_min%d' % (stat, tag, gkind, minc) not in only:
+            continue
         maf = stat.endswith('maf')
         nosub = stat.startswith('B0')
         nofreq = stat == 'B1'
-        if nofreq:
-            ks = [0, 1]
-        elif maf:
-            lo = 0 if not nosub else minc
-            ks = [k for k in range(lo, n // 2 + 1) if k == 0 or k >= minc]
-        else:
-            hi = n - 1 if nosub else n
-            ks = list(range(minc, hi + 1))
-        rows = [(k, n) for k in ks]
+        rows = [(k, v) for v in sizes for k in ks_of(stat, v, minc)]
         # two sample sizes in one file for one case, to pin the per-n handling
         if stat == 'B2' and n == 50 and minc == 1:
             rows += [(k, 40) for k in range(1, 41)]
@@ -93,7 +103,7 @@ def cmd_lut():
         xs = list(grid.x)
         abs_ = list(grid.abeta)
         tab = np.stack([np.stack([nb.get(x, a) for a in abs_]) for x in xs])
-        name = 'lut_%s_n%d_%s_min%d.npz' % (stat, n, gkind, minc)
+        name = 'lut_%s_n%s_%s_min%d.npz' % (stat, tag, gkind, minc)
         np.savez_compressed(os.path.join(HERE, name), table=tab,
                             x=np.array(xs, dtype=np.float64), abeta=np.array(abs_, dtype=np.float64),
                             count=np.asarray(data.count), total=np.asarray(data.total),
@@ -384,7 +394,7 @@ if __name__ == '__main__':
         cmd_hostmodel()
         sys.exit(0)
     if cmd == 'lut':
-        cmd_lut()
+        cmd_lut(sys.argv[2:])
     elif cmd == 'setorder':
         cmd_setorder()
     elif cmd == 'surface':

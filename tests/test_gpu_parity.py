@@ -22,7 +22,9 @@ def _engine():
 
 @pytest.mark.parametrize('path', LUTS, ids=[os.path.basename(p)[4:-4] for p in LUTS])
 def test_device_selection_table_matches_reference(path):
-    """K1 (device lgamma / beta-binomial) vs NormalizedBetaBinom.normProbs of the reference."""
+    """K1 (device lgamma / beta-binomial) vs NormalizedBetaBinom.normProbs of the reference.  The fixtures pin the glibc of the
+    host that made them (scipy's lgam calls its log), and K1 follows the log of the host it RUNS on through LogPatch: on a host
+    whose libm rounds a patched argument differently this is the test that fails first, at alpha_beta >= 1e4."""
     eng = _engine()
     stat = os.path.basename(path)[4:-4].split('_')[0]
     z = np.load(path)
