@@ -99,6 +99,9 @@ PROTOTYPES = {
     'bmx_ctx_locate_begin': (C.c_int, [_vp, C.c_int32, _ip, _ip, C.c_int32]),
     'bmx_ctx_locate_accumulate': (C.c_int, [_vp, C.c_int32]),
     'bmx_ctx_fetch_locate': (C.c_int, [_vp, _ip, _dp]),
+    'bmx_ctx_plant_sites': (C.c_int, [_vp, C.c_int32, C.c_uint64, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, _lp]),
+    'bmx_ctx_plant_ms': (C.c_int, [_vp, _dp]),
+    'bmx_ctx_fetch_at': (C.c_int, [_vp, C.c_int64, _ip, _dp, _ip, _ip]),
     'bmx_ctx_peaks': (C.c_int, [_vp, C.c_double, C.c_double, C.c_double]),
     'bmx_ctx_peaks_track': (C.c_int, [_vp, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_double]),
     'bmx_ctx_peak_count': (C.c_int, [_vp, _lp, _lp]),

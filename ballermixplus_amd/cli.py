@@ -44,6 +44,15 @@ Additions (do not change any reference command line):
                     (percentile ends at level L as rows of the main output, the spread, the share of replicates at the apex and
                     at the ends of the range) and with --locateReps <out>.locate.reps.txt next to each output file.  Default
                     window mode only (no -w, no --fixWinSize).
+  --power R --plant A,x,abeta [--powerThreshold C[,C...]] [--plantEvery D] [--powerSpan H] [--powerSeed S]
+  [--powerBackground perm|obs] [--powerBlock B] [--powerReps]     planted-signal power analysis (ballermixplus_amd/power.py): R
+                    replicates redraw, on the device, the derived counts of the sites within reach of centres every D along the
+                    track from the mixture the scan fits at the grid point A,x,abeta (on the rows permuted in blocks of B sites,
+                    or on the observed rows), scan the test positions within H of the centres and compare each centre's maximum
+                    with the thresholds C (with --nullPerm: also the run's genome-wide 5 % and 1 % thresholds; the power step
+                    then runs after the null); writes <out>.power.txt (per centre: the power at each threshold, the spread of the
+                    maxima and of their positions, how often the planted grid values are recovered) and with --powerReps
+                    <out>.power.reps.txt next to each output file.  Default window mode only.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m ballermixplus_amd.cli ...`;
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
@@ -204,7 +213,106 @@ def build_parser():
     parser.add_argument('--locateReps', dest='locateReps', action='store_true', default=False,
                         help='MI355X build only, with --locate: also write the argmax of every replicate of every peak to '
                              '<out>.locate.reps.txt')
+    parser.add_argument('--power', dest='power', type=int, default=0,
+                        help='MI355X build only: planted-signal power analysis with this many replicates (>= 2; 0: off).  Every '
+                             'replicate redraws the derived counts of the sites within reach of evenly spaced centres from the '
+                             'mixture of the grid point --plant, scans the neighbourhoods and compares each maximum with the '
+                             'thresholds; <out>.power.txt holds, per centre, the power and how well the locus is placed')
+    parser.add_argument('--plant', dest='plant', type=str, default=None,
+                        help='MI355X build only, with --power: the planted grid point A,x,abeta (values of the run\'s grids)')
+    parser.add_argument('--plantEvery', dest='plantEvery', type=float, default=None,
+                        help='MI355X build only, with --power: spacing D of the centres in the units of the test positions '
+                             '(default 1.05 x the smallest spacing at which the loci do not disturb each other)')
+    parser.add_argument('--powerSpan', dest='powerSpan', type=float, default=None,
+                        help='MI355X build only, with --power: half-width H of the range searched around every centre (default '
+                             '--peaks\' G when given, else the reach of the planted A)')
+    parser.add_argument('--powerSeed', dest='powerSeed', type=int, default=None,
+                        help='MI355X build only, with --power: seed of the draws (default 1; its stream is separate from the '
+                             'other seeds\')')
+    parser.add_argument('--powerBackground', dest='powerBackground', type=str, default=None,
+                        help='MI355X build only, with --power: perm (default; the rows are permuted in blocks of --powerBlock '
+                             'sites before planting) or obs (the observed rows)')
+    parser.add_argument('--powerBlock', dest='powerBlock', type=int, default=None,
+                        help='MI355X build only, with --power: sites per block of the perm background (default 1)')
+    parser.add_argument('--powerThreshold', dest='powerThreshold', type=str, default=None,
+                        help='MI355X build only, with --power: CLR thresholds C[,C...]; with --nullPerm the run\'s own genome-wide '
+                             '5%% and 1%% thresholds are added')
+    parser.add_argument('--powerReps', dest='powerReps', action='store_true', default=False,
+                        help='MI355X build only, with --power: also write every replicate of every centre to <out>.power.reps.txt')
     return parser
+
+
+def power_refusal(opt):
+    """The message that refuses a --power / --plant* / --power* command line, or None when it can run (or the power analysis
+    is off).  Whether --plant names grid values is asked once the grids are known."""
+    for flag, v in (('--plant', opt.plant), ('--plantEvery', opt.plantEvery), ('--powerSpan', opt.powerSpan),
+                    ('--powerSeed', opt.powerSeed), ('--powerBackground', opt.powerBackground), ('--powerBlock', opt.powerBlock),
+                    ('--powerThreshold', opt.powerThreshold), ('--powerReps', opt.powerReps or None)):
+        if v is not None and not opt.power:
+            return '%s needs --power.' % flag
+    if not opt.power:
+        return None
+    from . import power
+    refused = power.value_refusal(opt.power, opt.plantEvery, opt.powerSpan, opt.powerBlock, opt.powerBackground, opt.powerThreshold)
+    if refused:
+        return refused
+    if opt.plant is None:
+        return '--power needs --plant A,x,abeta: the grid point whose mixture the sites are drawn from.'
+    if opt.powerThreshold is None and not opt.nullPerm:
+        return '--power needs --powerThreshold C[,C...] or --nullPerm (whose genome-wide thresholds it then uses).'
+    if opt.getSpec or opt.getConfig:
+        return '--power scans the input; it cannot be combined with --getSpect / --getConfig.'
+    if opt.w != 0 or opt.size:
+        return ('--power needs the default window mode (no -w, no --fixWinSize): the replicates are scanned with every window '
+                'holding all sites.')
+    if not opt.outfile:
+        return '--power needs -o: the power file is written next to the output.'
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
+        return '--power runs in a single process; multi-rank launches are not supported.'
+    return None
+
+
+def planted_point(opt, grid):
+    """(iA, ix, ia) of --plant in the grids' scan order; the run is refused, with the grids printed, unless it names grid values."""
+    from . import power
+    xs, abetas, As = grid.scan_order()
+    try:
+        planted = power.parse_plant(opt.plant, As, xs, abetas)
+    except ValueError as e:
+        print(e)
+        sys.exit(1)
+    if opt.plantEvery is not None:      # refused before anything is scanned
+        A_plant = float(As[planted[0]])
+        H = opt.powerSpan if opt.powerSpan is not None else opt.peaks if opt.peaks is not None else power.ALPHA_CUT / A_plant
+        bound = power.bound_of(H, float(min(As)), A_plant)
+        if opt.plantEvery < bound:
+            print(power.spacing_refusal(opt.plantEvery, bound))
+            sys.exit(1)
+    return planted
+
+
+def write_power(opt, ctx, sel, outfile, ts, genpos, planted, null_maxima, say, f=0):
+    """<outfile>.power.txt (with --powerReps <outfile>.power.reps.txt) of one file (input-file ordinal f) whose sites are in
+    ctx's selected slot; null_maxima: the genome-wide maxima of --nullPerm's replicates, or None."""
+    from . import null, power
+    thr = power.parse_thresholds(opt.powerThreshold) if opt.powerThreshold is not None else []
+    if null_maxima is not None:
+        for t in (null.threshold(null_maxima, 0.95), null.threshold(null_maxima, 0.99)):
+            if t not in thr:            # (few replicates: the two levels may name one maximum)
+                thr.append(t)
+    line_of_row = np.asarray(ts.order, dtype=np.int64) + 1 if ts.na_rows else None
+    try:
+        n, mean = power.power_and_write(ctx, outfile, ts, genpos, sel.model, sel.grid_A, planted, thr, opt.power,
+                                        opt.powerSeed if opt.powerSeed is not None else 1, opt.powerBackground or 'perm',
+                                        opt.powerBlock if opt.powerBlock is not None else 1,
+                                        opt.powerSpan if opt.powerSpan is not None else opt.peaks, opt.plantEvery, f, opt.powerReps,
+                                        line_of_row, ([f'{v}' for v in sel.grid_x], [f'{v}' for v in sel.grid_abeta],
+                                                      [f'{v}' for v in sel.grid_A]))
+    except ValueError as e:
+        print(e)
+        sys.exit(1)
+    say(f'\n{datetime.now()}. Power: {n} centre/s, {opt.power} replicates -> {power.output_name(outfile)}; mean power '
+        + ', '.join('%r: %s' % (float(C), 'NA' if m != m else repr(m)) for C, m in zip(thr, mean)))
 
 
 def locate_refusal(opt):
@@ -495,7 +603,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
+    refused = power_refusal(opt) or locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)
@@ -559,6 +667,7 @@ def main(argv=None):
     say('Retrieving per-site neutral probabilities...')
     Neutral.get_neut_probs(data)
     grid = Grids(opt.x, opt.abeta, opt.bal, opt.pos, opt.seqA, opt.listA)
+    planted = planted_point(opt, grid) if opt.power else None
     say('\nOptimizing over x= ' + ', '.join(['%g' % (x) for x in grid.x]))
     say('\n \t alpha= ' + ', '.join([str(a) for a in grid.abeta]))
     say('\n \t A= ' + ', '.join([str(A) for A in grid.A]))
@@ -601,6 +710,10 @@ def main(argv=None):
         got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
         finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
         stamp('permutation null')
+    if opt.power:
+        write_power(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites, data.genPos, planted,
+                    got[3] if opt.nullPerm else None, say)
+        stamp('power')
     if opt.peaks is not None:
         n = len(write_peaks(opt.outfile, called, bool(opt.nullPerm)))
         say(f'\n{datetime.now()}. Peaks: {n} (separation {opt.peaks!r}) -> {opt.outfile}.peaks.txt')
@@ -675,6 +788,7 @@ def main_many(opt, files, stamp=lambda what: None):
         for d in sorted(set(os.path.dirname(os.path.abspath(o)) for o in outs)):
             os.makedirs(d, exist_ok=True)
     grid = Grids(opt.x, opt.abeta, opt.bal, opt.pos, opt.seqA, opt.listA)
+    planted = planted_point(opt, grid) if opt.power else None
     say('\nOptimizing over x= ' + ', '.join(['%g' % (x) for x in grid.x]))
     say('\n \t alpha= ' + ', '.join([str(a) for a in grid.abeta]))
     say('\n \t A= ' + ', '.join([str(A) for A in grid.A]))
@@ -703,6 +817,7 @@ def main_many(opt, files, stamp=lambda what: None):
     kernel_ms = 0.0
     null_files = []
     peak_files = []
+    power_files = []
     if opt.peaks is not None:
         ctx.refine_at_peaks(opt.atPeaks)
     for i, (infile, outfile) in enumerate(zip(files, outs)):
@@ -728,7 +843,7 @@ def main_many(opt, files, stamp=lambda what: None):
         stamp('file %d of %d' % (i + 1, len(files)))
         if pnames:
             write_profiles(opt, ctx, sel, outfile, sc.test_sites)
-            if opt.nullPerm or opt.locate:
+            if opt.nullPerm or opt.locate or opt.power:
                 ctx.set_profiles(0)
         if opt.peaks is not None:
             peak_files.append((infile, outfile, call_peaks(opt, ctx, sc.test_sites)))
@@ -743,8 +858,21 @@ def main_many(opt, files, stamp=lambda what: None):
             # CLR and counts stay until the genome-wide maxima are known
             null_files.append((outfile, sc.test_sites) + null_of_file(opt, ctx, sc.test_sites, i))
             stamp('file %d of %d: permutation null' % (i + 1, len(files)))
+        if opt.power and opt.nullPerm:
+            power_files.append((i, outfile, data, neut, sel, sc.test_sites))        # its thresholds wait for the last file's null
+        elif opt.power:
+            write_power(opt, ctx, sel, outfile, sc.test_sites, data.genPos, planted, None, say, i)
     if opt.nullPerm:
         finish_null(opt, null_files, null_name(opt.outfile, 'null'), say)
+    if power_files:
+        gmax = np.full(opt.nullPerm, -np.inf)
+        for rec in null_files:
+            gmax = np.maximum(gmax, rec[5])
+        for i, outfile, data, neut, sel, ts in power_files:
+            sel._bound_to = None            # the file's sites (and its model, where it differs) go back into the context
+            sel.bind(neut, reuse=ctx)
+            ctx = sel.ctx
+            write_power(opt, ctx, sel, outfile, ts, data.genPos, planted, gmax, say, i)
     if opt.peaks is not None:
         # (a few arrays per apex were kept per file; the tables wait for the null's p-value files)
         from . import peaks

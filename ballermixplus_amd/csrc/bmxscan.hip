@@ -38,6 +38,7 @@
 
 #include <dlfcn.h>
 #include <errno.h>
+#include <float.h>
 #include <rccl/rccl.h>     // types only: the library is opened with dlopen when a gather is first asked for
 
 #include <algorithm>
@@ -4535,6 +4536,152 @@ __global__ __launch_bounds__(LOCATE_THREADS) void locate_reduce_kernel(const dou
     if (lane == 0) { row_out[k] = best; clr_out[k] = best >= 0 ? bv : 0.0; }
 }
 
+// ----------------------------------------------------------------------------- planted sites (power analysis)
+// bmx_ctx_plant_sites / bmx_ctx_fetch_at (the definition is ballermixplus_amd/power.py).  The composite likelihood is a generative
+// model: a site in reach of a planted locus at c (the scan's own predicate, A |g - c| <= zcut and g != c) redraws its derived count
+// from m_k = max(0, gw[r] (1 + alpha R[ix][ia][r])), r over the rows of its sample size, alpha = exp(-A |g - c|).  The slot that
+// receives the array is then scanned by the unchanged kernels.
+//   plant_range_kernel   per centre (one thread): the run of sites that satisfy A |g - c| <= zcut, by two binary searches with
+//                        the exact predicate (rounding is monotone, so the run is contiguous and the searches are exact)
+//   plant_kernel         workgroups of PLANT_THREADS over (centre, tile of its run), one site per thread: the total of m_k in
+//                        ascending k, then the first k whose running sum exceeds u * total, u from the counter-based hash of the
+//                        site index.  gw and the (ix, ia) slice of R are staged in LDS while 16 * rows bytes fit PLANT_LDS_BYTES
+//                        (lanes of one sample size read one address: a broadcast), and are read through L2 otherwise
+//   plant_hist_kernel    the sites per table row of the finished array, counted as resample_expand_kernel counts them
+// A site belongs to one centre at most (the host refuses centres closer than twice the reach), so no two threads write one row.
+constexpr int PLANT_THREADS = 256;
+constexpr int PLANT_LDS_BYTES = 48 << 10;     // gw + R slice staged in LDS up to 3072 table rows
+constexpr int PLANT_HIST_BLOCKS_MAX = 1024;
+
+__global__ void plant_range_kernel(const double *__restrict__ g, int64_t N, const double *__restrict__ centre, int K, double A,
+                                   double zcut, int32_t *__restrict__ first, int32_t *__restrict__ count) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const double c = centre[k];
+    int64_t a = 0, b = N;                     // the first site that is not (below c and out of reach)
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        const double gm = g[mid];
+        if (gm < c && A * fabs(gm - c) > zcut) a = mid + 1; else b = mid;
+    }
+    const int64_t lo = a;
+    b = N;                                    // the first site from there on that is above c and out of reach
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        const double gm = g[mid];
+        if (gm > c && A * fabs(gm - c) > zcut) b = mid; else a = mid + 1;
+    }
+    first[k] = (int32_t)lo;
+    count[k] = (int32_t)(a - lo);
+}
+
+struct PlantParams {
+    uint64_t key;
+    const double *gen;                        // the positions (source and destination hold the same)
+    const void *src_row;
+    void *dst_row;
+    const double *centre;
+    const int32_t *first, *count;             // [K]
+    int K;
+    double A, zcut;
+    const double *gw, *R;                     // [rows]: the admissible neutral probabilities, the planted pair's slice of the table
+    const int32_t *row_off;                   // [n_sizes + 1]
+    int n_sizes, rows;
+    unsigned long long *changed;
+};
+
+template <class T, bool LDS>
+__global__ __launch_bounds__(PLANT_THREADS) void plant_kernel(PlantParams Q) {
+    extern __shared__ double plant_tab[];     // LDS: gw[rows], then R[rows]
+    if (LDS) {
+        for (int r = threadIdx.x; r < Q.rows; r += PLANT_THREADS) {
+            plant_tab[r] = Q.gw[r];
+            plant_tab[Q.rows + r] = Q.R[r];
+        }
+        __syncthreads();
+    }
+    const double *gw = LDS ? plant_tab : Q.gw;
+    const double *Rs = LDS ? plant_tab + Q.rows : Q.R;
+    const T *__restrict__ src_row = (const T *)Q.src_row;
+    T *__restrict__ dst_row = (T *)Q.dst_row;
+    for (int k = blockIdx.y; k < Q.K; k += gridDim.y) {
+        const int64_t i0 = Q.first[k], n = Q.count[k];
+        const double c = Q.centre[k];
+        for (int64_t o = (int64_t)blockIdx.x * PLANT_THREADS + threadIdx.x; o < n; o += (int64_t)gridDim.x * PLANT_THREADS) {
+            const int64_t i = i0 + o;
+            const double g = Q.gen[i];
+            const double z = Q.A * fabs(g - c);
+            if (!(z <= Q.zcut) || g == c) continue;
+            const int r0 = (int)src_row[i];
+            if (r0 >= Q.rows) continue;       // (never: set_sites checked every row)
+            int ja = 0, jb = Q.n_sizes - 1;   // the size block of the row: the last j with row_off[j] <= r0
+            while (ja < jb) {
+                const int mid = (ja + jb + 1) >> 1;
+                if (Q.row_off[mid] <= r0) ja = mid; else jb = mid - 1;
+            }
+            const int ra = Q.row_off[ja], rb = Q.row_off[ja + 1];
+            const double alpha = exp_neg(z);
+            double total = 0.0;
+            for (int r = ra; r < rb; r++) {
+                double m = gw[r] * (1.0 + alpha * Rs[r]);
+                if (!(m > 0.0) || m > DBL_MAX) m = 0.0;       // negative, NaN and infinite terms count as 0
+                total += m;
+            }
+            if (!(total > 0.0) || total > DBL_MAX) continue;  // nothing to draw from: the row stays
+            const double u = (double)(bmx_mix64(Q.key ^ bmx_mix64((uint64_t)i)) >> 11) * 0x1p-53;
+            const double target = u * total;
+            double cum = 0.0;
+            int pick = -1, last = -1;
+            for (int r = ra; r < rb; r++) {
+                double m = gw[r] * (1.0 + alpha * Rs[r]);
+                if (!(m > 0.0) || m > DBL_MAX) m = 0.0;
+                cum += m;
+                if (m > 0.0) last = r;
+                if (pick < 0 && cum > target) pick = r;
+            }
+            if (pick < 0) pick = last;        // rounding left no k above u * total: the last k with m_k > 0
+            if (pick != r0) {
+                dst_row[i] = (T)pick;
+                atomicAdd(Q.changed, 1ull);
+            }
+        }
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(RS_THREADS) void plant_hist_kernel(const T *__restrict__ row, int64_t N, int32_t *__restrict__ cnt, int rows,
+                                                                int use_hist) {
+    extern __shared__ int plant_hist[];       // [rows] when use_hist
+    if (use_hist) {
+        for (int r = threadIdx.x; r < rows; r += RS_THREADS) plant_hist[r] = 0;
+        __syncthreads();
+    }
+    for (int64_t i = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x; i < N; i += (int64_t)gridDim.x * RS_THREADS) {
+        const int r = (int)row[i];
+        if (r < rows) {
+            if (use_hist) atomicAdd(&plant_hist[r], 1);
+            else atomicAdd(&cnt[r], 1);
+        }
+    }
+    if (use_hist) {
+        __syncthreads();
+        for (int r = threadIdx.x; r < rows; r += RS_THREADS)
+            if (plant_hist[r]) atomicAdd(&cnt[r], plant_hist[r]);
+    }
+}
+
+// bmx_ctx_fetch_at: the scan's results at a list of test sites (-1: the empty result)
+__global__ void fetch_at_kernel(const double *__restrict__ clr, const int32_t *__restrict__ lin, const int32_t *__restrict__ ns,
+                                const int32_t *__restrict__ tests, int64_t n, double *__restrict__ o_clr, int32_t *__restrict__ o_lin,
+                                int32_t *__restrict__ o_ns) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t t = tests[j];
+    o_clr[j] = t < 0 ? 0.0 : clr[t];
+    o_lin[j] = t < 0 ? -1 : lin[t];
+    o_ns[j] = t < 0 ? 0 : ns[t];
+}
+
 // ----------------------------------------------------------------------------- peaks
 // Peak calling on a CLR track (bmx_ctx_peaks / bmx_ctx_peaks_track; the definition is ballermixplus_amd/peaks.py): rows
 // t = 0 .. M-1 with non-decreasing positions g and values c.  Every comparison is an exact FP64 comparison and the only
@@ -5075,6 +5222,13 @@ struct bmx_ctx {
     // resampled sites (bmx_ctx_resample_sites): the tile sums of the weights, their prefix, the copies per table row
     DevBuf<int32_t> rs_tsum, rs_cnt;
     DevBuf<int64_t> rs_tpre;
+    // planted sites (bmx_ctx_plant_sites): the centres and their runs of sites, the admissible neutral probabilities, the number
+    // of changed rows, the events around the device work of the last call; bmx_ctx_fetch_at's list and gathered results
+    DevBuf<double> pw_centre, pw_gw, fa_clr;
+    DevBuf<int32_t> pw_first, pw_count, fa_idx, fa_lin, fa_ns;
+    DevBuf<unsigned long long> pw_changed;
+    hipEvent_t pw_ev0 = nullptr, pw_ev1 = nullptr;
+    double pw_ms = -1.0;
     std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
@@ -5326,8 +5480,12 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->bt_keys.release(); c->bt_pws.release();
     c->pk_tmax.release(); c->pk_track.release(); c->pk_tfirst.release();
     c->rs_tsum.release(); c->rs_cnt.release(); c->rs_tpre.release();
+    c->pw_centre.release(); c->pw_gw.release(); c->pw_first.release(); c->pw_count.release(); c->pw_changed.release();
+    c->fa_idx.release(); c->fa_clr.release(); c->fa_lin.release(); c->fa_ns.release();
     if (c->pk_ev0) (void)hipEventDestroy(c->pk_ev0);
     if (c->pk_ev1) (void)hipEventDestroy(c->pk_ev1);
+    if (c->pw_ev0) (void)hipEventDestroy(c->pw_ev0);
+    if (c->pw_ev1) (void)hipEventDestroy(c->pw_ev1);
     dfree(c->d_prof);
     dfree(c->d_status);
     for (int k = 0; k < 2; k++) {
@@ -6919,6 +7077,163 @@ int bmx_ctx_fetch_locate(bmx_ctx *c, int32_t *row_out, double *clr_out) {
     const size_t n = (size_t)s->lc_K * (size_t)s->lc_R;
     if (row_out) HIP_TRY(hipMemcpy(row_out, s->lc_row.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (clr_out) HIP_TRY(hipMemcpy(clr_out, s->lc_clr.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    return BMX_OK;
+}
+
+/* ---- planted sites: the power analysis (ballermixplus_amd/power.py holds the definition) ---- */
+
+int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, const double *centre, int32_t iA, int32_t ix,
+                        int32_t ia, const double *gw, int32_t *first_out, int32_t *count_out, int64_t *changed_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (!c->has_model) return fail(BMX_E_STATE, "set_model must precede plant_sites");
+    if (src_slot < 0 || src_slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
+    if (src_slot == c->cur_index) return fail(BMX_E_INVALID, "plant_sites: the source slot must not be the selected slot");
+    if (K < 0) return fail(BMX_E_INVALID, "plant_sites: K must be >= 0");
+    if (iA < 0 || iA >= c->nA || ix < 0 || ix >= c->nx || ia < 0 || ia >= c->nab)
+        return fail(BMX_E_INVALID, "plant_sites: the planted grid point lies outside the model's grids");
+    if (K > 0 && (!centre || !gw)) return fail(BMX_E_INVALID, "plant_sites: centre and gw must be given");
+    const double A = c->h_A[(size_t)iA];
+    for (int32_t k = 0; k < K; k++) {
+        if (!(centre[k] - centre[k] == 0.0)) return fail(BMX_E_INVALID, "plant_sites: a centre is not finite");
+        if (k + 1 < K && !(A * (centre[k + 1] - centre[k]) > 2.000001 * c->zcut))
+            return fail(BMX_E_INVALID, "plant_sites: the centres must ascend and lie more than twice the reach apart");
+    }
+    ChromSlot *src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot] : nullptr;
+    if (!src || !src->has_sites) return fail(BMX_E_STATE, "plant_sites: the source slot has no sites");
+    ChromSlot *s = c->cur;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_sites(s);
+    if (changed_out) *changed_out = 0;
+    if (!c->pw_ev0) {
+        HIP_TRY(hipEventCreate(&c->pw_ev0));
+        HIP_TRY(hipEventCreate(&c->pw_ev1));
+    }
+    const int64_t N = src->N;
+    const bool wide = src->wide_rows;
+    const size_t row_bytes = (size_t)N * (wide ? sizeof(uint32_t) : sizeof(uint16_t));
+    HIP_TRY(s->genpos.ensure((size_t)N));
+    if (wide) HIP_TRY(s->row32.ensure((size_t)N));
+    else HIP_TRY(s->row16.ensure((size_t)N));
+    HIP_TRY(c->rs_cnt.ensure((size_t)c->rows));
+    HIP_TRY(c->pw_changed.ensure(1));
+    void *dst_row = wide ? (void *)s->row32.p : (void *)s->row16.p;
+    const void *src_row = wide ? (const void *)src->row32.p : (const void *)src->row16.p;
+    int rc;
+    std::vector<int32_t> first((size_t)K), count((size_t)K);
+    if (K > 0) {
+        if ((rc = upload(c->pw_centre, centre, (size_t)K, c->stream))) return rc;
+        if ((rc = upload(c->pw_gw, gw, (size_t)c->rows, c->stream))) return rc;
+        HIP_TRY(c->pw_first.ensure((size_t)K));
+        HIP_TRY(c->pw_count.ensure((size_t)K));
+    }
+    HIP_TRY(hipEventRecord(c->pw_ev0, c->stream));
+    HIP_TRY(hipMemcpyAsync(s->genpos.p, src->genpos.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst_row, src_row, row_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->pw_changed.p, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(c->rs_cnt.p, 0, (size_t)c->rows * sizeof(int32_t), c->stream));
+    if (K > 0) {
+        hipLaunchKernelGGL(plant_range_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (const double *)src->genpos.p, N,
+                           (const double *)c->pw_centre.p, (int)K, A, c->zcut, c->pw_first.p, c->pw_count.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(first.data(), c->pw_first.p, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(count.data(), c->pw_count.p, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));     // the longest run sizes the grid
+        int64_t longest = 0;
+        for (int32_t k = 0; k < K; k++) {
+            if (first[(size_t)k] < 0 || count[(size_t)k] < 0 || (int64_t)first[(size_t)k] + count[(size_t)k] > N)
+                return fail(BMX_E_HIP, "plant_sites: a run of sites lies outside the array");
+            longest = std::max<int64_t>(longest, count[(size_t)k]);
+        }
+        if (longest > 0) {
+            PlantParams Q;
+            Q.key = key;
+            Q.gen = src->genpos.p;
+            Q.src_row = src_row; Q.dst_row = dst_row;
+            Q.centre = c->pw_centre.p; Q.first = c->pw_first.p; Q.count = c->pw_count.p; Q.K = K;
+            Q.A = A; Q.zcut = c->zcut;
+            Q.gw = c->pw_gw.p;
+            Q.R = c->d_R + ((size_t)ix * c->nab + ia) * (size_t)c->rows;
+            Q.row_off = c->d_row_off; Q.n_sizes = c->n_sizes; Q.rows = c->rows;
+            Q.changed = c->pw_changed.p;
+            const bool in_lds = (size_t)c->rows * 16 <= (size_t)PLANT_LDS_BYTES;
+            const size_t lds = in_lds ? (size_t)c->rows * 16 : 0;
+            const dim3 grid((unsigned)std::min<int64_t>((longest + PLANT_THREADS - 1) / PLANT_THREADS, 65535), (unsigned)std::min<int32_t>(K, 4096));
+            if (wide) {
+                if (in_lds) hipLaunchKernelGGL((plant_kernel<uint32_t, true>), grid, dim3(PLANT_THREADS), lds, c->stream, Q);
+                else hipLaunchKernelGGL((plant_kernel<uint32_t, false>), grid, dim3(PLANT_THREADS), lds, c->stream, Q);
+            } else {
+                if (in_lds) hipLaunchKernelGGL((plant_kernel<uint16_t, true>), grid, dim3(PLANT_THREADS), lds, c->stream, Q);
+                else hipLaunchKernelGGL((plant_kernel<uint16_t, false>), grid, dim3(PLANT_THREADS), lds, c->stream, Q);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    {   // the sites per table row of the finished array
+        const int use_hist = c->rows <= RS_HIST_MAX ? 1 : 0;
+        const size_t lds = use_hist ? (size_t)c->rows * sizeof(int) : 0;
+        const unsigned blocks = (unsigned)std::min<int64_t>((N + RS_THREADS - 1) / RS_THREADS, PLANT_HIST_BLOCKS_MAX);
+        if (wide) hipLaunchKernelGGL(plant_hist_kernel<uint32_t>, dim3(blocks), dim3(RS_THREADS), lds, c->stream, (const uint32_t *)s->row32.p, N,
+                                     c->rs_cnt.p, c->rows, use_hist);
+        else hipLaunchKernelGGL(plant_hist_kernel<uint16_t>, dim3(blocks), dim3(RS_THREADS), lds, c->stream, (const uint16_t *)s->row16.p, N,
+                                c->rs_cnt.p, c->rows, use_hist);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->pw_ev1, c->stream));
+    std::vector<int32_t> cnt32((size_t)c->rows);
+    double ends[2] = {0.0, 0.0};
+    unsigned long long changed = 0;
+    HIP_TRY(hipMemcpyAsync(cnt32.data(), c->rs_cnt.p, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[0], s->genpos.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[1], s->genpos.p + (N - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&changed, c->pw_changed.p, sizeof(changed), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
+    c->pw_ms = (double)ms;
+    std::vector<int64_t> cnt(cnt32.begin(), cnt32.end());
+    s->wide_rows = wide;
+    if ((rc = derive_row_tables(c, s, cnt, N, ends[0], ends[1]))) return rc;
+    s->N = N;
+    s->has_sites = true;
+    for (int32_t k = 0; k < K; k++) {
+        if (first_out) first_out[k] = first[(size_t)k];
+        if (count_out) count_out[k] = count[(size_t)k];
+    }
+    if (changed_out) *changed_out = (int64_t)changed;
+    return BMX_OK;
+}
+
+int bmx_ctx_plant_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "null argument");
+    if (c->pw_ms < 0.0) return fail(BMX_E_STATE, "no plant_sites call yet");
+    *ms = c->pw_ms;
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_at(bmx_ctx *c, int64_t n, const int32_t *tests, double *clr, int32_t *lin, int32_t *nsites) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "fetch_at needs a scan: call bmx_ctx_scan first");
+    if (n < 0 || (n > 0 && !tests)) return fail(BMX_E_INVALID, "fetch_at: a list of test sites must be given");
+    if (n > 0x7fffff00LL) return fail(BMX_E_LIMIT, "fetch_at: more than 2^31 indices");
+    for (int64_t j = 0; j < n; j++)
+        if (tests[j] < -1 || (int64_t)tests[j] >= s->M) return fail(BMX_E_INVALID, "fetch_at: a test site index outside [0, M) (or -1)");
+    if (n == 0) return BMX_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = upload(c->fa_idx, tests, (size_t)n, c->stream))) return rc;
+    HIP_TRY(c->fa_clr.ensure((size_t)n));
+    HIP_TRY(c->fa_lin.ensure((size_t)n));
+    HIP_TRY(c->fa_ns.ensure((size_t)n));
+    hipLaunchKernelGGL(fetch_at_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double *)s->clr.p,
+                       (const int32_t *)s->lin.p, (const int32_t *)s->nsites.p, (const int32_t *)c->fa_idx.p, n, c->fa_clr.p, c->fa_lin.p,
+                       c->fa_ns.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (clr) HIP_TRY(hipMemcpy(clr, c->fa_clr.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (lin) HIP_TRY(hipMemcpy(lin, c->fa_lin.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nsites) HIP_TRY(hipMemcpy(nsites, c->fa_ns.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BMX_OK;
 }
 

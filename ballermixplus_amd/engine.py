@@ -391,6 +391,40 @@ class Context:
         _lib.check(self._L.bmx_ctx_fetch_locate(self._h, _lib.as_ip(row), _lib.as_dp(clr)))
         return row, clr
 
+    def plant_sites(self, src_slot, key, centres, iA, ix, ia, gw):
+        """The selected slot receives slot src_slot's positions and current rows with the sites in reach of `centres` redrawn
+        from the mixture at grid point (iA, ix, ia) under `key` (ballermixplus_amd/power.py: planted_rows), built on the device;
+        the slot is then as after set_sites of those arrays.  gw: power.allowed_rows' weights, one per table row.  Returns
+        (first i32[K], count i32[K]: every centre's run of sites with A |g - c| <= alpha_cut; sites whose row changed)."""
+        c = _lib.f64(centres)
+        w = _lib.f64(gw)
+        if c.ndim != 1 or w.shape != (self.model.rows,):
+            raise ValueError('a flat list of centres and one weight per table row are needed')
+        first, count = np.zeros(len(c), dtype=np.int32), np.zeros(len(c), dtype=np.int32)
+        changed = C.c_int64()
+        self.M = 0
+        self._slot_M.pop(self.slot, None)
+        _lib.check(self._L.bmx_ctx_plant_sites(self._h, int(src_slot), C.c_uint64(int(key) & ((1 << 64) - 1)), len(c), _lib.as_dp(c),
+                                               int(iA), int(ix), int(ia), _lib.as_dp(w), _lib.as_ip(first), _lib.as_ip(count),
+                                               C.byref(changed)))
+        return first, count, changed.value
+
+    def plant_ms(self):
+        """Device milliseconds of the context's last plant_sites() call."""
+        ms = C.c_double()
+        _lib.check(self._L.bmx_ctx_plant_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def fetch_at(self, tests):
+        """(clr f64[n], lin i32[n], nsites i32[n]) of the selected slot's last scan at the listed test sites (any order, repeats
+        allowed); -1 gives (0, -1, 0).  lin: the linear grid index (iA * nx + ix) * nab + ia, -1 without a grid result."""
+        t = _lib.i32(tests)
+        if t.ndim != 1:
+            raise ValueError('a flat list of test site indices is needed')
+        clr, lin, ns = np.empty(len(t), dtype=np.float64), np.empty(len(t), dtype=np.int32), np.empty(len(t), dtype=np.int32)
+        _lib.check(self._L.bmx_ctx_fetch_at(self._h, len(t), _lib.as_ip(t), _lib.as_dp(clr), _lib.as_ip(lin), _lib.as_ip(ns)))
+        return clr, lin, ns
+
     def peaks(self, sep, min_clr=0.0, frac=0.5):
         """Call peaks (ballermixplus_amd/peaks.py) on the selected slot's last scan: separation sep in the units of the test
         positions, floor min_clr, extent fraction frac.  Returns fetch_peaks()."""

@@ -364,6 +364,36 @@ int bmx_ctx_locate_begin(bmx_ctx *c, int32_t K, const int32_t *lo, const int32_t
 int bmx_ctx_locate_accumulate(bmx_ctx *c, int32_t r);
 int bmx_ctx_fetch_locate(bmx_ctx *c, int32_t *row_out, double *clr_out);
 
+/* ---- planted sites: the power analysis (opt-in; the CLI's --power; ballermixplus_amd/power.py holds the definition) -------
+ * The composite likelihood is a generative model.  A site i in reach of a planted locus at position c -- the scan's own
+ * predicate A |g_i - c| <= bmx_alpha_cut() and its exclusion g_i != c -- redraws its derived count from the mixture the scan
+ * fits at ONE grid point (iA, ix, ia) of the model:
+ *     m_k = max(0, gw[r] * (1 + alpha_i * R[ix][ia][r])),  r = row_off[j] + k over the rows of the site's sample size j,
+ *     alpha_i = exp(-A |g_i - c|);  a non-finite m_k counts as 0;  total = sum_k m_k in ascending k;
+ *     u_i = (mix(key ^ mix(i)) >> 11) * 2^-53  (splitmix64, i the site's index);
+ *     the new row is the first k whose running sum exceeds u_i * total (the last k with m_k > 0 if rounding leaves none);
+ *     total not finite or not > 0: the row stays.
+ * gw[rows] is the caller's: the neutral probability of every admissible (count, sample size), 0 elsewhere.  Positions and sample
+ * sizes never change.  The array is then scanned by the unchanged kernels.  These entry points arrived without a bump of
+ * BMX_ABI_VERSION_MINOR, as the groups above did: look the symbols up to find out whether a binary has them. */
+/* The SELECTED slot receives src_slot's positions and the rows src_slot holds now (a permutation by bmx_ctx_permute_rows
+ * included), with the sites in reach of centre[0 .. K) redrawn under key.  Afterwards the selected slot is in exactly the state
+ * bmx_ctx_set_sites leaves for those arrays (its test sites are discarded); src_slot is read only.  first_out[k] / count_out[k]
+ * (may be NULL): the run of sites with A |g_i - c_k| <= bmx_alpha_cut() (it holds the sites AT c_k, which are not redrawn);
+ * *changed_out (may be NULL): the sites whose row changed.  K == 0 succeeds and copies the source.  src_slot == the selected
+ * slot, indices outside the grids or the slots, K < 0, a centre that is not finite, centres that do not ascend with
+ * A (c[k+1] - c[k]) > 2.000001 bmx_alpha_cut() (no site is in reach of two), and a NULL gw or centre with K > 0 are
+ * BMX_E_INVALID; no model, or a source without sites, is BMX_E_STATE.  Blocks. */
+int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, const double *centre, int32_t iA, int32_t ix,
+                        int32_t ia, const double *gw /* [rows] */, int32_t *first_out, int32_t *count_out /* [K], may be NULL */,
+                        int64_t *changed_out /* may be NULL */);
+/* Milliseconds the last bmx_ctx_plant_sites spent on the device, the two copies of the arrays included (HIP events). */
+int bmx_ctx_plant_ms(bmx_ctx *c, double *ms);
+/* The selected slot's last scan results at tests[n] (indices into its M test sites, any order, repeats allowed), gathered on
+ * the device: clr, lin (linear grid index, -1: none) and nsites, any of which may be NULL.  An index of -1 gives (0, -1, 0);
+ * other indices outside [0, M) are BMX_E_INVALID; before a scan the call is BMX_E_STATE; n == 0 succeeds.  Blocks. */
+int bmx_ctx_fetch_at(bmx_ctx *c, int64_t n, const int32_t *tests, double *clr, int32_t *lin, int32_t *nsites);
+
 /* ---- peaks of the CLR track (opt-in; the CLI's --peaks; ballermixplus_amd/peaks.py holds the definition) ------------------
  * The track: rows t = 0 .. M-1 with non-decreasing positions g and values c.  Row t is an APEX iff c_t > 0, c_t >= min_clr and no
  * other row s with g_t - g_s <= sep and g_s - g_t <= sep has c_s > c_t, or c_s == c_t and s < t (a local-maximum rule, not greedy
