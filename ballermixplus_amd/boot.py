@@ -62,6 +62,20 @@ THR = (
 LEVEL = 0.95
 
 
+def value_refusal(R, block=None, level=None, min_clr=None):
+    """The message that refuses these values of --boot / --bootBlock / --bootLevel / --bootMin (None: the flag was not given),
+    or None."""
+    if R < 2:
+        return '--boot takes a number of replicates >= 2 (0: off).'
+    if block is not None and block < 1:
+        return '--bootBlock must be >= 1.'
+    if level is not None and not (0.0 < level < 1.0):
+        return '--bootLevel takes a number L with 0 < L < 1.'
+    if min_clr is not None and min_clr != min_clr:
+        return '--bootMin takes a number.'
+    return None
+
+
 def replicate_key(seed, r, f=0):
     """The key of replicate r of input file f (file ordinal 0 for a single file)."""
     return null.replicate_key(null.mix((int(seed) & _M64) ^ SEED_DOMAIN), r, f)

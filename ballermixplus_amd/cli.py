@@ -57,11 +57,14 @@ Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N -m b
 test sites are sharded over the ranks (rank r computes on GPU LOCAL_RANK), rank 0 gathers the 16-byte records
 (one RCCL gather) and writes the output file.  BMX_DIST_BACKEND=gloo BMX_SINGLE_DEVICE=1 lets several ranks
 share GPU 0 with a CPU gather: a rehearsal of the multi-rank control flow on a 1-GPU box.
+
+Structure: main() asks every addition's <feature>_refusal(opt) before anything is read.  main() (one file) and main_many()
+(several) bring a file to its Scan in their own ways; after it both call file_stages() per file and wrap_up() once.
 """
 import argparse
-import math
 import os
 import sys
+from collections import namedtuple
 from datetime import datetime
 
 import numpy as np
@@ -242,34 +245,65 @@ def build_parser():
     return parser
 
 
-def power_refusal(opt):
-    """The message that refuses a --power / --plant* / --power* command line, or None when it can run (or the power analysis
-    is off).  Whether --plant names grid values is asked once the grids are known."""
-    for flag, v in (('--plant', opt.plant), ('--plantEvery', opt.plantEvery), ('--powerSpan', opt.powerSpan),
-                    ('--powerSeed', opt.powerSeed), ('--powerBackground', opt.powerBackground), ('--powerBlock', opt.powerBlock),
-                    ('--powerThreshold', opt.powerThreshold), ('--powerReps', opt.powerReps or None)):
-        if v is not None and not opt.power:
-            return '%s needs --power.' % flag
-    if not opt.power:
-        return None
-    from . import power
-    refused = power.value_refusal(opt.power, opt.plantEvery, opt.powerSpan, opt.powerBlock, opt.powerBackground, opt.powerThreshold)
-    if refused:
-        return refused
-    if opt.plant is None:
-        return '--power needs --plant A,x,abeta: the grid point whose mixture the sites are drawn from.'
-    if opt.powerThreshold is None and not opt.nullPerm:
-        return '--power needs --powerThreshold C[,C...] or --nullPerm (whose genome-wide thresholds it then uses).'
-    if opt.getSpec or opt.getConfig:
-        return '--power scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if opt.w != 0 or opt.size:
-        return ('--power needs the default window mode (no -w, no --fixWinSize): the replicates are scanned with every window '
-                'holding all sites.')
-    if not opt.outfile:
-        return '--power needs -o: the power file is written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--power runs in a single process; multi-rank launches are not supported.'
+# ------------------------------------------------------------------------------------------------------------ refusals
+# Every <feature>_refusal(opt) returns the message that refuses the command line in that feature's name, or None when the
+# feature can run or is off.  Each is the list of its checks in the order they are asked, built from the five checks below and
+# the feature's own; the values of its flags are judged by <feature module>.value_refusal.  main() asks the features in a fixed
+# order and prints the first message (tests/test_cli_refusals_cpu.py holds every message and the precedence).
+
+def given(v, default):
+    """The value of a flag whose parser default is None (not given), or the default."""
+    return v if v is not None else default
+
+
+def when(fault, message):
+    return message if fault else None
+
+
+def orphan(opt, feature, dests):
+    """A flag of `feature` (by destination, which is its name) that was given although the feature is off."""
+    for d in dests:
+        if getattr(opt, d) is not None and getattr(opt, d) is not False:
+            return '--%s needs %s.' % (d, feature)
     return None
+
+
+def helper_mode(opt, feature):
+    return when(opt.getSpec or opt.getConfig, '%s scans the input; it cannot be combined with --getSpect / --getConfig.' % feature)
+
+
+def no_output(opt, feature, files):
+    return when(not opt.outfile, '%s needs -o: the %s written next to the output.' % (feature, files))
+
+
+def multi_rank(feature):
+    return when(int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1',
+                '%s runs in a single process; multi-rank launches are not supported.' % feature)
+
+
+def window_mode(opt, feature, why):
+    return when(opt.w != 0 or opt.size, '%s needs the default window mode (no -w, no --fixWinSize): %s' % (feature, why))
+
+
+def power_refusal(opt):
+    """--power / --plant* / --power*.  Whether --plant names grid values is asked once the grids are known (planted_point)."""
+    if not opt.power:
+        return orphan(opt, '--power', ('plant', 'plantEvery', 'powerSpan', 'powerSeed', 'powerBackground', 'powerBlock',
+                                       'powerThreshold', 'powerReps'))
+    from . import power
+    return (power.value_refusal(opt.power, opt.plantEvery, opt.powerSpan, opt.powerBlock, opt.powerBackground, opt.powerThreshold)
+            or when(opt.plant is None, '--power needs --plant A,x,abeta: the grid point whose mixture the sites are drawn from.')
+            or when(opt.powerThreshold is None and not opt.nullPerm,
+                    '--power needs --powerThreshold C[,C...] or --nullPerm (whose genome-wide thresholds it then uses).')
+            or helper_mode(opt, '--power')
+            or window_mode(opt, '--power', 'the replicates are scanned with every window holding all sites.')
+            or no_output(opt, '--power', 'power file is')
+            or multi_rank('--power'))
+
+
+def power_span(opt):
+    """--powerSpan, else --peaks' G, else None (power.py then takes the reach of the planted A)."""
+    return given(opt.powerSpan, opt.peaks)
 
 
 def planted_point(opt, grid):
@@ -283,7 +317,7 @@ def planted_point(opt, grid):
         sys.exit(1)
     if opt.plantEvery is not None:      # refused before anything is scanned
         A_plant = float(As[planted[0]])
-        H = opt.powerSpan if opt.powerSpan is not None else opt.peaks if opt.peaks is not None else power.ALPHA_CUT / A_plant
+        H = given(power_span(opt), power.ALPHA_CUT / A_plant)
         bound = power.bound_of(H, float(min(As)), A_plant)
         if opt.plantEvery < bound:
             print(power.spacing_refusal(opt.plantEvery, bound))
@@ -303,11 +337,9 @@ def write_power(opt, ctx, sel, outfile, ts, genpos, planted, null_maxima, say, f
     line_of_row = np.asarray(ts.order, dtype=np.int64) + 1 if ts.na_rows else None
     try:
         n, mean = power.power_and_write(ctx, outfile, ts, genpos, sel.model, sel.grid_A, planted, thr, opt.power,
-                                        opt.powerSeed if opt.powerSeed is not None else 1, opt.powerBackground or 'perm',
-                                        opt.powerBlock if opt.powerBlock is not None else 1,
-                                        opt.powerSpan if opt.powerSpan is not None else opt.peaks, opt.plantEvery, f, opt.powerReps,
-                                        line_of_row, ([f'{v}' for v in sel.grid_x], [f'{v}' for v in sel.grid_abeta],
-                                                      [f'{v}' for v in sel.grid_A]))
+                                        given(opt.powerSeed, 1), opt.powerBackground or 'perm', given(opt.powerBlock, 1),
+                                        power_span(opt), opt.plantEvery, f, opt.powerReps, line_of_row,
+                                        ([f'{v}' for v in sel.grid_x], [f'{v}' for v in sel.grid_abeta], [f'{v}' for v in sel.grid_A]))
     except ValueError as e:
         print(e)
         sys.exit(1)
@@ -316,40 +348,25 @@ def write_power(opt, ctx, sel, outfile, ts, genpos, planted, null_maxima, say, f
 
 
 def locate_refusal(opt):
-    """The message that refuses a --locate / --locate* command line, or None when it can run (or the position bootstrap is
-    off).  Asked before every other refusal, so that a command line with --locate is refused in --locate's name."""
-    for flag, v in (('--locateSeed', opt.locateSeed), ('--locateBlock', opt.locateBlock), ('--locateSpan', opt.locateSpan),
-                    ('--locateLevel', opt.locateLevel), ('--locateMin', opt.locateMin), ('--locateReps', opt.locateReps or None)):
-        if v is not None and not opt.locate:
-            return '%s needs --locate.' % flag
+    """--locate / --locate*.  Asked before the other features' refusals, so that a command line with --locate is refused in
+    --locate's name."""
     if not opt.locate:
-        return None
+        return orphan(opt, '--locate', ('locateSeed', 'locateBlock', 'locateSpan', 'locateLevel', 'locateMin', 'locateReps'))
     from . import locate
-    refused = locate.value_refusal(opt.locate, opt.locateBlock, opt.locateSpan, opt.locateLevel, opt.locateMin)
-    if refused:
-        return refused
-    if opt.getSpec or opt.getConfig:
-        return '--locate scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if opt.peaks is None:
-        return '--locate needs --peaks G: the intervals are drawn around the apexes of the peak call.'
-    if opt.w != 0 or opt.size:
-        return ('--locate needs the default window mode (no -w, no --fixWinSize): windows that count sites or nucleotides are '
-                'not defined on a resampled site array.')
-    if not opt.outfile:
-        return '--locate needs -o: the locate file is written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--locate runs in a single process; multi-rank launches are not supported.'
-    return None
+    return (locate.value_refusal(opt.locate, opt.locateBlock, opt.locateSpan, opt.locateLevel, opt.locateMin)
+            or helper_mode(opt, '--locate')
+            or when(opt.peaks is None, '--locate needs --peaks G: the intervals are drawn around the apexes of the peak call.')
+            or window_mode(opt, '--locate', 'windows that count sites or nucleotides are not defined on a resampled site array.')
+            or no_output(opt, '--locate', 'locate file is')
+            or multi_rank('--locate'))
 
 
 def write_locate(opt, ctx, outfile, ts, called, say, f=0):
     """<outfile>.locate.txt (with --locateReps <outfile>.locate.reps.txt) of one file (input-file ordinal f) whose observed scan
     and peak call (`called`) have just run on ctx's selected slot."""
     from . import locate
-    n, empty = locate.locate_and_write(ctx, outfile, ts, called, opt.locate, opt.locateSeed if opt.locateSeed is not None else 1,
-                                       opt.locateBlock if opt.locateBlock is not None else 1,
-                                       opt.locateSpan if opt.locateSpan is not None else opt.peaks,
-                                       opt.locateLevel if opt.locateLevel is not None else locate.LEVEL, opt.locateMin, f,
+    n, empty = locate.locate_and_write(ctx, outfile, ts, called, opt.locate, given(opt.locateSeed, 1), given(opt.locateBlock, 1),
+                                       given(opt.locateSpan, opt.peaks), given(opt.locateLevel, locate.LEVEL), opt.locateMin, f,
                                        opt.locateReps)
     say(f'\n{datetime.now()}. Position bootstrap: {n} peak/s, {opt.locate} replicates -> {locate.output_name(outfile)}')
     if empty:
@@ -357,35 +374,24 @@ def write_locate(opt, ctx, outfile, ts, called, say, f=0):
 
 
 def surfaces_refusal(opt):
-    """The message that refuses a --surfaces / --surfaceMin / --surfaceMax command line, or None when it can run (or surfaces
-    are off)."""
-    for flag, v in (('--surfaceMin', opt.surfaceMin), ('--surfaceMax', opt.surfaceMax)):
-        if v is not None and not opt.surfaces:
-            return '%s needs --surfaces.' % flag
+    """--surfaces / --surfaceMin / --surfaceMax."""
     if not opt.surfaces:
-        return None
+        return orphan(opt, '--surfaces', ('surfaceMin', 'surfaceMax'))
     from . import surfaces
-    refused = surfaces.value_refusal(opt.surfaceMin, opt.surfaceMax)
-    if refused:
-        return refused
-    if opt.peaks is None and opt.surfaceMin is None:
-        return ('--surfaces needs --peaks G (the surfaces of the apexes) or --surfaceMin C (of the windows with CLR >= C): '
-                'the surface of every window of a chromosome is never what is meant.')
-    if opt.getSpec or opt.getConfig:
-        return '--surfaces scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if not opt.outfile:
-        return '--surfaces needs -o: the surfaces file is written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--surfaces runs in a single process; multi-rank launches are not supported.'
-    return None
+    return (surfaces.value_refusal(opt.surfaceMin, opt.surfaceMax)
+            or when(opt.peaks is None and opt.surfaceMin is None,
+                    '--surfaces needs --peaks G (the surfaces of the apexes) or --surfaceMin C (of the windows with CLR >= C): '
+                    'the surface of every window of a chromosome is never what is meant.')
+            or helper_mode(opt, '--surfaces')
+            or no_output(opt, '--surfaces', 'surfaces file is')
+            or multi_rank('--surfaces'))
 
 
 def write_surfaces(opt, ctx, sel, outfile, ts, called, say):
     """<outfile>.surfaces.txt of one file whose observed scan (and peak call: `called`, or None without --peaks) has just run
     on ctx's selected slot."""
     from . import surfaces
-    n, dropped = surfaces.surfaces_and_write(ctx, outfile, ts, sel, opt.surfaceMin if opt.surfaceMin is not None else 0.0,
-                                             opt.surfaceMax if opt.surfaceMax is not None else surfaces.MAX_WINDOWS,
+    n, dropped = surfaces.surfaces_and_write(ctx, outfile, ts, sel, given(opt.surfaceMin, 0.0), given(opt.surfaceMax, surfaces.MAX_WINDOWS),
                                              called[0]['row'] if called is not None else None)
     say(f'\n{datetime.now()}. Surfaces: {n} window/s -> {surfaces.output_name(outfile)}')
     if dropped:
@@ -393,26 +399,16 @@ def write_surfaces(opt, ctx, sel, outfile, ts, called, say):
 
 
 def peaks_refusal(opt):
-    """The message that refuses a --peaks / --peakMin / --peakExtent / --atPeaks command line, or None when it can run (or peak
-    calling is off).  Asked before the other refusals, so that a command line with --peaks is refused in this feature's name."""
-    for flag, v in (('--peakMin', opt.peakMin), ('--peakExtent', opt.peakExtent), ('--atPeaks', opt.atPeaks or None)):
-        if v is not None and opt.peaks is None:
-            return '%s needs --peaks.' % flag
+    """--peaks / --peakMin / --peakExtent / --atPeaks.  Asked before the refusals of the features that do not need the peaks,
+    so that a command line with --peaks is refused in this feature's name."""
     if opt.peaks is None:
-        return None
+        return orphan(opt, '--peaks', ('peakMin', 'peakExtent', 'atPeaks'))
     from . import peaks
-    refused = peaks.value_refusal(opt.peaks, opt.peakMin, opt.peakExtent)
-    if refused:
-        return refused
-    if opt.getSpec or opt.getConfig:
-        return '--peaks scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if not opt.outfile:
-        return '--peaks needs -o: the peak file is written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--peaks runs in a single process; multi-rank launches are not supported.'
-    if opt.atPeaks and not opt.refine:
-        return '--atPeaks needs --refine: it restricts the refinement to the apexes.'
-    return None
+    return (peaks.value_refusal(opt.peaks, opt.peakMin, opt.peakExtent)
+            or helper_mode(opt, '--peaks')
+            or no_output(opt, '--peaks', 'peak file is')
+            or multi_rank('--peaks')
+            or when(opt.atPeaks and not opt.refine, '--atPeaks needs --refine: it restricts the refinement to the apexes.'))
 
 
 def call_peaks(opt, ctx, ts):
@@ -421,8 +417,7 @@ def call_peaks(opt, ctx, ts):
     from . import peaks
     if len(ts) == 0:
         return peaks.empty(), None
-    pk = ctx.peaks(opt.peaks, opt.peakMin if opt.peakMin is not None else 0.0,
-                   opt.peakExtent if opt.peakExtent is not None else peaks.FRAC)
+    pk = ctx.peaks(opt.peaks, given(opt.peakMin, 0.0), given(opt.peakExtent, peaks.FRAC))
     return pk, (np.asarray(ts.order, dtype=np.int64) + 1 if ts.na_rows else None)
 
 
@@ -434,87 +429,55 @@ def write_peaks(outfile, called, with_null):
 
 
 def refine_refusal(opt):
-    """The message that refuses a --refine / --refineMin command line, or None when it can run (or refinement is off)."""
-    if opt.refineMin is not None and not opt.refine:
-        return '--refineMin needs --refine.'
+    """--refine / --refineMin."""
     if not opt.refine:
-        return None
-    if opt.refineMin is not None and opt.refineMin != opt.refineMin:
-        return '--refineMin takes a number.'
-    if opt.getSpec or opt.getConfig:
-        return '--refine scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if not opt.outfile:
-        return '--refine needs -o: the refined file is written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--refine runs in a single process; multi-rank launches are not supported.'
-    return None
+        return orphan(opt, '--refine', ('refineMin',))
+    return (when(opt.refineMin is not None and opt.refineMin != opt.refineMin, '--refineMin takes a number.')
+            or helper_mode(opt, '--refine')
+            or no_output(opt, '--refine', 'refined file is')
+            or multi_rank('--refine'))
 
 
 def write_refined(opt, ctx, outfile, ts, f=0):
     """<outfile>.refined.txt (with --support <outfile>.support.txt, with --boot <outfile>.boot.txt) of one file (input-file
     ordinal f) whose observed scan has just run on ctx's selected slot."""
     from . import refine
-    refine.refine_and_write(ctx, outfile, ts, opt.refineMin if opt.refineMin is not None else 0.0)
+    min_clr = given(opt.refineMin, 0.0)         # --supportMin and --bootMin fall back to it
+    refine.refine_and_write(ctx, outfile, ts, min_clr)
     if opt.support:
         from . import support
-        drop = opt.supportDrop if opt.supportDrop is not None else support.DROP
-        min_clr = opt.supportMin if opt.supportMin is not None else opt.refineMin if opt.refineMin is not None else 0.0
-        support.support_and_write(ctx, outfile, ts, drop, min_clr)
+        support.support_and_write(ctx, outfile, ts, given(opt.supportDrop, support.DROP), given(opt.supportMin, min_clr))
     if opt.boot:
         from . import boot
-        min_clr = opt.bootMin if opt.bootMin is not None else opt.refineMin if opt.refineMin is not None else 0.0
-        boot.boot_and_write(ctx, outfile, ts, opt.boot, opt.bootSeed if opt.bootSeed is not None else 1,
-                            opt.bootBlock if opt.bootBlock is not None else 1,
-                            opt.bootLevel if opt.bootLevel is not None else boot.LEVEL, min_clr, f, opt.bootReps)
+        boot.boot_and_write(ctx, outfile, ts, opt.boot, given(opt.bootSeed, 1), given(opt.bootBlock, 1), given(opt.bootLevel, boot.LEVEL),
+                            given(opt.bootMin, min_clr), f, opt.bootReps)
 
 
 def boot_refusal(opt):
-    """The message that refuses a --boot / --boot* command line, or None when it can run (or the bootstrap is off).  Asked
-    before refine_refusal, so that a command line with --boot is refused in --boot's name."""
-    for flag, v in (('--bootSeed', opt.bootSeed), ('--bootBlock', opt.bootBlock), ('--bootLevel', opt.bootLevel),
-                    ('--bootMin', opt.bootMin), ('--bootReps', opt.bootReps or None)):
-        if v is not None and not opt.boot:
-            return '%s needs --boot.' % flag
+    """--boot / --boot*.  Asked before refine_refusal, so that a command line with --boot is refused in --boot's name; the
+    number of replicates is judged first, the values of the other flags last."""
     if not opt.boot:
-        return None
-    if opt.boot < 2:
-        return '--boot takes a number of replicates >= 2 (0: off).'
-    if opt.getSpec or opt.getConfig:
-        return '--boot scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if not opt.refine:
-        return '--boot needs --refine: the replicates start at the refined maxima.'
-    if not opt.outfile:
-        return '--boot needs -o: the bootstrap file is written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--boot runs in a single process; multi-rank launches are not supported.'
-    if opt.bootBlock is not None and opt.bootBlock < 1:
-        return '--bootBlock must be >= 1.'
-    if opt.bootLevel is not None and not (0.0 < opt.bootLevel < 1.0):
-        return '--bootLevel takes a number L with 0 < L < 1.'
-    if opt.bootMin is not None and opt.bootMin != opt.bootMin:
-        return '--bootMin takes a number.'
-    return None
+        return orphan(opt, '--boot', ('bootSeed', 'bootBlock', 'bootLevel', 'bootMin', 'bootReps'))
+    from . import boot
+    return (boot.value_refusal(opt.boot)
+            or helper_mode(opt, '--boot')
+            or when(not opt.refine, '--boot needs --refine: the replicates start at the refined maxima.')
+            or no_output(opt, '--boot', 'bootstrap file is')
+            or multi_rank('--boot')
+            or boot.value_refusal(opt.boot, opt.bootBlock, opt.bootLevel, opt.bootMin))
 
 
 def support_refusal(opt):
-    """The message that refuses a --support / --supportDrop / --supportMin command line, or None when it can run (or support
-    intervals are off).  --refine's own refusals come first (refine_refusal)."""
-    for flag, v in (('--supportDrop', opt.supportDrop), ('--supportMin', opt.supportMin)):
-        if v is not None and not opt.support:
-            return '%s needs --support.' % flag
+    """--support / --supportDrop / --supportMin.  --refine's own refusals come first (refine_refusal)."""
     if not opt.support:
-        return None
-    if not opt.refine:
-        return '--support needs --refine: the intervals are drawn around the refined maxima.'
-    if opt.supportDrop is not None and not (math.isfinite(opt.supportDrop) and opt.supportDrop > 0):
-        return '--supportDrop takes a finite number > 0.'
-    if opt.supportMin is not None and opt.supportMin != opt.supportMin:
-        return '--supportMin takes a number.'
-    return None
+        return orphan(opt, '--support', ('supportDrop', 'supportMin'))
+    from . import support
+    return (when(not opt.refine, '--support needs --refine: the intervals are drawn around the refined maxima.')
+            or support.value_refusal(opt.supportDrop, opt.supportMin))
 
 
 def profiles_refusal(opt):
-    """The message that refuses a --profiles command line, or None when it can run (or profiles are off)."""
+    """--profiles."""
     if opt.profiles is None:
         return None
     from . import profiles
@@ -522,13 +485,7 @@ def profiles_refusal(opt):
         profiles.parse(opt.profiles)
     except ValueError as e:
         return str(e)
-    if opt.getSpec or opt.getConfig:
-        return '--profiles scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if not opt.outfile:
-        return '--profiles needs -o: the profile files are written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--profiles runs in a single process; multi-rank launches are not supported.'
-    return None
+    return helper_mode(opt, '--profiles') or no_output(opt, '--profiles', 'profile files are') or multi_rank('--profiles')
 
 
 def profile_names(opt):
@@ -544,41 +501,19 @@ def write_profiles(opt, ctx, sel, outfile, ts):
 
 
 def null_refusal(opt):
-    """The message that refuses a --nullPerm command line, or None when it can run."""
+    """--nullPerm / --nullBlock."""
     if not opt.nullPerm:
         return None
-    if opt.nullPerm < 0:
-        return '--nullPerm takes a number of replicates >= 1 (0: off).'
-    if opt.nullBlock < 1:
-        return '--nullBlock must be >= 1.'
-    if opt.getSpec or opt.getConfig:
-        return '--nullPerm scans the input; it cannot be combined with --getSpect / --getConfig.'
-    if not opt.outfile:
-        return '--nullPerm needs -o: the null and p-value files are written next to the output.'
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 or os.environ.get('BMX_FORCE_DIST') == '1':
-        return '--nullPerm runs in a single process; multi-rank launches are not supported.'
-    return None
+    return (when(opt.nullPerm < 0, '--nullPerm takes a number of replicates >= 1 (0: off).')
+            or when(opt.nullBlock < 1, '--nullBlock must be >= 1.')
+            or helper_mode(opt, '--nullPerm')
+            or no_output(opt, '--nullPerm', 'null and p-value files are')
+            or multi_rank('--nullPerm'))
 
 
 def null_name(outspec, what):
     """<out>.null.txt of a one-file run; for several files <dir>/null.txt, or the -o pattern with `null` for {}."""
     return outspec.replace('{}', what) if '{}' in outspec else os.path.join(outspec, what + '.txt')
-
-
-def finish_null(opt, per_file, null_path, say):
-    """per_file: (outfile, test sites, observed clr, iA, counts, maxima[R]) of every file.  The genome-wide maximum of a
-    replicate is the maximum over the files; writes the null file and one p-value file per output file."""
-    from . import null
-    R = opt.nullPerm
-    gmax = np.full(R, -np.inf)
-    for rec in per_file:
-        gmax = np.maximum(gmax, rec[5])
-    null.write_null(null_path, gmax)
-    for outfile, ts, clr, iA, counts, _ in per_file:
-        null.write_pval(outfile + '.pval.txt', ts, clr, iA, counts, gmax)
-    say(f'\n{datetime.now()}. Permutation null: {R} replicates (seed {opt.nullSeed}, blocks of {opt.nullBlock} site/s) -> {null_path}')
-    say('Genome-wide CLR threshold, 5%% level: %r' % null.threshold(gmax, 0.95))
-    say('Genome-wide CLR threshold, 1%% level: %r' % null.threshold(gmax, 0.99))
 
 
 def null_of_file(opt, ctx, ts, f):
@@ -588,6 +523,90 @@ def null_of_file(opt, ctx, ts, f):
         z = np.zeros(0)
         return z, z.astype(np.int32), z.astype(np.int32), np.full(opt.nullPerm, -np.inf)
     return null.run_file(ctx, opt.nullPerm, opt.nullSeed, opt.nullBlock, f)
+
+
+# ------------------------------------------------------------------------------- the stages after a file's observed scan
+# main() and main_many() differ in how a file reaches its Scan, in the names of the outputs and in the closing line; from there
+# on both run file_stages() per file and wrap_up() over the files' records (the one-file form: a list of one record).
+
+# One file's results that wait for all files: called = call_peaks()'s pair (None without --peaks), null = null_of_file()'s
+# tuple (None without --nullPerm), waiting = (data, neut, sel) when the file's power step waits for the genome-wide null;
+# ts: the test sites, kept only with --nullPerm (for the p-value file and the waiting power step) -- a whole genome's are large.
+FileRecord = namedtuple('FileRecord', 'outfile ts called null waiting')
+
+
+def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
+    """The additions' stages of one file (input-file ordinal f) whose observed scan has just run on ctx's selected slot and
+    written outfile, in their order; what still needs every file's results is left to wrap_up()."""
+    if opt.profiles is not None:
+        write_profiles(opt, ctx, sel, outfile, ts)
+        ctx.set_profiles(0)         # the observed scan's profiles only: the scans of --nullPerm, --locate and --power stay as they are
+        stamp('file %d: profiles' % (f + 1))
+    called = None
+    if opt.peaks is not None:
+        called = call_peaks(opt, ctx, ts)
+        ctx.refine_at_peaks(opt.atPeaks)
+        stamp('file %d: peaks' % (f + 1))
+    if opt.surfaces:
+        write_surfaces(opt, ctx, sel, outfile, ts, called, say)
+        stamp('file %d: surfaces' % (f + 1))
+    if opt.refine:
+        write_refined(opt, ctx, outfile, ts, f)
+        stamp('file %d: refine' % (f + 1))
+    if opt.locate:
+        write_locate(opt, ctx, outfile, ts, called, say, f)
+        stamp('file %d: locate' % (f + 1))
+    null = None
+    if opt.nullPerm:
+        # per-file permutations are independent (key of file ordinal f): only the host copies of this file's observed CLR and
+        # counts stay until the genome-wide maxima are known
+        null = null_of_file(opt, ctx, ts, f)
+        stamp('file %d: permutation null' % (f + 1))
+    waiting = None
+    if opt.power and opt.nullPerm:
+        waiting = (data, neut, sel)         # its thresholds wait for the last file's null
+    elif opt.power:
+        write_power(opt, ctx, sel, outfile, ts, data.genPos, planted, None, say, f)
+        stamp('file %d: power' % (f + 1))
+    return FileRecord(outfile, ts if opt.nullPerm else None, called, null, waiting)
+
+
+def wrap_up(opt, ctx, records, planted, say, stamp, inputs=None):
+    """What needs every file's results: the genome-wide null with the p-value files, the power steps that waited for its
+    thresholds, and the peak tables (whose p-value columns come from the p-value files).  records: file_stages()'s, in file
+    order, the last one's sites still in ctx.  inputs: the input files of the several-files form, which names the null file
+    by null_name() and adds the genome-wide peak table; None: the one-file form (<out>.null.txt, no such table)."""
+    gmax = None
+    if opt.nullPerm:
+        from . import null
+        null_path = null_name(opt.outfile, 'null') if inputs is not None else opt.outfile + '.null.txt'
+        gmax = np.full(opt.nullPerm, -np.inf)           # a replicate's genome-wide maximum: the maximum over the files
+        for rec in records:
+            gmax = np.maximum(gmax, rec.null[3])
+        null.write_null(null_path, gmax)
+        for rec in records:
+            null.write_pval(rec.outfile + '.pval.txt', rec.ts, *rec.null[:3], gmax)
+        say(f'\n{datetime.now()}. Permutation null: {opt.nullPerm} replicates (seed {opt.nullSeed}, blocks of {opt.nullBlock} site/s) -> {null_path}')
+        say('Genome-wide CLR threshold, 5%% level: %r' % null.threshold(gmax, 0.95))
+        say('Genome-wide CLR threshold, 1%% level: %r' % null.threshold(gmax, 0.99))
+        stamp('permutation null')
+    held = records[-1]
+    for f, rec in enumerate(records):
+        if rec.waiting is not None:
+            data, neut, sel = rec.waiting
+            if rec is not held:             # the file's sites (and its model, where it differs) go back into the context
+                sel.rebind(neut, ctx)
+                held = rec
+            write_power(opt, ctx, sel, rec.outfile, rec.ts, data.genPos, planted, gmax, say, f)
+            stamp('file %d: power' % (f + 1))
+    if opt.peaks is not None:
+        tables = [write_peaks(rec.outfile, rec.called, bool(opt.nullPerm)) for rec in records]
+        where = opt.outfile + '.peaks.txt'
+        if inputs is not None:
+            from . import peaks
+            where = null_name(opt.outfile, 'peaks')
+            peaks.write_genome(where, [(os.path.basename(i), t) for i, t in zip(inputs, tables)])
+        say(f'\n{datetime.now()}. Peaks: {sum(len(t) for t in tables)} (separation {opt.peaks!r}) -> {where}')
 
 
 def main(argv=None):
@@ -688,35 +707,8 @@ def main(argv=None):
     sc = Scan(data, Neutral, Sel_Probs, grid, opt.outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w,
               s=opt.step, phys=opt.phys, noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False)
     stamp('table, scan, output')
-    if pnames:
-        # the observed scan's profiles only: off before the null's replicates, whose cost and output stay as they are
-        write_profiles(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites)
-        Sel_Probs.ctx.set_profiles(0)
-        stamp('profiles')
-    if opt.peaks is not None:
-        called = call_peaks(opt, Sel_Probs.ctx, sc.test_sites)
-        Sel_Probs.ctx.refine_at_peaks(opt.atPeaks)
-        stamp('peaks')
-    if opt.surfaces:
-        write_surfaces(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites, called if opt.peaks is not None else None, say)
-        stamp('surfaces')
-    if opt.refine:
-        write_refined(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites)
-        stamp('refine')
-    if opt.locate:
-        write_locate(opt, Sel_Probs.ctx, opt.outfile, sc.test_sites, called, say)
-        stamp('locate')
-    if opt.nullPerm:
-        got = null_of_file(opt, Sel_Probs.ctx, sc.test_sites, 0)
-        finish_null(opt, [(opt.outfile, sc.test_sites) + got], opt.outfile + '.null.txt', say)
-        stamp('permutation null')
-    if opt.power:
-        write_power(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites, data.genPos, planted,
-                    got[3] if opt.nullPerm else None, say)
-        stamp('power')
-    if opt.peaks is not None:
-        n = len(write_peaks(opt.outfile, called, bool(opt.nullPerm)))
-        say(f'\n{datetime.now()}. Peaks: {n} (separation {opt.peaks!r}) -> {opt.outfile}.peaks.txt')
+    rec = file_stages(opt, Sel_Probs.ctx, Sel_Probs, opt.outfile, sc.test_sites, data, Neutral, 0, planted, say, stamp)
+    wrap_up(opt, Sel_Probs.ctx, [rec], planted, say, stamp)
     world.finish()
     say(f'\n{datetime.now()}. Pipeline finished.')
 
@@ -815,11 +807,7 @@ def main_many(opt, files, stamp=lambda what: None):
         pmask = profiles.mask(pnames)
     tables = 0
     kernel_ms = 0.0
-    null_files = []
-    peak_files = []
-    power_files = []
-    if opt.peaks is not None:
-        ctx.refine_at_peaks(opt.atPeaks)
+    records = []
     for i, (infile, outfile) in enumerate(zip(files, outs)):
         th.join()
         got = nxt.pop(i)
@@ -831,7 +819,7 @@ def main_many(opt, files, stamp=lambda what: None):
             th.start()
         say(f"\n{datetime.now()}. {infile} -> {outfile}")
         if pnames:
-            ctx.set_profiles(pmask)         # (switched off for the previous file's null replicates)
+            ctx.set_profiles(pmask)         # (switched off after the previous file's observed scan)
         sc = Scan(data, neut, sel, grid, outfile if world.rank == 0 else None, fixSize=opt.size, r=opt.w, s=opt.step, phys=opt.phys,
                   noCenter=opt.noCenter, runner=runner, verbose=verbose, keep_results=False, reuse_ctx=ctx)
         ctx = sel.ctx
@@ -841,44 +829,8 @@ def main_many(opt, files, stamp=lambda what: None):
         except Exception:           # a file without test sites
             pass
         stamp('file %d of %d' % (i + 1, len(files)))
-        if pnames:
-            write_profiles(opt, ctx, sel, outfile, sc.test_sites)
-            if opt.nullPerm or opt.locate or opt.power:
-                ctx.set_profiles(0)
-        if opt.peaks is not None:
-            peak_files.append((infile, outfile, call_peaks(opt, ctx, sc.test_sites)))
-        if opt.surfaces:
-            write_surfaces(opt, ctx, sel, outfile, sc.test_sites, peak_files[-1][2] if opt.peaks is not None else None, say)
-        if opt.refine:
-            write_refined(opt, ctx, outfile, sc.test_sites, i)
-        if opt.locate:
-            write_locate(opt, ctx, outfile, sc.test_sites, peak_files[-1][2], say, i)
-        if opt.nullPerm:
-            # per-file permutations are independent (key of file ordinal i): only the host copies of this file's observed
-            # CLR and counts stay until the genome-wide maxima are known
-            null_files.append((outfile, sc.test_sites) + null_of_file(opt, ctx, sc.test_sites, i))
-            stamp('file %d of %d: permutation null' % (i + 1, len(files)))
-        if opt.power and opt.nullPerm:
-            power_files.append((i, outfile, data, neut, sel, sc.test_sites))        # its thresholds wait for the last file's null
-        elif opt.power:
-            write_power(opt, ctx, sel, outfile, sc.test_sites, data.genPos, planted, None, say, i)
-    if opt.nullPerm:
-        finish_null(opt, null_files, null_name(opt.outfile, 'null'), say)
-    if power_files:
-        gmax = np.full(opt.nullPerm, -np.inf)
-        for rec in null_files:
-            gmax = np.maximum(gmax, rec[5])
-        for i, outfile, data, neut, sel, ts in power_files:
-            sel._bound_to = None            # the file's sites (and its model, where it differs) go back into the context
-            sel.bind(neut, reuse=ctx)
-            ctx = sel.ctx
-            write_power(opt, ctx, sel, outfile, ts, data.genPos, planted, gmax, say, i)
-    if opt.peaks is not None:
-        # (a few arrays per apex were kept per file; the tables wait for the null's p-value files)
-        from . import peaks
-        ptabs = [(os.path.basename(infile), write_peaks(outfile, called, bool(opt.nullPerm))) for infile, outfile, called in peak_files]
-        peaks.write_genome(null_name(opt.outfile, 'peaks'), ptabs)
-        say(f'\n{datetime.now()}. Peaks: {sum(len(r) for _, r in ptabs)} (separation {opt.peaks!r}) -> {null_name(opt.outfile, "peaks")}')
+        records.append(file_stages(opt, ctx, sel, outfile, sc.test_sites, data, neut, i, planted, say, stamp))
+    wrap_up(opt, ctx, records, planted, say, stamp, inputs=files)
     world.finish()
     say(f'\n{datetime.now()}. Pipeline finished: {len(files)} files, selection table built {tables} time(s), '
         f'scan kernels {kernel_ms / 1e3:.2f} s.')

@@ -594,6 +594,11 @@ class NormalizedBetaBinom:
         self._psel = None
         return self
 
+    def rebind(self, NeutralSFS, ctx):
+        """bind() again into ctx after another file's sites have replaced this one's there (cli.wrap_up)."""
+        self._bound_to = None
+        return self.bind(NeutralSFS, reuse=ctx)
+
     def prepare(self, NeutralSFS):
         """The host half of bind(): the bmx_model arrays and every site's table row.  No device call, so a whole-genome run
         does it for the next chromosome on a helper thread while the current one is scanned (cli.main_many)."""

@@ -48,6 +48,15 @@ DROP = 3.841458820694124          # chi-square(1) 95 % point
 COLUMNS = ('A', 'x', 's')         # coordinate k -> column stem (s: s_hat, alpha_beta)
 
 
+def value_refusal(drop, min_clr):
+    """The message that refuses these values of --supportDrop / --supportMin (None: the flag was not given), or None."""
+    if drop is not None and not (math.isfinite(drop) and drop > 0):
+        return '--supportDrop takes a finite number > 0.'
+    if min_clr is not None and min_clr != min_clr:
+        return '--supportMin takes a number.'
+    return None
+
+
 def centre(setup, grid_point, refined_point):
     """(c*, nat*, h0) of a window from its scan argmax (A, x, abeta) and its refined natural values."""
     c0, nat0, h0 = setup.start(*grid_point)
