@@ -5000,6 +5000,34 @@ struct DevBuf {
     }
 };
 
+// Device time of an interval on a stream; ms < 0: none measured yet.  The events are created on first use.
+struct DevTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double ms = -1.0;
+    hipError_t begin(hipStream_t s) {
+        hipError_t e = ev0 ? hipSuccess : hipEventCreate(&ev0);
+        if (e == hipSuccess && !ev1) e = hipEventCreate(&ev1);
+        return e == hipSuccess ? hipEventRecord(ev0, s) : e;
+    }
+    hipError_t end(hipStream_t s) { return hipEventRecord(ev1, s); }
+    hipError_t read() {         // once the caller has waited for the stream: ms = the interval
+        float f = 0.f;
+        const hipError_t e = hipEventElapsedTime(&f, ev0, ev1);
+        if (e == hipSuccess) ms = (double)f;
+        return e;
+    }
+    int get(double *out, const char *none_yet) const {          // the entry points' *_ms getters
+        if (ms < 0) return fail(BMX_E_STATE, none_yet);
+        *out = ms;
+        return BMX_OK;
+    }
+    void release() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        ev0 = ev1 = nullptr;
+    }
+};
+
 // fn(t, begin, end) on T host threads over [0, n)
 template <class F>
 void parallel_ranges(int64_t n, int64_t grain, F fn) {
@@ -5129,6 +5157,20 @@ struct ChromSlot {
     DevBuf<int32_t> lc_lo, lc_hi, lc_row;
     DevBuf<double> lc_clr;
 
+    // the row indices: 16-bit unless the table has more than 65535 rows (wide_rows); orig: the given rows while they are permuted
+    RowArray row_array() const { return RowArray{wide_rows ? nullptr : row16.p, wide_rows ? row32.p : nullptr}; }
+    void *row_ptr() const { return wide_rows ? (void *)row32.p : (void *)row16.p; }
+    void *orig_ptr() const { return wide_rows ? (void *)orig32.p : (void *)orig16.p; }
+    size_t row_bytes(size_t n) const { return n * (wide_rows ? sizeof(uint32_t) : sizeof(uint16_t)); }
+    hipError_t ensure_rows(size_t n, bool wide) {       // room for n of them in a slot without sites, about to receive them
+        wide_rows = wide;
+        return wide ? row32.ensure(n) : row16.ensure(n);
+    }
+    // what the entry points ask of the slot before they act (c: its context); each refuses with a message of its own
+    bool has_results() const { return has_tests && timed; }
+    bool ready_to_scan(const bmx_ctx *c) const;
+    bool has_refinement_of_last_scan(const bmx_ctx *c) const;
+
     void release_peaks() {
         pk_have = false;
         pk_flag.release(); pk_row.release(); pk_lo.release(); pk_hi.release(); pk_sad.release();
@@ -5197,8 +5239,7 @@ struct bmx_ctx {
     // surfaces of a list of test sites (bmx_ctx_surfaces): the list, one chunk's output, the events around a chunk's kernel
     DevBuf<double> sfs_T;
     DevBuf<int32_t> sfs_ns, sfs_list;
-    hipEvent_t sfs_ev0 = nullptr, sfs_ev1 = nullptr;
-    double sfs_ms = -1.0;
+    DevTimer sfs;
     DevBuf<int64_t> gap_sample;
     // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
     int pl_which = 0;
@@ -5216,8 +5257,7 @@ struct bmx_ctx {
     // restricts bmx_ctx_refine to the apexes (bmx_ctx_refine_at_peaks)
     DevBuf<double> pk_tmax, pk_track;
     DevBuf<int32_t> pk_tfirst;
-    hipEvent_t pk_ev0 = nullptr, pk_ev1 = nullptr;
-    double pk_ms = -1.0;
+    DevTimer pk;
     bool rf_at_peaks = false;
     // resampled sites (bmx_ctx_resample_sites): the tile sums of the weights, their prefix, the copies per table row
     DevBuf<int32_t> rs_tsum, rs_cnt;
@@ -5227,14 +5267,18 @@ struct bmx_ctx {
     DevBuf<double> pw_centre, pw_gw, fa_clr;
     DevBuf<int32_t> pw_first, pw_count, fa_idx, fa_lin, fa_ns;
     DevBuf<unsigned long long> pw_changed;
-    hipEvent_t pw_ev0 = nullptr, pw_ev1 = nullptr;
-    double pw_ms = -1.0;
+    DevTimer pw;
     std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
     void *h_stage[2] = {nullptr, nullptr};
     size_t h_stage_cap = 0;
     double zcut = 0;
 };
+
+inline bool ChromSlot::ready_to_scan(const bmx_ctx *c) const { return c->has_model && has_sites && has_tests; }
+inline bool ChromSlot::has_refinement_of_last_scan(const bmx_ctx *c) const {
+    return c->has_model && has_results() && rf_have && rf_seq == scan_seq;
+}
 
 namespace {
 
@@ -5272,6 +5316,23 @@ int upload(DevBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
     HIP_TRY(dst.ensure(n));
     if (n) HIP_TRY(hipMemcpyAsync(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
     return BMX_OK;
+}
+
+// n values back to the host, now; a NULL dst is an output the caller did not ask for
+template <class T>
+hipError_t download(T *dst, const T *src, size_t n) {
+    return dst ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+}
+
+// n flags -> their exclusive prefix in c->rf_pre (the count at rf_pre[n]) -> the flagged indices, ascending, in `list`.  Both only
+// enqueue on the context's stream: a caller that needs the count on the host reads rf_pre[n] back and waits itself.
+hipError_t flag_prefix(bmx_ctx *c, const int32_t *flag, int64_t n) {
+    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, flag, n, c->rf_pre.p);
+    return hipGetLastError();
+}
+hipError_t flag_compact(bmx_ctx *c, const int32_t *flag, int64_t n, int32_t *list) {
+    hipLaunchKernelGGL(refine_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, flag, (const int64_t *)c->rf_pre.p, n, list);
+    return hipGetLastError();
 }
 
 int validate_model(const bmx_model *m) {
@@ -5407,6 +5468,34 @@ int derive_row_tables(bmx_ctx *c, ChromSlot *s, const std::vector<int64_t> &cnt,
     HIP_TRY(hipStreamSynchronize(c->stream));     // the staging vectors go out of scope here
     return BMX_OK;
 }
+
+// A slot that receives sites derived from another slot's on the device (bmx_ctx_resample_sites, bmx_ctx_plant_sites).  The source:
+// src_slot checked, src = that slot if it holds sites, else nullptr (which the caller refuses after its own argument checks) ...
+int source_slot(bmx_ctx *c, const char *who, int32_t src_slot, ChromSlot *&src) {
+    if (src_slot < 0 || src_slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
+    if (src_slot == c->cur_index) return fail(BMX_E_INVALID, std::string(who) + ": the source slot must not be the selected slot");
+    src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot] : nullptr;
+    if (src && !src->has_sites) src = nullptr;
+    return BMX_OK;
+}
+// ... and the end: the n sites are in s->genpos and the slot's row array, their number per table row in c->rs_cnt.  The counts and
+// the two end positions come back -- with plant_sites' number of changed rows (c->pw_changed) behind them, on the same wait --
+// and everything set_sites derives from them follows on the host.
+int finish_derived_sites(bmx_ctx *c, ChromSlot *s, int64_t n, unsigned long long *changed = nullptr) {
+    std::vector<int32_t> cnt32((size_t)c->rows);
+    double ends[2] = {0.0, 0.0};
+    HIP_TRY(hipMemcpyAsync(cnt32.data(), c->rs_cnt.p, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[0], s->genpos.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[1], s->genpos.p + (n - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (changed) HIP_TRY(hipMemcpyAsync(changed, c->pw_changed.p, sizeof(*changed), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> cnt(cnt32.begin(), cnt32.end());
+    int rc;
+    if ((rc = derive_row_tables(c, s, cnt, n, ends[0], ends[1]))) return rc;
+    s->N = n;
+    s->has_sites = true;
+    return BMX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -5472,8 +5561,7 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->part_T.release(); c->part_lin.release(); c->part_ns.release(); c->arena.release(); c->gap_sample.release();
     c->surf_T.release(); c->surf_ns.release();
     c->sfs_T.release(); c->sfs_ns.release(); c->sfs_list.release();
-    if (c->sfs_ev0) (void)hipEventDestroy(c->sfs_ev0);
-    if (c->sfs_ev1) (void)hipEventDestroy(c->sfs_ev1);
+    c->sfs.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
@@ -5482,10 +5570,8 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->rs_tsum.release(); c->rs_cnt.release(); c->rs_tpre.release();
     c->pw_centre.release(); c->pw_gw.release(); c->pw_first.release(); c->pw_count.release(); c->pw_changed.release();
     c->fa_idx.release(); c->fa_clr.release(); c->fa_lin.release(); c->fa_ns.release();
-    if (c->pk_ev0) (void)hipEventDestroy(c->pk_ev0);
-    if (c->pk_ev1) (void)hipEventDestroy(c->pk_ev1);
-    if (c->pw_ev0) (void)hipEventDestroy(c->pw_ev0);
-    if (c->pw_ev1) (void)hipEventDestroy(c->pw_ev1);
+    c->pk.release();
+    c->pw.release();
     dfree(c->d_prof);
     dfree(c->d_status);
     for (int k = 0; k < 2; k++) {
@@ -5755,7 +5841,7 @@ int64_t pl_bytes_per_test(const bmx_ctx *c, int which) {
 
 int plan_scan(bmx_ctx *c, ChromSlot *s, ScanPlan &pl) {
     ScanParams &P = pl.P;
-    P.genpos = s->genpos.p; P.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; P.N = s->N; P.Rt = c->d_Rt;
+    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N; P.Rt = c->d_Rt;
     P.rows = c->rows; P.NP = c->NP; P.npairs = c->npairs; P.nslices = c->nslices;
     P.A = c->d_A; P.nA = c->nA; P.zcut = c->zcut; P.renorm_every = c->renorm_every; P.span_hi = c->span_hi; P.rmax = c->rmax;
     {
@@ -6129,7 +6215,7 @@ extern "C" {
 int bmx_ctx_scan(bmx_ctx *c) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before scan");
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before scan");
     HIP_TRY(hipSetDevice(c->device));
     std::vector<PrepRange> rs;
     int rc = scan_ranges(c, s, rs);
@@ -6151,7 +6237,7 @@ int bmx_ctx_scan(bmx_ctx *c) {
 int bmx_ctx_plan(bmx_ctx *c, int32_t *J, int32_t *use_lds, int32_t *mode, int64_t *stream_bytes) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before the plan exists");
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before the plan exists");
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_plan(c, s);
     if (rc) return rc;
@@ -6169,7 +6255,7 @@ int bmx_ctx_plan(bmx_ctx *c, int32_t *J, int32_t *use_lds, int32_t *mode, int64_
 int bmx_ctx_launch_ranges(bmx_ctx *c, int64_t *offs, int32_t cap, int32_t *n_out) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before the plan exists");
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before the plan exists");
     HIP_TRY(hipSetDevice(c->device));
     std::vector<PrepRange> rs;
     int rc = scan_ranges(c, s, rs);
@@ -6217,12 +6303,12 @@ int bmx_ctx_pack_records(bmx_ctx *c, void *dst, int64_t cap, int32_t dst_on_devi
     HIP_TRY(hipSetDevice(c->device));
     int64_t n = 0;
     for (ChromSlot *s : c->slots)
-        if (s && s->has_tests && s->timed) n += s->M;
+        if (s && s->has_results()) n += s->M;
     if (n_out) *n_out = n;
     if (n > cap) return fail(BMX_E_INVALID, "pack_records: destination too small");
     int64_t at = 0;
     for (ChromSlot *s : c->slots) {
-        if (!s || !s->has_tests || !s->timed) continue;
+        if (!s || !s->has_results()) continue;
         HIP_TRY(hipMemcpyAsync((bmx_record *)dst + at, s->rec.p, (size_t)s->M * sizeof(bmx_record),
                                dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
         at += s->M;
@@ -6234,7 +6320,7 @@ int bmx_ctx_pack_records(bmx_ctx *c, void *dst, int64_t cap, int32_t dst_on_devi
 int bmx_ctx_copy_records(bmx_ctx *c, void *dst_device, int64_t cap) {
     if (!c || !dst_device) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "no scan results in the selected slot");
+    if (!s->has_results()) return fail(BMX_E_STATE, "no scan results in the selected slot");
     if (cap < s->M) return fail(BMX_E_INVALID, "copy_records: destination too small");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(dst_device, s->rec.p, (size_t)s->M * sizeof(bmx_record), hipMemcpyDeviceToDevice, c->stream));
@@ -6256,7 +6342,7 @@ int bmx_ctx_last_scan_ms(bmx_ctx *c, double *ms) {
 int bmx_ctx_result_ptrs(bmx_ctx *c, void **d_clr, void **d_lin, void **d_nsites) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "no scan results: call bmx_ctx_scan after bmx_ctx_set_tests");
+    if (!s->has_results()) return fail(BMX_E_STATE, "no scan results: call bmx_ctx_scan after bmx_ctx_set_tests");
     if (d_clr) *d_clr = s->clr.p;
     if (d_lin) *d_lin = s->lin.p;
     if (d_nsites) *d_nsites = s->nsites.p;
@@ -6266,7 +6352,7 @@ int bmx_ctx_result_ptrs(bmx_ctx *c, void **d_clr, void **d_lin, void **d_nsites)
 int bmx_ctx_records(bmx_ctx *c, void **d_rec) {
     if (!c || !d_rec) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "no scan results: call bmx_ctx_scan after bmx_ctx_set_tests");
+    if (!s->has_results()) return fail(BMX_E_STATE, "no scan results: call bmx_ctx_scan after bmx_ctx_set_tests");
     *d_rec = s->rec.p;
     return BMX_OK;
 }
@@ -6274,7 +6360,7 @@ int bmx_ctx_records(bmx_ctx *c, void **d_rec) {
 int bmx_ctx_fetch_records(bmx_ctx *c, bmx_record *rec) {
     if (!c || !rec) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "no scan results to fetch");
+    if (!s->has_results()) return fail(BMX_E_STATE, "no scan results to fetch");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int st = check_status(c)) return st;
@@ -6285,13 +6371,13 @@ int bmx_ctx_fetch_records(bmx_ctx *c, bmx_record *rec) {
 int bmx_ctx_fetch(bmx_ctx *c, double *clr, int32_t *ix, int32_t *ia, int32_t *iA, int32_t *nsites) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "no scan results to fetch");
+    if (!s->has_results()) return fail(BMX_E_STATE, "no scan results to fetch");
     HIP_TRY(hipSetDevice(c->device));
     std::vector<int32_t> lin((size_t)s->M);
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int st = check_status(c)) return st;
-    if (clr) HIP_TRY(hipMemcpy(clr, s->clr.p, (size_t)s->M * sizeof(double), hipMemcpyDeviceToHost));
-    if (nsites) HIP_TRY(hipMemcpy(nsites, s->nsites.p, (size_t)s->M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(download(clr, s->clr.p, (size_t)s->M));
+    HIP_TRY(download(nsites, s->nsites.p, (size_t)s->M));
     HIP_TRY(hipMemcpy(lin.data(), s->lin.p, (size_t)s->M * sizeof(int32_t), hipMemcpyDeviceToHost));
     const int32_t npairs = c->npairs, nab = c->nab;
     parallel_ranges(s->M, 1 << 18, [&](int, int64_t b, int64_t e) {
@@ -6336,7 +6422,7 @@ int bmx_ctx_fetch_profile(bmx_ctx *c, int32_t which, double *out) {
     if (which != BMX_PL_A && which != BMX_PL_X && which != BMX_PL_ABETA) return fail(BMX_E_INVALID, "fetch_profile: one of BMX_PL_A, BMX_PL_X, BMX_PL_ABETA");
     if (!out) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed || !(s->pl_have & which)) return fail(BMX_E_STATE, "the slot's last scan did not compute this profile");
+    if (!s->has_results() || !(s->pl_have & which)) return fail(BMX_E_STATE, "the slot's last scan did not compute this profile");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int st = check_status(c)) return st;
@@ -6355,12 +6441,10 @@ int bmx_ctx_permute_rows(bmx_ctx *c, uint64_t key, int64_t block) {
     if (block < 1) return fail(BMX_E_INVALID, "permutation block size must be >= 1");
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)s->N;
-    const size_t bytes = N * (s->wide_rows ? sizeof(uint32_t) : sizeof(uint16_t));
-    void *cur = s->wide_rows ? (void *)s->row32.p : (void *)s->row16.p;
     if (!s->has_orig) {         // first permutation since set_sites: keep the given rows (on the stream, after any scan reading them)
         if (s->wide_rows) HIP_TRY(s->orig32.ensure(N));
         else HIP_TRY(s->orig16.ensure(N));
-        HIP_TRY(hipMemcpyAsync(s->wide_rows ? (void *)s->orig32.p : (void *)s->orig16.p, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(s->orig_ptr(), s->row_ptr(), s->row_bytes(N), hipMemcpyDeviceToDevice, c->stream));
         s->has_orig = true;
     }
     PermParams Q;
@@ -6368,8 +6452,7 @@ int bmx_ctx_permute_rows(bmx_ctx *c, uint64_t key, int64_t block) {
     Q.B = block;
     Q.nb = s->N / block;
     if (Q.nb < 2) {             // sigma is the identity: the rows given to set_sites
-        HIP_TRY(hipMemcpyAsync(cur, s->wide_rows ? (const void *)s->orig32.p : (const void *)s->orig16.p, bytes, hipMemcpyDeviceToDevice,
-                               c->stream));
+        HIP_TRY(hipMemcpyAsync(s->row_ptr(), s->orig_ptr(), s->row_bytes(N), hipMemcpyDeviceToDevice, c->stream));
     } else {
         int w = 0;
         for (uint64_t v = (uint64_t)(Q.nb - 1); v; v >>= 1) w++;
@@ -6394,9 +6477,7 @@ int bmx_ctx_restore_rows(bmx_ctx *c) {
     if (!s->has_sites) return fail(BMX_E_STATE, "set_sites must precede restore_rows");
     if (!s->has_orig) return BMX_OK;        // never permuted: the rows are the given ones
     HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)s->N * (s->wide_rows ? sizeof(uint32_t) : sizeof(uint16_t));
-    if (s->wide_rows) HIP_TRY(hipMemcpyAsync(s->row32.p, s->orig32.p, bytes, hipMemcpyDeviceToDevice, c->stream));
-    else HIP_TRY(hipMemcpyAsync(s->row16.p, s->orig16.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(s->row_ptr(), s->orig_ptr(), s->row_bytes((size_t)s->N), hipMemcpyDeviceToDevice, c->stream));
     s->plan_ok = false;
     s->prep_ok = false;
     return BMX_OK;
@@ -6405,7 +6486,7 @@ int bmx_ctx_restore_rows(bmx_ctx *c) {
 int bmx_ctx_null_begin(bmx_ctx *c) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "null_begin needs the observed scan: call bmx_ctx_scan first");
+    if (!s->has_results()) return fail(BMX_E_STATE, "null_begin needs the observed scan: call bmx_ctx_scan first");
     HIP_TRY(hipSetDevice(c->device));
     const size_t M = (size_t)s->M;
     HIP_TRY(s->null_obs.ensure(M));
@@ -6447,7 +6528,7 @@ int bmx_ctx_null_fetch(bmx_ctx *c, int32_t *counts, int32_t *replicates) {
     if (!s->null_ok) return fail(BMX_E_STATE, "null_begin must precede null_fetch");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (counts) HIP_TRY(hipMemcpy(counts, s->null_cnt.p, (size_t)s->M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(download(counts, s->null_cnt.p, (size_t)s->M));
     if (replicates) *replicates = s->null_reps;
     return BMX_OK;
 }
@@ -6457,9 +6538,9 @@ int bmx_ctx_fetch_lut(bmx_ctx *c, double *psel_out, double *R_out) {
     if (!c->has_model) return fail(BMX_E_STATE, "no model set");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    size_t tab = (size_t)c->npairs * c->rows * sizeof(double);
-    if (psel_out) HIP_TRY(hipMemcpy(psel_out, c->d_psel, tab, hipMemcpyDeviceToHost));
-    if (R_out) HIP_TRY(hipMemcpy(R_out, c->d_R, tab, hipMemcpyDeviceToHost));
+    const size_t tab = (size_t)c->npairs * c->rows;
+    HIP_TRY(download(psel_out, c->d_psel, tab));
+    HIP_TRY(download(R_out, c->d_R, tab));
     return BMX_OK;
 }
 
@@ -6469,7 +6550,7 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
     if (!c->has_model || !s->has_sites) return fail(BMX_E_STATE, "model and sites must be set before surface");
     HIP_TRY(hipSetDevice(c->device));
     SurfParams S;
-    S.genpos = s->genpos.p; S.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; S.N = s->N; S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs;
+    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N; S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs;
     S.nslices = c->nslices; S.A = c->d_A; S.nA = c->nA; S.tg = test_gen;
     S.lo = std::max<int64_t>(win_lo, 0); S.hi = std::min<int64_t>(win_hi, s->N - 1); S.zcut = c->zcut;
     HIP_TRY(c->surf_T.ensure((size_t)c->nA * c->npairs));
@@ -6487,16 +6568,12 @@ int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out,
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     if (n < 0) return fail(BMX_E_INVALID, "surfaces: n < 0");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before surfaces");
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before surfaces");
     if (n == 0) return BMX_OK;
     if (!tests || !T_out) return fail(BMX_E_INVALID, "surfaces: NULL argument");
     for (int64_t q = 0; q < n; q++)
         if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "surfaces: test site index out of range at entry " + std::to_string(q));
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->sfs_ev0) {
-        HIP_TRY(hipEventCreate(&c->sfs_ev0));
-        HIP_TRY(hipEventCreate(&c->sfs_ev1));
-    }
     const size_t per = (size_t)c->nA * c->npairs;              // doubles of one window's surface
     const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / (per * sizeof(double)), 1);
     const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
@@ -6509,7 +6586,7 @@ int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out,
     HIP_TRY(c->sfs_ns.ensure((size_t)std::min<int64_t>(step, n) * c->nA));
     HIP_TRY(hipMemcpyAsync(c->sfs_list.p, tests, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     SurfsParams S;
-    S.genpos = s->genpos.p; S.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; S.N = s->N;
+    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N;
     S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
     S.test_gen = s->test_gen.p; S.win_lo = s->win_lo.p; S.win_hi = s->win_hi.p; S.zcut = c->zcut;
     S.T = c->sfs_T.p; S.ns = c->sfs_ns.p;
@@ -6517,28 +6594,25 @@ int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out,
     for (int64_t q0 = 0; q0 < n; q0 += step) {
         const int64_t m = std::min(step, n - q0);
         S.tests = c->sfs_list.p + q0;
-        HIP_TRY(hipEventRecord(c->sfs_ev0, c->stream));
+        HIP_TRY(c->sfs.begin(c->stream));
         hipLaunchKernelGGL(surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->sfs_ev1, c->stream));
+        HIP_TRY(c->sfs.end(c->stream));
         // each chunk goes back before the next is launched: one device buffer serves the whole list
         HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (nsites_out)
             HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->sfs_ev0, c->sfs_ev1));
-        total += (double)ms;
+        HIP_TRY(c->sfs.read());
+        total += c->sfs.ms;
     }
-    c->sfs_ms = total;
+    c->sfs.ms = total;       // the call's figure: its chunks' kernels
     return BMX_OK;
 }
 
 int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
-    if (c->sfs_ms < 0) return fail(BMX_E_STATE, "no surfaces call yet");
-    *ms = c->sfs_ms;
-    return BMX_OK;
+    return c->sfs.get(ms, "no surfaces call yet");
 }
 
 }  // extern "C"
@@ -6584,7 +6658,7 @@ int refine_setup(bmx_ctx *c, ChromSlot *s, RefineParams &P, int max_rounds) {
     P.sizes = c->d_sizes; P.row_off = c->d_row_off; P.g = c->d_g; P.prop = c->d_prop;
     P.gA = c->d_A; P.gx = c->d_x; P.gab = c->d_abeta; P.npairs = c->npairs; P.nab = nab;
     P.max_rounds = max_rounds;
-    P.genpos = s->genpos.p; P.row = RowArray{s->wide_rows ? nullptr : s->row16.p, s->wide_rows ? s->row32.p : nullptr}; P.N = s->N;
+    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N;
     P.test_gen = s->test_gen.p; P.win_lo = s->win_lo.p; P.win_hi = s->win_hi.p; P.zcut = c->zcut;
     P.M = s->M;
     P.list = nullptr; P.count = nullptr; P.lin = nullptr; P.clr = nullptr; P.pA = P.px = P.pab = nullptr;
@@ -6611,13 +6685,36 @@ int refine_workspace(bmx_ctx *c, RefineParams &P, int64_t work, int64_t &blocks_
     return BMX_OK;
 }
 
-// ... and the launch of refine_kernel
-int refine_launch(bmx_ctx *c, RefineParams &P, int64_t work) {
+// ... and the launch of a kernel that works in it (refine_kernel, support_kernel, boot_kernel) with its parameters Q, whose
+// RefineParams are P
+template <class Params>
+int launch_ws(bmx_ctx *c, void (*kernel)(Params), Params &Q, RefineParams &P, int64_t work) {
     int64_t blocks = 0;
     int rc = refine_workspace(c, P, work, blocks);
     if (rc) return rc;
-    hipLaunchKernelGGL(refine_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), P.ws_lds ? (size_t)P.ws_bytes : 0, c->stream, P);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), P.ws_lds ? (size_t)P.ws_bytes : 0, c->stream, Q);
     HIP_TRY(hipGetLastError());
+    return BMX_OK;
+}
+
+// The points of a point evaluation (bmx_ctx_eval_points, bmx_ctx_eval_points_weighted): one (A, x, abeta) per test site of the
+// slot, checked; then, with the stream idle, P set up for them, the points in c->rf_pts and room for a value each in c->rf_pT
+int upload_points(bmx_ctx *c, const char *who, const double *A, const double *x, const double *abeta, RefineParams &P) {
+    ChromSlot *s = c->cur;
+    const int64_t M = s->M;
+    for (int64_t t = 0; t < M; t++)
+        if (!(A[t] > 0.0) || !(x[t] > 0.0 && x[t] < 1.0) || !(abeta[t] > 0.0) || !std::isfinite(A[t]) || !std::isfinite(abeta[t]))
+            return fail(BMX_E_INVALID, std::string(who) + ": A > 0, 0 < x < 1 and alpha_beta > 0 (finite) at every point");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int rc = refine_setup(c, s, P, 0);
+    if (rc) return rc;
+    HIP_TRY(c->rf_pts.ensure((size_t)3 * M));
+    const double *src[3] = {A, x, abeta};
+    for (int k = 0; k < 3; k++)
+        HIP_TRY(hipMemcpyAsync(c->rf_pts.p + k * M, src[k], (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->rf_pT.ensure((size_t)M));
+    P.pA = c->rf_pts.p; P.px = c->rf_pts.p + M; P.pab = c->rf_pts.p + 2 * M;
     return BMX_OK;
 }
 
@@ -6628,25 +6725,14 @@ extern "C" {
 int bmx_ctx_eval_points(bmx_ctx *c, const double *A, const double *x, const double *abeta, double *T_out, int32_t *nsites_out) {
     if (!c || !A || !x || !abeta || !T_out) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_sites || !s->has_tests) return fail(BMX_E_STATE, "model, sites and tests must be set before eval_points");
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before eval_points");
     const int64_t M = s->M;
-    for (int64_t t = 0; t < M; t++)
-        if (!(A[t] > 0.0) || !(x[t] > 0.0 && x[t] < 1.0) || !(abeta[t] > 0.0) || !std::isfinite(A[t]) || !std::isfinite(abeta[t]))
-            return fail(BMX_E_INVALID, "eval_points: A > 0, 0 < x < 1 and alpha_beta > 0 (finite) at every point");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
     RefineParams P;
-    int rc = refine_setup(c, s, P, 0);
+    int rc = upload_points(c, "eval_points", A, x, abeta, P);
     if (rc) return rc;
-    HIP_TRY(c->rf_pts.ensure((size_t)3 * M));
-    HIP_TRY(hipMemcpyAsync(c->rf_pts.p, A, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + M, x, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + 2 * M, abeta, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c->rf_pT.ensure((size_t)M));
     HIP_TRY(c->rf_pns.ensure((size_t)M));
-    P.pA = c->rf_pts.p; P.px = c->rf_pts.p + M; P.pab = c->rf_pts.p + 2 * M;
     P.o_clr = c->rf_pT.p; P.o_ns = c->rf_pns.p;
-    if ((rc = refine_launch(c, P, M))) return rc;
+    if ((rc = launch_ws(c, refine_kernel, P, P, M))) return rc;
     HIP_TRY(hipMemcpyAsync(T_out, c->rf_pT.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out, c->rf_pns.p, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -6656,7 +6742,7 @@ int bmx_ctx_eval_points(bmx_ctx *c, const double *A, const double *x, const doub
 int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_tests || !s->timed) return fail(BMX_E_STATE, "refine: no scan results (scan the slot first)");
+    if (!c->has_model || !s->has_results()) return fail(BMX_E_STATE, "refine: no scan results (scan the slot first)");
     if (min_clr != min_clr) return fail(BMX_E_INVALID, "refine: min_clr is NaN");
     if (c->rf_at_peaks && !(s->pk_have && s->pk_scan && s->pk_seq == s->scan_seq && s->pk_M == s->M))
         return fail(BMX_E_INVALID, "refine: restricted to the apexes (bmx_ctx_refine_at_peaks), but the slot has no peak call on its last scan: "
@@ -6677,18 +6763,14 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     Q.gA = c->d_A; Q.gx = c->d_x; Q.gab = c->d_abeta; Q.npairs = c->npairs; Q.nab = c->nab;
     Q.M = M; Q.min_clr = min_clr; Q.flag = c->rf_flag.p;
     Q.o_clr = s->rf_clr.p; Q.o_A = s->rf_A.p; Q.o_x = s->rf_x.p; Q.o_ab = s->rf_ab.p; Q.o_ns = s->rf_ns.p; Q.o_rounds = s->rf_rounds.p;
-    const unsigned nb = (unsigned)((M + 255) / 256);
-    hipLaunchKernelGGL(refine_init_kernel, dim3(nb), dim3(256), 0, c->stream, Q);
+    hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, Q);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rf_flag.p, M, c->rf_pre.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)c->rf_flag.p,
-                       (const int64_t *)c->rf_pre.p, M, c->rf_list.p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(flag_prefix(c, c->rf_flag.p, M));
+    HIP_TRY(flag_compact(c, c->rf_flag.p, M, c->rf_list.p));
     P.list = c->rf_list.p; P.count = c->rf_pre.p + M;
     P.lin = s->lin.p; P.clr = s->clr.p;
     P.o_clr = s->rf_clr.p; P.o_A = s->rf_A.p; P.o_x = s->rf_x.p; P.o_ab = s->rf_ab.p; P.o_ns = s->rf_ns.p; P.o_rounds = s->rf_rounds.p;
-    if ((rc = refine_launch(c, P, M))) return rc;
+    if ((rc = launch_ws(c, refine_kernel, P, P, M))) return rc;
     s->rf_have = true;
     s->rf_seq = s->scan_seq;
     s->release_support();
@@ -6703,19 +6785,15 @@ int bmx_ctx_fetch_refined(bmx_ctx *c, double *clr, double *A, double *x, double 
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t M = (size_t)s->M;
-    if (clr) HIP_TRY(hipMemcpy(clr, s->rf_clr.p, M * sizeof(double), hipMemcpyDeviceToHost));
-    if (A) HIP_TRY(hipMemcpy(A, s->rf_A.p, M * sizeof(double), hipMemcpyDeviceToHost));
-    if (x) HIP_TRY(hipMemcpy(x, s->rf_x.p, M * sizeof(double), hipMemcpyDeviceToHost));
-    if (abeta) HIP_TRY(hipMemcpy(abeta, s->rf_ab.p, M * sizeof(double), hipMemcpyDeviceToHost));
-    if (nsites) HIP_TRY(hipMemcpy(nsites, s->rf_ns.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (rounds) HIP_TRY(hipMemcpy(rounds, s->rf_rounds.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(download(clr, s->rf_clr.p, M)); HIP_TRY(download(A, s->rf_A.p, M)); HIP_TRY(download(x, s->rf_x.p, M));
+    HIP_TRY(download(abeta, s->rf_ab.p, M)); HIP_TRY(download(nsites, s->rf_ns.p, M)); HIP_TRY(download(rounds, s->rf_rounds.p, M));
     return BMX_OK;
 }
 
 int bmx_ctx_support(bmx_ctx *c, double drop, double min_clr) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_tests || !s->timed || !s->rf_have || s->rf_seq != s->scan_seq)
+    if (!s->has_refinement_of_last_scan(c))
         return fail(BMX_E_STATE, "support: no refinement of the slot's last scan (call bmx_ctx_refine after the scan)");
     if (!(drop > 0.0) || !std::isfinite(drop)) return fail(BMX_E_INVALID, "support: drop must be finite and > 0");
     if (min_clr != min_clr) return fail(BMX_E_INVALID, "support: min_clr is NaN");
@@ -6737,23 +6815,15 @@ int bmx_ctx_support(bmx_ctx *c, double drop, double min_clr) {
     I.clr = s->rf_clr.p; I.rounds = s->rf_rounds.p;
     for (int k = 0; k < 3; k++) I.fr[k] = Q.P.fr[k];
     I.M = M; I.min_clr = min_clr; I.flag = c->rf_flag.p; I.o_d = s->sp_d.p; I.o_i = s->sp_i.p;
-    const unsigned nb = (unsigned)((nt + 255) / 256);
-    hipLaunchKernelGGL(support_init_kernel, dim3(nb), dim3(256), 0, c->stream, I);
+    hipLaunchKernelGGL(support_init_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, I);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rf_flag.p, nt, c->rf_pre.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)c->rf_flag.p,
-                       (const int64_t *)c->rf_pre.p, nt, c->rf_list.p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(flag_prefix(c, c->rf_flag.p, nt));
+    HIP_TRY(flag_compact(c, c->rf_flag.p, nt, c->rf_list.p));
     Q.P.lin = s->lin.p; Q.P.clr = s->clr.p;
     Q.list = c->rf_list.p; Q.count = c->rf_pre.p + nt;
     Q.rA = s->rf_A.p; Q.rx = s->rf_x.p; Q.rab = s->rf_ab.p;
     Q.o_d = s->sp_d.p; Q.o_i = s->sp_i.p;
-    int64_t blocks = 0;
-    if ((rc = refine_workspace(c, Q.P, nt, blocks))) return rc;
-    hipLaunchKernelGGL(support_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), Q.P.ws_lds ? (size_t)Q.P.ws_bytes : 0,
-                       c->stream, Q);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_ws(c, support_kernel, Q, Q.P, nt))) return rc;
     s->sp_have = true;
     return BMX_OK;
 }
@@ -6801,51 +6871,26 @@ int bmx_ctx_fetch_support(bmx_ctx *c, double *end, double *witness, double *witn
 
 /* ---- block bootstrap (ballermixplus_amd/boot.py holds the definition: weights, objective, one replicate) ---- */
 
-namespace {
-
-int boot_launch(bmx_ctx *c, BootParams &Q, int64_t work) {
-    int64_t blocks = 0;
-    int rc = refine_workspace(c, Q.P, work, blocks);
-    if (rc) return rc;
-    hipLaunchKernelGGL(boot_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), Q.P.ws_lds ? (size_t)Q.P.ws_bytes : 0, c->stream, Q);
-    HIP_TRY(hipGetLastError());
-    return BMX_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int bmx_ctx_eval_points_weighted(bmx_ctx *c, uint64_t key, int64_t block, const double *A, const double *x, const double *abeta,
                                  double *T_out, int64_t *wsum_out) {
     if (!c || !A || !x || !abeta || !T_out) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_sites || !s->has_tests)
-        return fail(BMX_E_STATE, "model, sites and tests must be set before eval_points_weighted");
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before eval_points_weighted");
     if (block < 1) return fail(BMX_E_INVALID, "eval_points_weighted: block must be >= 1");
     const int64_t M = s->M;
-    for (int64_t t = 0; t < M; t++)
-        if (!(A[t] > 0.0) || !(x[t] > 0.0 && x[t] < 1.0) || !(abeta[t] > 0.0) || !std::isfinite(A[t]) || !std::isfinite(abeta[t]))
-            return fail(BMX_E_INVALID, "eval_points_weighted: A > 0, 0 < x < 1 and alpha_beta > 0 (finite) at every point");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
     BootParams Q;
-    int rc = refine_setup(c, s, Q.P, 0);
+    int rc = upload_points(c, "eval_points_weighted", A, x, abeta, Q.P);
     if (rc) return rc;
-    HIP_TRY(c->rf_pts.ensure((size_t)3 * M));
-    HIP_TRY(hipMemcpyAsync(c->rf_pts.p, A, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + M, x, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->rf_pts.p + 2 * M, abeta, (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c->rf_pT.ensure((size_t)M));
     HIP_TRY(c->bt_pws.ensure((size_t)M));
     HIP_TRY(c->bt_keys.ensure(1));
     HIP_TRY(hipMemcpyAsync(c->bt_keys.p, &key, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    Q.P.pA = c->rf_pts.p; Q.P.px = c->rf_pts.p + M; Q.P.pab = c->rf_pts.p + 2 * M;
     Q.keys = c->bt_keys.p; Q.R = 1; Q.block = block;
     Q.list = nullptr; Q.count = nullptr; Q.rA = Q.rx = Q.rab = nullptr;
     Q.o_A = Q.o_x = Q.o_ab = Q.o_Tc = nullptr; Q.o_rounds = nullptr;
     Q.o_T = c->rf_pT.p; Q.o_wsum = c->bt_pws.p;
-    if ((rc = boot_launch(c, Q, M))) return rc;
+    if ((rc = launch_ws(c, boot_kernel, Q, Q.P, M))) return rc;
     HIP_TRY(hipMemcpyAsync(T_out, c->rf_pT.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (wsum_out) HIP_TRY(hipMemcpyAsync(wsum_out, c->bt_pws.p, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));     // (also: `key` leaves scope here)
@@ -6855,7 +6900,7 @@ int bmx_ctx_eval_points_weighted(bmx_ctx *c, uint64_t key, int64_t block, const 
 int bmx_ctx_boot(bmx_ctx *c, const uint64_t *keys, int32_t R, int64_t block, double min_clr) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_tests || !s->timed || !s->rf_have || s->rf_seq != s->scan_seq)
+    if (!s->has_refinement_of_last_scan(c))
         return fail(BMX_E_STATE, "boot: no refinement of the slot's last scan (call bmx_ctx_refine after the scan)");
     if (!keys || R < 1) return fail(BMX_E_INVALID, "boot: at least one replicate key is needed");
     if (block < 1) return fail(BMX_E_INVALID, "boot: block must be >= 1");
@@ -6870,15 +6915,11 @@ int bmx_ctx_boot(bmx_ctx *c, const uint64_t *keys, int32_t R, int64_t block, dou
     HIP_TRY(c->rf_flag.ensure((size_t)M));
     HIP_TRY(c->rf_pre.ensure((size_t)M + 1));
     HIP_TRY(s->bt_win.ensure((size_t)M));
-    const unsigned nb = (unsigned)((M + 255) / 256);
-    hipLaunchKernelGGL(boot_init_kernel, dim3(nb), dim3(256), 0, c->stream, (const double *)s->rf_clr.p,
+    hipLaunchKernelGGL(boot_init_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, (const double *)s->rf_clr.p,
                        (const int32_t *)s->rf_rounds.p, M, min_clr, c->rf_flag.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->rf_flag.p, M, c->rf_pre.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)c->rf_flag.p,
-                       (const int64_t *)c->rf_pre.p, M, s->bt_win.p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(flag_prefix(c, c->rf_flag.p, M));
+    HIP_TRY(flag_compact(c, c->rf_flag.p, M, s->bt_win.p));
     int64_t nsel = 0;
     HIP_TRY(hipMemcpyAsync(&nsel, c->rf_pre.p + M, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -6898,7 +6939,7 @@ int bmx_ctx_boot(bmx_ctx *c, const uint64_t *keys, int32_t R, int64_t block, dou
         Q.rA = s->rf_A.p; Q.rx = s->rf_x.p; Q.rab = s->rf_ab.p;
         Q.o_A = s->bt_A.p; Q.o_x = s->bt_x.p; Q.o_ab = s->bt_ab.p; Q.o_T = s->bt_T.p; Q.o_Tc = s->bt_Tc.p;
         Q.o_rounds = s->bt_rounds.p; Q.o_wsum = nullptr;
-        if ((rc = boot_launch(c, Q, (int64_t)nt))) return rc;
+        if ((rc = launch_ws(c, boot_kernel, Q, Q.P, (int64_t)nt))) return rc;
     }
     s->bt_have = true;
     return BMX_OK;
@@ -6924,13 +6965,9 @@ int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t n = (size_t)s->bt_nsel, nt = n * (size_t)s->bt_R;
     if (!nt) return BMX_OK;
-    if (window) HIP_TRY(hipMemcpy(window, s->bt_win.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (A) HIP_TRY(hipMemcpy(A, s->bt_A.p, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (x) HIP_TRY(hipMemcpy(x, s->bt_x.p, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (abeta) HIP_TRY(hipMemcpy(abeta, s->bt_ab.p, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (T) HIP_TRY(hipMemcpy(T, s->bt_T.p, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (T_centre) HIP_TRY(hipMemcpy(T_centre, s->bt_Tc.p, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (rounds) HIP_TRY(hipMemcpy(rounds, s->bt_rounds.p, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(download(window, s->bt_win.p, n));
+    HIP_TRY(download(A, s->bt_A.p, nt)); HIP_TRY(download(x, s->bt_x.p, nt)); HIP_TRY(download(abeta, s->bt_ab.p, nt));
+    HIP_TRY(download(T, s->bt_T.p, nt)); HIP_TRY(download(T_centre, s->bt_Tc.p, nt)); HIP_TRY(download(rounds, s->bt_rounds.p, nt));
     return BMX_OK;
 }
 
@@ -6939,12 +6976,11 @@ int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double
 int bmx_ctx_resample_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int64_t block, int64_t *N_out) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     if (!c->has_model) return fail(BMX_E_STATE, "set_model must precede resample_sites");
-    if (src_slot < 0 || src_slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
-    if (src_slot == c->cur_index) return fail(BMX_E_INVALID, "resample_sites: the source slot must not be the selected slot");
+    ChromSlot *src = nullptr, *s = c->cur;
+    int rc = source_slot(c, "resample_sites", src_slot, src);
+    if (rc) return rc;
     if (block < 1) return fail(BMX_E_INVALID, "resampling block size must be >= 1");
-    ChromSlot *src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot] : nullptr;
-    if (!src || !src->has_sites) return fail(BMX_E_STATE, "resample_sites: the source slot has no sites");
-    ChromSlot *s = c->cur;
+    if (!src) return fail(BMX_E_STATE, "resample_sites: the source slot has no sites");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_sites(s);
@@ -6965,15 +7001,14 @@ int bmx_ctx_resample_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int64_t b
     if (total < 1) return BMX_OK;             // every weight is 0: the slot stays without sites
     const bool wide = src->wide_rows;
     HIP_TRY(s->genpos.ensure((size_t)total));
-    if (wide) HIP_TRY(s->row32.ensure((size_t)total));
-    else HIP_TRY(s->row16.ensure((size_t)total));
+    HIP_TRY(s->ensure_rows((size_t)total, wide));
     HIP_TRY(hipMemsetAsync(c->rs_cnt.p, 0, (size_t)c->rows * sizeof(int32_t), c->stream));
     ResampleParams Q;
     Q.key = key; Q.B = block; Q.N = N; Q.ntiles = ntiles; Q.N_out = total;
     Q.src_gen = src->genpos.p;
-    Q.src_row = wide ? (const void *)src->row32.p : (const void *)src->row16.p;
+    Q.src_row = src->row_ptr();
     Q.dst_gen = s->genpos.p;
-    Q.dst_row = wide ? (void *)s->row32.p : (void *)s->row16.p;
+    Q.dst_row = s->row_ptr();
     Q.tile_pre = c->rs_tpre.p;
     Q.cnt = c->rs_cnt.p;
     Q.rows = c->rows;
@@ -6982,19 +7017,7 @@ int bmx_ctx_resample_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int64_t b
     if (wide) hipLaunchKernelGGL(resample_expand_kernel<uint32_t>, dim3(blocks), dim3(RS_THREADS), lds, c->stream, Q);
     else hipLaunchKernelGGL(resample_expand_kernel<uint16_t>, dim3(blocks), dim3(RS_THREADS), lds, c->stream, Q);
     HIP_TRY(hipGetLastError());
-    // the per-row counts and the two end positions come back; everything set_sites derives from them follows on the host
-    std::vector<int32_t> cnt32((size_t)c->rows);
-    double ends[2] = {0.0, 0.0};
-    HIP_TRY(hipMemcpyAsync(cnt32.data(), c->rs_cnt.p, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&ends[0], s->genpos.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&ends[1], s->genpos.p + (total - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::vector<int64_t> cnt(cnt32.begin(), cnt32.end());
-    s->wide_rows = wide;
-    int rc;
-    if ((rc = derive_row_tables(c, s, cnt, total, ends[0], ends[1]))) return rc;
-    s->N = total;
-    s->has_sites = true;
+    if ((rc = finish_derived_sites(c, s, total))) return rc;
     if (N_out) *N_out = total;
     return BMX_OK;
 }
@@ -7006,7 +7029,7 @@ int bmx_ctx_fetch_sites(bmx_ctx *c, double *genpos_out, int32_t *row_out) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t N = (size_t)s->N;
-    if (genpos_out) HIP_TRY(hipMemcpy(genpos_out, s->genpos.p, N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(download(genpos_out, s->genpos.p, N));
     if (row_out) {
         if (s->wide_rows) {
             HIP_TRY(hipMemcpy(row_out, s->row32.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -7053,7 +7076,7 @@ int bmx_ctx_locate_accumulate(bmx_ctx *c, int32_t r) {
     ChromSlot *s = c->cur;
     if (!s->lc_ok) return fail(BMX_E_STATE, "locate_begin must precede locate_accumulate");
     if (r < 0 || r >= s->lc_R) return fail(BMX_E_INVALID, "locate_accumulate: replicate index outside [0, R)");
-    if (!s->has_tests || !s->timed || s->scan_seq == s->lc_seq)
+    if (!s->has_results() || s->scan_seq == s->lc_seq)
         return fail(BMX_E_STATE, "locate_accumulate needs a new scan (one per replicate)");
     if (s->M < s->lc_M) return fail(BMX_E_INVALID, "locate_accumulate: a range reaches past the slot's test sites");
     HIP_TRY(hipSetDevice(c->device));
@@ -7075,8 +7098,8 @@ int bmx_ctx_fetch_locate(bmx_ctx *c, int32_t *row_out, double *clr_out) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t n = (size_t)s->lc_K * (size_t)s->lc_R;
-    if (row_out) HIP_TRY(hipMemcpy(row_out, s->lc_row.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (clr_out) HIP_TRY(hipMemcpy(clr_out, s->lc_clr.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(download(row_out, s->lc_row.p, n));
+    HIP_TRY(download(clr_out, s->lc_clr.p, n));
     return BMX_OK;
 }
 
@@ -7086,8 +7109,9 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
                         int32_t ia, const double *gw, int32_t *first_out, int32_t *count_out, int64_t *changed_out) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     if (!c->has_model) return fail(BMX_E_STATE, "set_model must precede plant_sites");
-    if (src_slot < 0 || src_slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
-    if (src_slot == c->cur_index) return fail(BMX_E_INVALID, "plant_sites: the source slot must not be the selected slot");
+    ChromSlot *src = nullptr, *s = c->cur;
+    int rc = source_slot(c, "plant_sites", src_slot, src);
+    if (rc) return rc;
     if (K < 0) return fail(BMX_E_INVALID, "plant_sites: K must be >= 0");
     if (iA < 0 || iA >= c->nA || ix < 0 || ix >= c->nx || ia < 0 || ia >= c->nab)
         return fail(BMX_E_INVALID, "plant_sites: the planted grid point lies outside the model's grids");
@@ -7098,28 +7122,17 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
         if (k + 1 < K && !(A * (centre[k + 1] - centre[k]) > 2.000001 * c->zcut))
             return fail(BMX_E_INVALID, "plant_sites: the centres must ascend and lie more than twice the reach apart");
     }
-    ChromSlot *src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot] : nullptr;
-    if (!src || !src->has_sites) return fail(BMX_E_STATE, "plant_sites: the source slot has no sites");
-    ChromSlot *s = c->cur;
+    if (!src) return fail(BMX_E_STATE, "plant_sites: the source slot has no sites");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_sites(s);
     if (changed_out) *changed_out = 0;
-    if (!c->pw_ev0) {
-        HIP_TRY(hipEventCreate(&c->pw_ev0));
-        HIP_TRY(hipEventCreate(&c->pw_ev1));
-    }
     const int64_t N = src->N;
     const bool wide = src->wide_rows;
-    const size_t row_bytes = (size_t)N * (wide ? sizeof(uint32_t) : sizeof(uint16_t));
     HIP_TRY(s->genpos.ensure((size_t)N));
-    if (wide) HIP_TRY(s->row32.ensure((size_t)N));
-    else HIP_TRY(s->row16.ensure((size_t)N));
+    HIP_TRY(s->ensure_rows((size_t)N, wide));
     HIP_TRY(c->rs_cnt.ensure((size_t)c->rows));
     HIP_TRY(c->pw_changed.ensure(1));
-    void *dst_row = wide ? (void *)s->row32.p : (void *)s->row16.p;
-    const void *src_row = wide ? (const void *)src->row32.p : (const void *)src->row16.p;
-    int rc;
     std::vector<int32_t> first((size_t)K), count((size_t)K);
     if (K > 0) {
         if ((rc = upload(c->pw_centre, centre, (size_t)K, c->stream))) return rc;
@@ -7127,9 +7140,9 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
         HIP_TRY(c->pw_first.ensure((size_t)K));
         HIP_TRY(c->pw_count.ensure((size_t)K));
     }
-    HIP_TRY(hipEventRecord(c->pw_ev0, c->stream));
+    HIP_TRY(c->pw.begin(c->stream));
     HIP_TRY(hipMemcpyAsync(s->genpos.p, src->genpos.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dst_row, src_row, row_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(s->row_ptr(), src->row_ptr(), s->row_bytes((size_t)N), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->pw_changed.p, 0, sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemsetAsync(c->rs_cnt.p, 0, (size_t)c->rows * sizeof(int32_t), c->stream));
     if (K > 0) {
@@ -7149,7 +7162,7 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
             PlantParams Q;
             Q.key = key;
             Q.gen = src->genpos.p;
-            Q.src_row = src_row; Q.dst_row = dst_row;
+            Q.src_row = src->row_ptr(); Q.dst_row = s->row_ptr();
             Q.centre = c->pw_centre.p; Q.first = c->pw_first.p; Q.count = c->pw_count.p; Q.K = K;
             Q.A = A; Q.zcut = c->zcut;
             Q.gw = c->pw_gw.p;
@@ -7179,23 +7192,10 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
                                 c->rs_cnt.p, c->rows, use_hist);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(c->pw_ev1, c->stream));
-    std::vector<int32_t> cnt32((size_t)c->rows);
-    double ends[2] = {0.0, 0.0};
+    HIP_TRY(c->pw.end(c->stream));
     unsigned long long changed = 0;
-    HIP_TRY(hipMemcpyAsync(cnt32.data(), c->rs_cnt.p, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&ends[0], s->genpos.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&ends[1], s->genpos.p + (N - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&changed, c->pw_changed.p, sizeof(changed), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
-    c->pw_ms = (double)ms;
-    std::vector<int64_t> cnt(cnt32.begin(), cnt32.end());
-    s->wide_rows = wide;
-    if ((rc = derive_row_tables(c, s, cnt, N, ends[0], ends[1]))) return rc;
-    s->N = N;
-    s->has_sites = true;
+    if ((rc = finish_derived_sites(c, s, N, &changed))) return rc;
+    HIP_TRY(c->pw.read());          // (that call has waited for the stream)
     for (int32_t k = 0; k < K; k++) {
         if (first_out) first_out[k] = first[(size_t)k];
         if (count_out) count_out[k] = count[(size_t)k];
@@ -7206,15 +7206,13 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
 
 int bmx_ctx_plant_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "null argument");
-    if (c->pw_ms < 0.0) return fail(BMX_E_STATE, "no plant_sites call yet");
-    *ms = c->pw_ms;
-    return BMX_OK;
+    return c->pw.get(ms, "no plant_sites call yet");
 }
 
 int bmx_ctx_fetch_at(bmx_ctx *c, int64_t n, const int32_t *tests, double *clr, int32_t *lin, int32_t *nsites) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!s->has_tests || !s->timed) return fail(BMX_E_STATE, "fetch_at needs a scan: call bmx_ctx_scan first");
+    if (!s->has_results()) return fail(BMX_E_STATE, "fetch_at needs a scan: call bmx_ctx_scan first");
     if (n < 0 || (n > 0 && !tests)) return fail(BMX_E_INVALID, "fetch_at: a list of test sites must be given");
     if (n > 0x7fffff00LL) return fail(BMX_E_LIMIT, "fetch_at: more than 2^31 indices");
     for (int64_t j = 0; j < n; j++)
@@ -7231,9 +7229,7 @@ int bmx_ctx_fetch_at(bmx_ctx *c, int64_t n, const int32_t *tests, double *clr, i
                        c->fa_ns.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (clr) HIP_TRY(hipMemcpy(clr, c->fa_clr.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    if (lin) HIP_TRY(hipMemcpy(lin, c->fa_lin.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nsites) HIP_TRY(hipMemcpy(nsites, c->fa_ns.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(download(clr, c->fa_clr.p, (size_t)n)); HIP_TRY(download(lin, c->fa_lin.p, (size_t)n)); HIP_TRY(download(nsites, c->fa_ns.p, (size_t)n));
     return BMX_OK;
 }
 
@@ -7254,12 +7250,8 @@ int peaks_check(const char *who, double sep, double min_clr, double frac) {
 int peaks_run(bmx_ctx *c, ChromSlot *s, const double *g, const double *clr, int64_t M, double sep, double min_clr, double frac) {
     if (M > 0x7fffff00LL) return fail(BMX_E_LIMIT, "peaks: more than 2^31 rows");
     s->pk_have = false;
-    if (!c->pk_ev0) {
-        HIP_TRY(hipEventCreate(&c->pk_ev0));
-        HIP_TRY(hipEventCreate(&c->pk_ev1));
-    }
     int64_t K = 0;
-    HIP_TRY(hipEventRecord(c->pk_ev0, c->stream));
+    HIP_TRY(c->pk.begin(c->stream));
     if (M > 0) {
         const int64_t tiles = (M + PEAK_TILE - 1) / PEAK_TILE;
         HIP_TRY(c->pk_tmax.ensure((size_t)tiles));
@@ -7275,16 +7267,13 @@ int peaks_run(bmx_ctx *c, ChromSlot *s, const double *g, const double *clr, int6
         hipLaunchKernelGGL(peak_apex_kernel, dim3(nb), dim3(PEAK_THREADS), 0, c->stream, Q);
         HIP_TRY(hipGetLastError());
         // the apexes in row order: the order is part of the result, so a prefix sum and not an atomic counter
-        hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)s->pk_flag.p, M, c->rf_pre.p);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(flag_prefix(c, s->pk_flag.p, M));
         HIP_TRY(hipMemcpyAsync(&K, c->rf_pre.p + M, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));       // the number of apexes sizes their arrays
         HIP_TRY(s->pk_row.ensure((size_t)K)); HIP_TRY(s->pk_lo.ensure((size_t)K)); HIP_TRY(s->pk_hi.ensure((size_t)K));
         HIP_TRY(s->pk_sad.ensure((size_t)K + 1));
         if (K > 0) {
-            hipLaunchKernelGGL(refine_compact_kernel, dim3(nb), dim3(256), 0, c->stream, (const int32_t *)s->pk_flag.p,
-                               (const int64_t *)c->rf_pre.p, M, s->pk_row.p);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(flag_compact(c, s->pk_flag.p, M, s->pk_row.p));
             const unsigned ng = (unsigned)std::min<int64_t>(std::max<int64_t>(K - 1, 1), 1 << 20);
             hipLaunchKernelGGL(peak_saddle_kernel, dim3(ng), dim3(PEAK_THREADS), 0, c->stream, clr, (const int32_t *)s->pk_row.p, K, s->pk_sad.p);
             HIP_TRY(hipGetLastError());
@@ -7294,11 +7283,9 @@ int peaks_run(bmx_ctx *c, ChromSlot *s, const double *g, const double *clr, int6
             HIP_TRY(hipGetLastError());
         }
     }
-    HIP_TRY(hipEventRecord(c->pk_ev1, c->stream));
+    HIP_TRY(c->pk.end(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->pk_ev0, c->pk_ev1));
-    c->pk_ms = (double)ms;
+    HIP_TRY(c->pk.read());
     s->pk_M = M; s->pk_K = K;
     s->pk_have = true;
     s->pk_scan = false;
@@ -7314,7 +7301,7 @@ int bmx_ctx_peaks(bmx_ctx *c, double sep, double min_clr, double frac) {
     int rc = peaks_check("peaks", sep, min_clr, frac);
     if (rc) return rc;
     ChromSlot *s = c->cur;
-    if (!c->has_model || !s->has_tests || !s->timed) return fail(BMX_E_INVALID, "peaks: no scan results (scan the slot first)");
+    if (!c->has_model || !s->has_results()) return fail(BMX_E_INVALID, "peaks: no scan results (scan the slot first)");
     if (!s->tests_sorted) return fail(BMX_E_INVALID, "peaks: the slot's test positions are not non-decreasing");
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = peaks_run(c, s, s->test_gen.p, s->clr.p, s->M, sep, min_clr, frac))) return rc;
@@ -7360,19 +7347,14 @@ int bmx_ctx_fetch_peaks(bmx_ctx *c, int32_t *row, int32_t *lo, int32_t *hi, int3
     if (!K) return BMX_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (row) HIP_TRY(hipMemcpy(row, s->pk_row.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (lo) HIP_TRY(hipMemcpy(lo, s->pk_lo.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (hi) HIP_TRY(hipMemcpy(hi, s->pk_hi.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (saddle_lo) HIP_TRY(hipMemcpy(saddle_lo, s->pk_sad.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (saddle_hi) HIP_TRY(hipMemcpy(saddle_hi, s->pk_sad.p + 1, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(download(row, s->pk_row.p, K)); HIP_TRY(download(lo, s->pk_lo.p, K)); HIP_TRY(download(hi, s->pk_hi.p, K));
+    HIP_TRY(download(saddle_lo, s->pk_sad.p, K)); HIP_TRY(download(saddle_hi, s->pk_sad.p + 1, K));
     return BMX_OK;
 }
 
 int bmx_ctx_peaks_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
-    if (c->pk_ms < 0) return fail(BMX_E_STATE, "no peak call yet");
-    *ms = c->pk_ms;
-    return BMX_OK;
+    return c->pk.get(ms, "no peak call yet");
 }
 
 int bmx_ctx_refine_at_peaks(bmx_ctx *c, int32_t on) {

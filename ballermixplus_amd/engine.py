@@ -99,6 +99,24 @@ class Context:
         except Exception:
             pass
 
+    @staticmethod
+    def _key64(key):
+        return C.c_uint64(int(key) & ((1 << 64) - 1))
+
+    def _ms(self, fn):
+        """A call whose one output is a double: the *_ms getters, a replicate's maximum."""
+        ms = C.c_double()
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
+    def _points(self, A, x, abeta):
+        """One (A, x, abeta) per test site of the selected slot: f64[M] each, scalars broadcast."""
+        return tuple(_lib.f64(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.M,))) for v in (A, x, abeta))
+
+    def _sites_replaced(self):       # the library drops the slot's test sites with its sites (they were located in the old array)
+        self.M = 0
+        self._slot_M.pop(self.slot, None)
+
     def set_model(self, model, As):
         A = _lib.f64(As)
         self.model, self.nA = model, len(A)
@@ -110,8 +128,7 @@ class Context:
     def set_sites(self, genpos, rows):
         g, r = _lib.f64(genpos), _lib.i32(rows)
         self.N = len(g)
-        self.M = 0                       # the library drops the slot's test sites (they were located in the old array)
-        self._slot_M.pop(self.slot, None)
+        self._sites_replaced()
         _lib.check(self._L.bmx_ctx_set_sites(self._h, len(g), _lib.as_dp(g), _lib.as_ip(r)))
 
     def set_tests(self, test_gen, win_lo=None, win_hi=None):
@@ -185,9 +202,7 @@ class Context:
         _lib.check(self._L.bmx_ctx_sync(self._h))
 
     def last_scan_ms(self):
-        ms = C.c_double()
-        _lib.check(self._L.bmx_ctx_last_scan_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self._L.bmx_ctx_last_scan_ms)
 
     def fetch(self):
         M = self.M
@@ -227,7 +242,7 @@ class Context:
     def permute_rows(self, key, block=1):
         """Permute the selected slot's site rows on the device: row[i] = given_row[sigma(i)], sigma =
         null.block_permutation(N, key, block).  Always from the rows given to set_sites."""
-        _lib.check(self._L.bmx_ctx_permute_rows(self._h, C.c_uint64(int(key) & ((1 << 64) - 1)), int(block)))
+        _lib.check(self._L.bmx_ctx_permute_rows(self._h, self._key64(key), int(block)))
 
     def restore_rows(self):
         """Back to the rows given to set_sites."""
@@ -239,9 +254,7 @@ class Context:
 
     def null_accumulate(self):
         """After a replicate's scan: counts += (clr >= observed); returns the replicate's maximum CLR."""
-        m = C.c_double()
-        _lib.check(self._L.bmx_ctx_null_accumulate(self._h, C.byref(m)))
-        return m.value
+        return self._ms(self._L.bmx_ctx_null_accumulate)
 
     def null_fetch(self):
         """(exceedance counts i32[M], number of accumulated replicates)."""
@@ -272,10 +285,8 @@ class Context:
     def eval_points(self, A, x, abeta):
         """T (f64[M], -inf where the window is empty) and nSites (i32[M]) of every test site of the selected slot at the
         point (A[t], x[t], abeta[t]) -- the refinement's arithmetic (ballermixplus_amd/refine.py).  Scalars broadcast."""
-        M = self.M
-        A, x, abeta = (_lib.f64(np.broadcast_to(np.asarray(v, dtype=np.float64), (M,))) for v in (A, x, abeta))
-        T = np.empty(M, dtype=np.float64)
-        ns = np.empty(M, dtype=np.int32)
+        A, x, abeta = self._points(A, x, abeta)
+        T, ns = np.empty(self.M, dtype=np.float64), np.empty(self.M, dtype=np.int32)
         _lib.check(self._L.bmx_ctx_eval_points(self._h, _lib.as_dp(A), _lib.as_dp(x), _lib.as_dp(abeta), _lib.as_dp(T),
                                                _lib.as_ip(ns)))
         return T, ns
@@ -320,18 +331,16 @@ class Context:
         """T_w (f64[M], -inf where no site of the window has a positive weight) and the sum of the weights of the window's
         sites at that A (i64[M]) of every test site of the selected slot at the point (A[t], x[t], abeta[t]), under the
         block-bootstrap weights of (key, block) -- the bootstrap's arithmetic (ballermixplus_amd/boot.py).  Scalars broadcast."""
-        M = self.M
-        A, x, abeta = (_lib.f64(np.broadcast_to(np.asarray(v, dtype=np.float64), (M,))) for v in (A, x, abeta))
-        T = np.empty(M, dtype=np.float64)
-        ws = np.empty(M, dtype=np.int64)
-        _lib.check(self._L.bmx_ctx_eval_points_weighted(self._h, C.c_uint64(int(key) & ((1 << 64) - 1)), int(block), _lib.as_dp(A),
+        A, x, abeta = self._points(A, x, abeta)
+        T, ws = np.empty(self.M, dtype=np.float64), np.empty(self.M, dtype=np.int64)
+        _lib.check(self._L.bmx_ctx_eval_points_weighted(self._h, self._key64(key), int(block), _lib.as_dp(A),
                                                         _lib.as_dp(x), _lib.as_dp(abeta), _lib.as_dp(T), _lib.as_lp(ws)))
         return T, ws
 
     def boot(self, keys, block=1, min_clr=0.0):
         """Block bootstrap (ballermixplus_amd/boot.py) of the refined maxima of the selected slot's last refinement: one
         replicate per key (boot.replicate_key) for every window with a refined CLR >= min_clr."""
-        k = np.array([int(v) & ((1 << 64) - 1) for v in keys], dtype=np.uint64)
+        k = np.array([self._key64(v).value for v in keys], dtype=np.uint64)
         _lib.check(self._L.bmx_ctx_boot(self._h, k.ctypes.data_as(C.POINTER(C.c_uint64)), len(k), int(block), float(min_clr)))
 
     def fetch_boot(self):
@@ -356,10 +365,8 @@ class Context:
         (ballermixplus_amd/locate.py: np.repeat of positions and rows by boot.site_weights), built on the device; the slot is
         then as after set_sites of those arrays.  Returns the number of resampled sites (0: the slot has no sites)."""
         n = C.c_int64()
-        self.M = 0
-        self._slot_M.pop(self.slot, None)
-        _lib.check(self._L.bmx_ctx_resample_sites(self._h, int(src_slot), C.c_uint64(int(key) & ((1 << 64) - 1)), int(block),
-                                                  C.byref(n)))
+        self._sites_replaced()
+        _lib.check(self._L.bmx_ctx_resample_sites(self._h, int(src_slot), self._key64(key), int(block), C.byref(n)))
         self.N = n.value
         return n.value
 
@@ -402,18 +409,14 @@ class Context:
             raise ValueError('a flat list of centres and one weight per table row are needed')
         first, count = np.zeros(len(c), dtype=np.int32), np.zeros(len(c), dtype=np.int32)
         changed = C.c_int64()
-        self.M = 0
-        self._slot_M.pop(self.slot, None)
-        _lib.check(self._L.bmx_ctx_plant_sites(self._h, int(src_slot), C.c_uint64(int(key) & ((1 << 64) - 1)), len(c), _lib.as_dp(c),
-                                               int(iA), int(ix), int(ia), _lib.as_dp(w), _lib.as_ip(first), _lib.as_ip(count),
-                                               C.byref(changed)))
+        self._sites_replaced()
+        _lib.check(self._L.bmx_ctx_plant_sites(self._h, int(src_slot), self._key64(key), len(c), _lib.as_dp(c), int(iA), int(ix),
+                                               int(ia), _lib.as_dp(w), _lib.as_ip(first), _lib.as_ip(count), C.byref(changed)))
         return first, count, changed.value
 
     def plant_ms(self):
         """Device milliseconds of the context's last plant_sites() call."""
-        ms = C.c_double()
-        _lib.check(self._L.bmx_ctx_plant_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self._L.bmx_ctx_plant_ms)
 
     def fetch_at(self, tests):
         """(clr f64[n], lin i32[n], nsites i32[n]) of the selected slot's last scan at the listed test sites (any order, repeats
@@ -453,9 +456,7 @@ class Context:
 
     def peaks_ms(self):
         """Device milliseconds of the context's last peak call."""
-        ms = C.c_double()
-        _lib.check(self._L.bmx_ctx_peaks_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self._L.bmx_ctx_peaks_ms)
 
     def refine_at_peaks(self, on=True):
         """Later refine() calls take only the apexes of their slot's peaks() call on the same scan (min_clr still applies)."""
@@ -484,9 +485,7 @@ class Context:
 
     def surfaces_ms(self):
         """Device milliseconds of the kernels of the context's last surfaces() call."""
-        ms = C.c_double()
-        _lib.check(self._L.bmx_ctx_surfaces_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self._L.bmx_ctx_surfaces_ms)
 
     def fetch_lut(self):
         m = self.model
