@@ -3536,13 +3536,50 @@ __device__ __forceinline__ int64_t wave_first_true(int64_t a, int64_t b, F pred)
     return b;
 }
 
+__device__ const uint64_t BOOT_THR[20] = {     // floor(2^64 * Poisson(1).cdf(k)), k = 0..19 (boot.py THR)
+    6786177901268885274ull, 13572355802537770549ull, 16965444753172213186ull, 18096474403383694065ull, 18379231815936564285ull,
+    18435783298447138329ull, 18445208545532234003ull, 18446555009401533385ull, 18446723317385195808ull, 18446742018272269410ull,
+    18446743888360976771ull, 18446744058369041076ull, 18446744072536379768ull, 18446744073626175052ull, 18446744073704017573ull,
+    18446744073709207074ull, 18446744073709531418ull, 18446744073709550497ull, 18446744073709551557ull, 18446744073709551613ull};
+
+// w(key, b) of boot.py: the number of thresholds at or below the hash (ascending table: stop at the first one above it)
+__device__ __forceinline__ int boot_weight(uint64_t key, uint64_t b) {
+    const uint64_t h = bmx_mix64(key ^ bmx_mix64(b));
+    int w = 0;
+    while (w < 20 && h >= BOOT_THR[w]) ++w;
+    return w;
+}
+
+// The weight of a site in the sums of a round, carried along a thread's stride of REFINE_THREADS sites: start(i) at the thread's
+// first site, then one next() per site.  count_t holds a thread's total weight inside a cut.
+struct UnitWeight {                 // T: every site once (refine_kernel, support_kernel)
+    using count_t = int;
+    __device__ __forceinline__ void start(int64_t) {}
+    __device__ __forceinline__ int next() { return 1; }
+};
+
+struct BootWeight {                 // T_w: w_i = boot_weight(key, i / B) (boot_kernel)
+    using count_t = long long;
+    uint64_t key, B, qB, rB;        // qB, rB: REFINE_THREADS / B and REFINE_THREADS % B
+    uint64_t blk, rem;              // i / B and i % B, carried along with i: no division in the loop
+    __device__ __forceinline__ void start(int64_t i) { blk = (uint64_t)i / B; rem = (uint64_t)i % B; }
+    __device__ __forceinline__ int next() {
+        const int w = boot_weight(key, blk);
+        blk += qB; rem += rB;
+        if (rem >= B) { rem -= B; blk++; }
+        return w;
+    }
+};
+
 struct RefineState {
     double c[3], nat[3];            // the centre: coordinates (u, x, v) and natural values (A, x, alpha_beta)
     double c0[3], nat0[3];          // the start
     double h[3];
     double Tc;
-    int nsc, have_c, rounds, phase, cand;
-    int valid[REFINE_EVALS];
+    long long nsc;                  // sites (BootWeight: total weight) inside the cut of the centre's A
+    int have_c, rounds, phase, cand;
+    int valid[REFINE_EVALS];        // the evaluations of the last round laid out ...
+    double T[REFINE_EVALS];         // ... and their T where that round summed (for the caller's thread 0, after the round)
     double cc[REFINE_EVALS][3], cn[REFINE_EVALS][3];
     double Aev[3];                  // A of the centre, u-, u+
     int need_tab[REFINE_TABS];
@@ -3554,7 +3591,7 @@ struct RefineState {
     int nused, rv;
     double tg;
     double red[REFINE_WAVES][REFINE_EVALS];
-    int redn[REFINE_WAVES][3];
+    long long redn[REFINE_WAVES][3];
     int wtot[REFINE_WAVES];
 };
 
@@ -3562,207 +3599,259 @@ __device__ __forceinline__ double refine_nat(const RefineState &S, int k, double
     return v == S.c0[k] ? S.nat0[k] : (k == 1 ? v : exp(v));
 }
 
+// A workgroup's workspace, in LDS or in its slab: [REFINE_TABS][rows] f64 tables, [rows] i32 row list, [rows] u8 row map
+struct CompassWs {
+    double *tab; int32_t *list; uint8_t *map;
+};
+
+__device__ __forceinline__ CompassWs compass_ws(const RefineParams &P, double *lds_ws) {
+    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
+    CompassWs W;
+    W.tab = (double *)ws;
+    W.list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
+    W.map = (uint8_t *)(W.list + P.rows);
+    return W;
+}
+
+// Thread 0, a start: point t of a point evaluation (no steps: nothing to search) ...
+__device__ __forceinline__ void compass_start_point(const RefineParams &P, RefineState &S, int64_t t) {
+    S.nat0[0] = P.pA[t]; S.nat0[1] = P.px[t]; S.nat0[2] = P.pab[t];
+    S.c0[0] = log(P.pA[t]); S.c0[1] = P.px[t]; S.c0[2] = log(P.pab[t]);
+    S.h[0] = S.h[1] = S.h[2] = 0.0;
+}
+
+// ... or the refined point (rA, rx, rab)[t] of window t, with the grid start's own coordinate where a value is the grid's; the
+// grid start's steps go to h0
+__device__ __forceinline__ void compass_start_refined(const RefineParams &P, RefineState &S, int64_t t, const double *rA,
+                                                      const double *rx, const double *rab, double *h0) {
+    const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
+    const double g0[3] = {P.gA[iA], P.gx[ix], P.gab[ia]}, gc[3] = {P.cu[iA], P.gx[ix], P.cv[ia]};
+    S.nat0[0] = rA[t]; S.nat0[1] = rx[t]; S.nat0[2] = rab[t];
+    for (int k = 0; k < 3; ++k) S.c0[k] = S.nat0[k] == g0[k] ? gc[k] : (k == 1 ? S.nat0[k] : log(S.nat0[k]));
+    h0[0] = P.h0u[iA]; h0[1] = P.h0x[ix]; h0[2] = P.h0v[ia];
+}
+
+// All threads, once per window, after thread 0 set the start (S.c0, S.nat0, S.h): the centre at the start, nothing evaluated
+// or built, and the window -- its bounds and the first site at or right of the test position
+__device__ __forceinline__ void compass_begin(const RefineParams &P, RefineState &S, int64_t t) {
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 3; ++k) { S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k]; }
+        S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
+        S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
+        S.tg = P.test_gen[t];
+        S.wlo = max(P.win_lo[t], (int64_t)0);
+        S.whi = min(P.win_hi[t], P.N - 1);
+    }
+    __syncthreads();
+    if (threadIdx.x / WAVE == 0) {
+        const double tg = S.tg;
+        const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
+        if (threadIdx.x % WAVE == 0) S.ctr = ctr;
+    }
+}
+
+// One round of the compass search (steps 1-4 above) over the free coordinates fr[3], with the site weights wt: the one text of
+// refine_kernel, support_kernel and boot_kernel.  All threads of the workgroup call it; false: the search has ended (converged
+// or out of rounds, nothing left to evaluate) at the centre S.c / S.nat with S.Tc and S.nsc.  After a round thread 0 finds in
+// S.valid[] what it evaluated and in S.T[] the values, until it lays out the next one.
+template <class W>
+__device__ __forceinline__ bool compass_round(const RefineParams &P, RefineState &S, const int *fr, const CompassWs &ws, W wt) {
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    // ---- 1. the round's candidates (thread 0)
+    if (tid == 0) {
+        for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
+        S.valid[0] = !S.have_c;
+        bool conv = true;
+        for (int k = 0; k < 3; ++k)
+            if (fr[k] && !(S.h[k] < P.tol[k])) conv = false;
+        S.cand = S.rounds < P.max_rounds && !conv;
+        if (S.cand) {
+            for (int d = 0; d < 6; ++d) {
+                const int k = d >> 1;
+                if (!fr[k]) continue;
+                const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
+                if (v == S.c[k]) continue;
+                S.valid[d + 1] = 1;
+                for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
+                S.cc[d + 1][k] = v;
+                S.cn[d + 1][k] = refine_nat(S, k, v);
+            }
+        }
+        bool any = false;
+        for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
+        S.phase = any ? 1 : S.cand ? 2 : 0;
+        S.Aev[0] = S.nat[0];
+        S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
+        S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
+        S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
+        S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
+        for (int q = 1; q < REFINE_TABS; ++q) {
+            S.need_tab[q] = S.valid[q + 2];
+            S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
+            S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
+        }
+    }
+    __syncthreads();
+    const int phase = S.phase;
+    if (phase == 0) return false;
+    if (phase == 2) {       // every candidate clamps onto the centre: halve
+        if (tid == 0) {
+            for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+            S.rounds++;
+        }
+        __syncthreads();
+        return true;
+    }
+    const double tg = S.tg;
+    // ---- the site range of the smallest A of the round, and the rows it references
+    double Amin = S.Aev[0];
+    if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
+    if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
+    if (Amin != S.rangeA) {
+        if (wave == 0) {
+            const double zc = P.zcut;
+            const int64_t ctr = S.ctr;
+            const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
+            const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
+            if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
+        }
+        for (int r = tid; r < P.rows; r += REFINE_THREADS) ws.map[r] = 0;
+        __syncthreads();
+        for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) ws.map[P.row[i]] = 1;
+        __syncthreads();
+        int base = 0;
+        for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
+            const int r = r0 + tid;
+            const bool on = r < P.rows && ws.map[r];
+            const unsigned long long m = __ballot(on);
+            if (lane == 0) S.wtot[wave] = __popcll(m);
+            __syncthreads();
+            int off = base;
+            for (int q = 0; q < wave; ++q) off += S.wtot[q];
+            if (on) ws.list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+            for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
+            __syncthreads();
+        }
+        if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
+        __syncthreads();
+    }
+    // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
+    {
+        int qmask = 0, nq = 0;          // the tables to build, as a bit set (an indexed array goes to scratch in boot_kernel)
+        const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
+        for (int q = 0; q < REFINE_TABS; ++q)
+            if (S.need_tab[q] && !(q == 0 && keep0)) { qmask |= 1 << q; nq++; }
+        const int nu = S.nused;
+        for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
+            int m = qmask;
+            for (int j = it / nu; j > 0; --j) m &= m - 1;
+            const int q = __ffs(m) - 1, r = ws.list[it % nu];
+            ws.tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
+        }
+        __syncthreads();
+        if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
+    }
+    // ---- 3. the (weighted) site sums, aligned to the site index; a site of weight 0 skips its loads and its exp / log1p
+    double acc[REFINE_EVALS];
+    typename W::count_t ns[3] = {0, 0, 0};
+    for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
+    {
+        int vmask = 0;
+        for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
+        const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
+        const int64_t lo = S.rlo, hi = S.rhi;
+        int64_t i = lo - (lo % REFINE_THREADS) + tid;
+        if (i < lo) i += REFINE_THREADS;
+        if (i <= hi) wt.start(i);
+        for (; i <= hi; i += REFINE_THREADS) {
+            const int wi = wt.next();
+            if (wi == 0) continue;
+            const double wd = (double)wi;
+            const double gi = P.genpos[i];
+            const int r = P.row[i];
+            const double d = fabs(gi - tg);
+            const bool same = gi == tg;
+            const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
+            const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
+            const double a0 = exp(-z0);
+            if (in0) ns[0] += wi;
+            if (in1) ns[1] += wi;
+            if (in2) ns[2] += wi;
+            if (vmask & 1) { const double v = log1p(a0 * ws.tab[r]); if (in0) acc[0] += wd * v; }
+            if (vmask & 2) { const double v = log1p(exp(-z1) * ws.tab[r]); if (in1) acc[1] += wd * v; }
+            if (vmask & 4) { const double v = log1p(exp(-z2) * ws.tab[r]); if (in2) acc[2] += wd * v; }
+            for (int q = 1; q < REFINE_TABS; ++q)
+                if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * ws.tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += wd * v; }
+        }
+    }
+    // ---- 4. fixed-order reduction, the decision
+    for (int off = 1; off < WAVE; off <<= 1) {
+        for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
+        for (int k = 0; k < 3; ++k) ns[k] += __shfl_xor(ns[k], off);
+    }
+    if (lane == 0) {
+        for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
+        for (int k = 0; k < 3; ++k) S.redn[wave][k] = ns[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long nk[3];
+        for (int k = 0; k < 3; ++k) nk[k] = (S.redn[0][k] + S.redn[1][k]) + (S.redn[2][k] + S.redn[3][k]);
+        for (int e = 0; e < REFINE_EVALS; ++e) {
+            const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
+            const long long n = nk[e == 1 ? 1 : e == 2 ? 2 : 0];
+            const double v = 2.0 * s;
+            S.T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
+        }
+        if (S.valid[0]) { S.Tc = S.T[0]; S.nsc = nk[0]; S.have_c = 1; }
+        if (S.cand) {
+            double best = S.Tc;
+            int bi = -1;
+            for (int e = 1; e < REFINE_EVALS; ++e)
+                if (S.valid[e] && S.T[e] > best) { best = S.T[e]; bi = e; }
+            if (bi >= 0) {
+                for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
+                S.Tc = best;
+                S.nsc = nk[bi == 1 ? 1 : bi == 2 ? 2 : 0];
+            } else {
+                for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
+            }
+            S.rounds++;
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
 __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(RefineParams P) {
     extern __shared__ __attribute__((aligned(16))) double lds_ws[];
     __shared__ RefineState S;
-    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
-    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
-    double *tab = (double *)ws;                                              // [REFINE_TABS][rows]
-    int32_t *list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
-    uint8_t *map = (uint8_t *)(list + P.rows);
+    const int tid = threadIdx.x;
+    const CompassWs ws = compass_ws(P, lds_ws);
     const int64_t count = P.list ? *P.count : P.M;
     for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
         const int64_t t = P.list ? (int64_t)P.list[w] : w;
         if (tid == 0) {
-            if (P.list) {
+            if (P.list) {           // the scan's argmax, with the host's coordinates and steps of its grid values
                 const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
                 S.nat0[0] = P.gA[iA]; S.nat0[1] = P.gx[ix]; S.nat0[2] = P.gab[ia];
                 S.c0[0] = P.cu[iA]; S.c0[1] = P.gx[ix]; S.c0[2] = P.cv[ia];
                 S.h[0] = P.h0u[iA]; S.h[1] = P.h0x[ix]; S.h[2] = P.h0v[ia];
             } else {
-                S.nat0[0] = P.pA[t]; S.nat0[1] = P.px[t]; S.nat0[2] = P.pab[t];
-                S.c0[0] = log(P.pA[t]); S.c0[1] = P.px[t]; S.c0[2] = log(P.pab[t]);
-                S.h[0] = S.h[1] = S.h[2] = 0.0;
+                compass_start_point(P, S, t);
             }
-            for (int k = 0; k < 3; ++k) { S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k]; }
-            S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
-            S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
-            S.tg = P.test_gen[t];
-            S.wlo = max(P.win_lo[t], (int64_t)0);
-            S.whi = min(P.win_hi[t], P.N - 1);
         }
-        __syncthreads();
-        const double tg = S.tg;
-        if (wave == 0) {            // first site at or right of the test position
-            const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
-            if (lane == 0) S.ctr = ctr;
-        }
-        for (;;) {
-            // ---- 1. the round's candidates (thread 0)
-            if (tid == 0) {
-                for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
-                S.valid[0] = !S.have_c;
-                bool conv = true;
-                for (int k = 0; k < 3; ++k)
-                    if (P.fr[k] && !(S.h[k] < P.tol[k])) conv = false;
-                S.cand = S.rounds < P.max_rounds && !conv;
-                if (S.cand) {
-                    for (int d = 0; d < 6; ++d) {
-                        const int k = d >> 1;
-                        if (!P.fr[k]) continue;
-                        const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
-                        if (v == S.c[k]) continue;
-                        S.valid[d + 1] = 1;
-                        for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
-                        S.cc[d + 1][k] = v;
-                        S.cn[d + 1][k] = refine_nat(S, k, v);
-                    }
-                }
-                bool any = false;
-                for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
-                S.phase = any ? 1 : S.cand ? 2 : 0;
-                S.Aev[0] = S.nat[0];
-                S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
-                S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
-                S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
-                S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
-                for (int q = 1; q < REFINE_TABS; ++q) {
-                    S.need_tab[q] = S.valid[q + 2];
-                    S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
-                    S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
-                }
-            }
-            __syncthreads();
-            const int phase = S.phase;
-            if (phase == 0) break;
-            if (phase == 2) {       // every candidate clamps onto the centre: halve
-                if (tid == 0) {
-                    for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
-                    S.rounds++;
-                }
-                __syncthreads();
-                continue;
-            }
-            // ---- the site range of the smallest A of the round, and the rows it references
-            double Amin = S.Aev[0];
-            if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
-            if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
-            if (Amin != S.rangeA) {
-                if (wave == 0) {
-                    const double zc = P.zcut;
-                    const int64_t ctr = S.ctr;
-                    const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
-                    const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
-                    if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
-                }
-                for (int r = tid; r < P.rows; r += REFINE_THREADS) map[r] = 0;
-                __syncthreads();
-                for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) map[P.row[i]] = 1;
-                __syncthreads();
-                int base = 0;
-                for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
-                    const int r = r0 + tid;
-                    const bool on = r < P.rows && map[r];
-                    const unsigned long long m = __ballot(on);
-                    if (lane == 0) S.wtot[wave] = __popcll(m);
-                    __syncthreads();
-                    int off = base;
-                    for (int q = 0; q < wave; ++q) off += S.wtot[q];
-                    if (on) list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
-                    for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
-                    __syncthreads();
-                }
-                if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
-                __syncthreads();
-            }
-            // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
-            {
-                int qs[REFINE_TABS], nq = 0;
-                const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
-                for (int q = 0; q < REFINE_TABS; ++q)
-                    if (S.need_tab[q] && !(q == 0 && keep0)) qs[nq++] = q;
-                const int nu = S.nused;
-                for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
-                    const int q = qs[it / nu], r = list[it % nu];
-                    tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
-                }
-                __syncthreads();
-                if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
-            }
-            // ---- 3. the site sums, aligned to the site index
-            double acc[REFINE_EVALS];
-            int ns[3] = {0, 0, 0};
-            for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
-            {
-                int vmask = 0;
-                for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
-                const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
-                const int64_t lo = S.rlo, hi = S.rhi;
-                int64_t i = lo - (lo % REFINE_THREADS) + tid;
-                if (i < lo) i += REFINE_THREADS;
-                for (; i <= hi; i += REFINE_THREADS) {
-                    const double gi = P.genpos[i];
-                    const int r = P.row[i];
-                    const double d = fabs(gi - tg);
-                    const bool same = gi == tg;
-                    const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
-                    const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
-                    const double a0 = exp(-z0);
-                    ns[0] += in0; ns[1] += in1; ns[2] += in2;
-                    if (vmask & 1) { const double v = log1p(a0 * tab[r]); if (in0) acc[0] += v; }
-                    if (vmask & 2) { const double v = log1p(exp(-z1) * tab[r]); if (in1) acc[1] += v; }
-                    if (vmask & 4) { const double v = log1p(exp(-z2) * tab[r]); if (in2) acc[2] += v; }
-                    for (int q = 1; q < REFINE_TABS; ++q)
-                        if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += v; }
-                }
-            }
-            // ---- 4. fixed-order reduction, the decision
-            for (int off = 1; off < WAVE; off <<= 1) {
-                for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
-                for (int k = 0; k < 3; ++k) ns[k] += __shfl_xor(ns[k], off);
-            }
-            if (lane == 0) {
-                for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
-                for (int k = 0; k < 3; ++k) S.redn[wave][k] = ns[k];
-            }
-            __syncthreads();
-            if (tid == 0) {
-                double T[REFINE_EVALS];
-                int nk[3];
-                for (int k = 0; k < 3; ++k) nk[k] = (S.redn[0][k] + S.redn[1][k]) + (S.redn[2][k] + S.redn[3][k]);
-                for (int e = 0; e < REFINE_EVALS; ++e) {
-                    const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
-                    const int n = nk[e == 1 ? 1 : e == 2 ? 2 : 0];
-                    const double v = 2.0 * s;
-                    T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
-                }
-                if (S.valid[0]) { S.Tc = T[0]; S.nsc = nk[0]; S.have_c = 1; }
-                if (S.cand) {
-                    double best = S.Tc;
-                    int bi = -1;
-                    for (int e = 1; e < REFINE_EVALS; ++e)
-                        if (S.valid[e] && T[e] > best) { best = T[e]; bi = e; }
-                    if (bi >= 0) {
-                        for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
-                        S.Tc = best;
-                        S.nsc = nk[bi == 1 ? 1 : bi == 2 ? 2 : 0];
-                    } else {
-                        for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
-                    }
-                    S.rounds++;
-                }
-            }
-            __syncthreads();
-        }
+        compass_begin(P, S, t);
+        while (compass_round(P, S, P.fr, ws, UnitWeight())) {}
         if (tid == 0) {
             if (P.list) {
                 if (S.Tc > P.clr[t]) {
-                    P.o_clr[t] = S.Tc; P.o_A[t] = S.nat[0]; P.o_x[t] = S.nat[1]; P.o_ab[t] = S.nat[2]; P.o_ns[t] = S.nsc;
+                    P.o_clr[t] = S.Tc; P.o_A[t] = S.nat[0]; P.o_x[t] = S.nat[1]; P.o_ab[t] = S.nat[2]; P.o_ns[t] = (int32_t)S.nsc;
                 }
                 P.o_rounds[t] = S.rounds;
             } else {
                 P.o_clr[t] = S.Tc;
-                P.o_ns[t] = S.nsc;
+                P.o_ns[t] = (int32_t)S.nsc;
             }
         }
         __syncthreads();
@@ -3810,11 +3899,12 @@ __global__ void refine_compact_kernel(const int32_t *flag, const int64_t *pre, i
 // Profile-likelihood support intervals around each refined maximum (bmx_ctx_support; the definition is
 // ballermixplus_amd/support.py).  One task per (window, free coordinate k, side): task id (t * 3 + k) * 2 + side, side 0 the
 // lower end.  One workgroup of REFINE_THREADS per task, grid-striding over a device-compacted task list, so the six tasks of a
-// window run in parallel.  A task is a sequence of nuisance searches -- refine_kernel's compass rounds with coordinate k held
-// (steps 1-4 of the refinement above, operation for operation: the same candidate layout, row list, R tables, site-aligned
-// sums and fixed-order reduction, so a witness's T is bmx_ctx_eval_points' T at its natural values bit for bit).  Between the
-// searches thread 0 runs the walk / bisection of support.py: search 0 evaluates T* at the centre (no free coordinate), then
-// each search is one profile P_k(t).  No atomics: a task's result is a function of its window alone.
+// window run in parallel.  A task is a sequence of nuisance searches -- compass_round, the refinement's own round, over the
+// task's free coordinates U.fr (coordinate k held), so a witness's T is bmx_ctx_eval_points' T at its natural values bit for
+// bit.  After each round thread 0 folds the round's evaluations into T_best.  Between the searches it runs the walk /
+// bisection of support.py: search 0 evaluates T* at the centre (no free coordinate), then each search is one profile P_k(t),
+// started at the refined point as compass_start_refined lays it out.  No atomics: a task's result is a function of its
+// window alone.
 constexpr int SUPPORT_TASKS = 6;                // per window: (k, side)
 constexpr int SUPPORT_MAX_WALK = 64;
 constexpr int SUPPORT_ND = 11;                  // doubles per task: end, witness[3], witness T, outside[3], outside T, T*, T_best
@@ -3839,11 +3929,8 @@ __global__ __launch_bounds__(REFINE_THREADS) void support_kernel(SupportParams Q
     __shared__ RefineState S;
     __shared__ SupportTask U;
     const RefineParams &P = Q.P;
-    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
-    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
-    double *tab = (double *)ws;                                              // [REFINE_TABS][rows]
-    int32_t *list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
-    uint8_t *map = (uint8_t *)(list + P.rows);
+    const int tid = threadIdx.x;
+    const CompassWs ws = compass_ws(P, lds_ws);
     const int64_t count = *Q.count;
     for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
         const int64_t task = Q.list[w];
@@ -3851,236 +3938,70 @@ __global__ __launch_bounds__(REFINE_THREADS) void support_kernel(SupportParams Q
         if (tid == 0) {
             U.k = (int)(task % SUPPORT_TASKS) / 2;
             U.side = (int)(task % 2);
-            const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
-            const double g0[3] = {P.gA[iA], P.gx[ix], P.gab[ia]}, gc[3] = {P.cu[iA], P.gx[ix], P.cv[ia]};
-            S.nat0[0] = Q.rA[t]; S.nat0[1] = Q.rx[t]; S.nat0[2] = Q.rab[t];
+            compass_start_refined(P, S, t, Q.rA, Q.rx, Q.rab, U.h0);
             for (int k = 0; k < 3; ++k) {
-                S.c0[k] = S.nat0[k] == g0[k] ? gc[k] : (k == 1 ? S.nat0[k] : log(S.nat0[k]));
-                S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k];
                 S.h[k] = 0.0;
                 U.fr[k] = 0;                // search 0: T* at the centre
             }
-            U.h0[0] = P.h0u[iA]; U.h0[1] = P.h0x[ix]; U.h0[2] = P.h0v[ia];
             U.d = U.h0[U.k];
             U.stage = 0; U.walk = 0; U.censored = 0; U.evals = 0; U.rounds = 0; U.done = 0;
             U.tbest = -INFINITY;
-            S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
-            S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
-            S.tg = P.test_gen[t];
-            S.wlo = max(P.win_lo[t], (int64_t)0);
-            S.whi = min(P.win_hi[t], P.N - 1);
         }
-        __syncthreads();
-        const double tg = S.tg;
-        if (wave == 0) {            // first site at or right of the test position
-            const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
-            if (lane == 0) S.ctr = ctr;
-        }
+        compass_begin(P, S, t);
         for (;;) {
-            // ---- 1. the round's candidates (thread 0): refine_kernel's, over the task's free coordinates U.fr
-            if (tid == 0) {
-                for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
-                S.valid[0] = !S.have_c;
-                bool conv = true;
-                for (int k = 0; k < 3; ++k)
-                    if (U.fr[k] && !(S.h[k] < P.tol[k])) conv = false;
-                S.cand = S.rounds < P.max_rounds && !conv;
-                if (S.cand) {
-                    for (int d = 0; d < 6; ++d) {
-                        const int k = d >> 1;
-                        if (!U.fr[k]) continue;
-                        const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
-                        if (v == S.c[k]) continue;
-                        S.valid[d + 1] = 1;
-                        for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
-                        S.cc[d + 1][k] = v;
-                        S.cn[d + 1][k] = refine_nat(S, k, v);
-                    }
-                }
-                bool any = false;
-                for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
-                S.phase = any ? 1 : S.cand ? 2 : 0;
-                S.Aev[0] = S.nat[0];
-                S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
-                S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
-                S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
-                S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
-                for (int q = 1; q < REFINE_TABS; ++q) {
-                    S.need_tab[q] = S.valid[q + 2];
-                    S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
-                    S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
-                }
+            if (compass_round(P, S, U.fr, ws, UnitWeight())) {
+                if (tid == 0)
+                    for (int e = 0; e < REFINE_EVALS; ++e)
+                        if (S.valid[e] && S.T[e] > U.tbest) U.tbest = S.T[e];
+                continue;
             }
-            __syncthreads();
-            const int phase = S.phase;
-            if (phase == 0) {
-                // ---- the search has ended: P = S.Tc at S.c.  Walk / bisection (support.py), then the next search or the end
-                if (tid == 0) {
-                    const int k = U.k;
-                    const double Tr = S.Tc;
-                    bool bisect = false;
-                    if (U.stage == 0) {
-                        U.Tstar = Tr; U.L = Tr - Q.drop;
+            // ---- the search has ended: P = S.Tc at S.c.  Walk / bisection (support.py), then the next search or the end
+            if (tid == 0) {
+                const int k = U.k;
+                const double Tr = S.Tc;
+                bool bisect = false;
+                U.rounds += S.rounds;
+                if (U.stage == 0) {
+                    U.Tstar = Tr; U.L = Tr - Q.drop;
+                    for (int q = 0; q < 3; ++q) { U.in_c[q] = S.c[q]; U.in_n[q] = S.nat[q]; }
+                    U.in_T = Tr;
+                    U.stage = 1;
+                } else {
+                    U.evals++;
+                    const bool inside = Tr >= U.L;
+                    if (inside) {
                         for (int q = 0; q < 3; ++q) { U.in_c[q] = S.c[q]; U.in_n[q] = S.nat[q]; }
                         U.in_T = Tr;
-                        U.stage = 1;
+                        if (U.stage == 1) U.d *= 2.0;
                     } else {
-                        U.evals++;
-                        const bool inside = Tr >= U.L;
-                        if (inside) {
-                            for (int q = 0; q < 3; ++q) { U.in_c[q] = S.c[q]; U.in_n[q] = S.nat[q]; }
-                            U.in_T = Tr;
-                            if (U.stage == 1) U.d *= 2.0;
-                        } else {
-                            for (int q = 0; q < 3; ++q) { U.out_c[q] = S.c[q]; U.out_n[q] = S.nat[q]; }
-                            U.out_T = Tr;
-                            U.stage = 2;
-                        }
-                        bisect = U.stage == 2;
+                        for (int q = 0; q < 3; ++q) { U.out_c[q] = S.c[q]; U.out_n[q] = S.nat[q]; }
+                        U.out_T = Tr;
+                        U.stage = 2;
                     }
-                    double v = 0.0;
-                    if (!bisect) {
-                        v = min(max(U.in_c[k] + (U.side ? U.d : -U.d), P.lo[k]), P.hi[k]);
-                        if (U.walk == SUPPORT_MAX_WALK || v == U.in_c[k]) { U.censored = 1; U.done = 1; }
-                        U.walk++;
-                    } else {
-                        if (!(fabs(U.out_c[k] - U.in_c[k]) >= Q.end_tol[k])) U.done = 1;
-                        v = U.in_c[k] + 0.5 * (U.out_c[k] - U.in_c[k]);
+                    bisect = U.stage == 2;
+                }
+                double v = 0.0;
+                if (!bisect) {
+                    v = min(max(U.in_c[k] + (U.side ? U.d : -U.d), P.lo[k]), P.hi[k]);
+                    if (U.walk == SUPPORT_MAX_WALK || v == U.in_c[k]) { U.censored = 1; U.done = 1; }
+                    U.walk++;
+                } else {
+                    if (!(fabs(U.out_c[k] - U.in_c[k]) >= Q.end_tol[k])) U.done = 1;
+                    v = U.in_c[k] + 0.5 * (U.out_c[k] - U.in_c[k]);
+                }
+                if (!U.done) {          // P_k(v), warm-started from the inside point with the grid-start steps
+                    for (int q = 0; q < 3; ++q) {
+                        S.c[q] = U.in_c[q]; S.nat[q] = U.in_n[q];
+                        S.h[q] = U.h0[q];
+                        U.fr[q] = P.fr[q] && q != k;
                     }
-                    if (!U.done) {          // P_k(v), warm-started from the inside point with the grid-start steps
-                        for (int q = 0; q < 3; ++q) {
-                            S.c[q] = U.in_c[q]; S.nat[q] = U.in_n[q];
-                            S.h[q] = U.h0[q];
-                            U.fr[q] = P.fr[q] && q != k;
-                        }
-                        S.c[k] = v;
-                        S.nat[k] = refine_nat(S, k, v);
-                        S.Tc = -INFINITY; S.have_c = 0; S.rounds = 0;
-                    }
-                }
-                __syncthreads();
-                if (U.done) break;
-                continue;
-            }
-            if (phase == 2) {       // every candidate clamps onto the centre: halve
-                if (tid == 0) {
-                    for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
-                    S.rounds++; U.rounds++;
-                }
-                __syncthreads();
-                continue;
-            }
-            // ---- the site range of the smallest A of the round, and the rows it references
-            double Amin = S.Aev[0];
-            if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
-            if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
-            if (Amin != S.rangeA) {
-                if (wave == 0) {
-                    const double zc = P.zcut;
-                    const int64_t ctr = S.ctr;
-                    const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
-                    const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
-                    if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
-                }
-                for (int r = tid; r < P.rows; r += REFINE_THREADS) map[r] = 0;
-                __syncthreads();
-                for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) map[P.row[i]] = 1;
-                __syncthreads();
-                int base = 0;
-                for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
-                    const int r = r0 + tid;
-                    const bool on = r < P.rows && map[r];
-                    const unsigned long long m = __ballot(on);
-                    if (lane == 0) S.wtot[wave] = __popcll(m);
-                    __syncthreads();
-                    int off = base;
-                    for (int q = 0; q < wave; ++q) off += S.wtot[q];
-                    if (on) list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
-                    for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
-                    __syncthreads();
-                }
-                if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
-                __syncthreads();
-            }
-            // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
-            {
-                int qs[REFINE_TABS], nq = 0;
-                const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
-                for (int q = 0; q < REFINE_TABS; ++q)
-                    if (S.need_tab[q] && !(q == 0 && keep0)) qs[nq++] = q;
-                const int nu = S.nused;
-                for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
-                    const int q = qs[it / nu], r = list[it % nu];
-                    tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
-                }
-                __syncthreads();
-                if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
-            }
-            // ---- 3. the site sums, aligned to the site index
-            double acc[REFINE_EVALS];
-            int ns[3] = {0, 0, 0};
-            for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
-            {
-                int vmask = 0;
-                for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
-                const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
-                const int64_t lo = S.rlo, hi = S.rhi;
-                int64_t i = lo - (lo % REFINE_THREADS) + tid;
-                if (i < lo) i += REFINE_THREADS;
-                for (; i <= hi; i += REFINE_THREADS) {
-                    const double gi = P.genpos[i];
-                    const int r = P.row[i];
-                    const double d = fabs(gi - tg);
-                    const bool same = gi == tg;
-                    const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
-                    const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
-                    const double a0 = exp(-z0);
-                    ns[0] += in0; ns[1] += in1; ns[2] += in2;
-                    if (vmask & 1) { const double v = log1p(a0 * tab[r]); if (in0) acc[0] += v; }
-                    if (vmask & 2) { const double v = log1p(exp(-z1) * tab[r]); if (in1) acc[1] += v; }
-                    if (vmask & 4) { const double v = log1p(exp(-z2) * tab[r]); if (in2) acc[2] += v; }
-                    for (int q = 1; q < REFINE_TABS; ++q)
-                        if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += v; }
-                }
-            }
-            // ---- 4. fixed-order reduction, the decision
-            for (int off = 1; off < WAVE; off <<= 1) {
-                for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
-                for (int k = 0; k < 3; ++k) ns[k] += __shfl_xor(ns[k], off);
-            }
-            if (lane == 0) {
-                for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
-                for (int k = 0; k < 3; ++k) S.redn[wave][k] = ns[k];
-            }
-            __syncthreads();
-            if (tid == 0) {
-                double T[REFINE_EVALS];
-                int nk[3];
-                for (int k = 0; k < 3; ++k) nk[k] = (S.redn[0][k] + S.redn[1][k]) + (S.redn[2][k] + S.redn[3][k]);
-                for (int e = 0; e < REFINE_EVALS; ++e) {
-                    const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
-                    const int n = nk[e == 1 ? 1 : e == 2 ? 2 : 0];
-                    const double v = 2.0 * s;
-                    T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
-                    if (S.valid[e] && T[e] > U.tbest) U.tbest = T[e];
-                }
-                if (S.valid[0]) { S.Tc = T[0]; S.nsc = nk[0]; S.have_c = 1; }
-                if (S.cand) {
-                    double best = S.Tc;
-                    int bi = -1;
-                    for (int e = 1; e < REFINE_EVALS; ++e)
-                        if (S.valid[e] && T[e] > best) { best = T[e]; bi = e; }
-                    if (bi >= 0) {
-                        for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
-                        S.Tc = best;
-                        S.nsc = nk[bi == 1 ? 1 : bi == 2 ? 2 : 0];
-                    } else {
-                        for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
-                    }
-                    S.rounds++; U.rounds++;
+                    S.c[k] = v;
+                    S.nat[k] = refine_nat(S, k, v);
+                    S.Tc = -INFINITY; S.have_c = 0; S.rounds = 0;
                 }
             }
             __syncthreads();
+            if (U.done) break;
         }
         if (tid == 0) {
             double *od = Q.o_d + (size_t)task * SUPPORT_ND;
@@ -4124,29 +4045,16 @@ __global__ void support_init_kernel(SupportInitParams Q) {
 // Block bootstrap of each refined maximum (bmx_ctx_boot / bmx_ctx_eval_points_weighted; the definition is
 // ballermixplus_amd/boot.py).  One task per (selected window, replicate), window-major: task q * R + r is replicate r of the
 // q-th selected window, so the R tasks of a window -- the same site range, the same first-round tables -- are neighbours in
-// dispatch order.  One workgroup of REFINE_THREADS per task, grid-striding over the tasks.  A task is refine_kernel's compass
-// search (steps 1-4 of the refinement, the same candidate layout, row list, R tables, site-aligned sums and fixed-order
-// reduction) from the refined point, with support_kernel's centre and the grid start's steps, on
+// dispatch order.  One workgroup of REFINE_THREADS per task, grid-striding over the tasks.  A task is one compass search --
+// compass_round, the refinement's own round, with the weights of BootWeight -- from the refined point
+// (compass_start_refined: support_kernel's centre, the grid start's steps), on
 //     T_w = 2 * sum_i w_i log1p(alpha_i R_i),   w_i = boot_weight(key_r, i / B)
 // over the sites of T with w_i > 0.  The weight is computed in the loop: the block index advances with the site index
 // (i += REFINE_THREADS: b += REFINE_THREADS / B, carrying the remainder) so the loop has no division, and a site of weight
 // 0 skips its exp / log1p (a wave skips them where its 64 consecutive sites all have weight 0: whole blocks when B >= 64).
-// In place of nSites the sums carry the total weight of the sites inside each A's cut: T_w is -inf when it is 0.
+// In place of nSites the sums carry the total weight of the sites inside each A's cut (S.nsc): T_w is -inf when it is 0.
+// After a round thread 0 keeps T_w of the start (T_centre) where that round evaluated it.
 // No atomics: a task's result is a function of its window and its key alone.
-__device__ const uint64_t BOOT_THR[20] = {     // floor(2^64 * Poisson(1).cdf(k)), k = 0..19 (boot.py THR)
-    6786177901268885274ull, 13572355802537770549ull, 16965444753172213186ull, 18096474403383694065ull, 18379231815936564285ull,
-    18435783298447138329ull, 18445208545532234003ull, 18446555009401533385ull, 18446723317385195808ull, 18446742018272269410ull,
-    18446743888360976771ull, 18446744058369041076ull, 18446744072536379768ull, 18446744073626175052ull, 18446744073704017573ull,
-    18446744073709207074ull, 18446744073709531418ull, 18446744073709550497ull, 18446744073709551557ull, 18446744073709551613ull};
-
-// w(key, b) of boot.py: the number of thresholds at or below the hash (ascending table: stop at the first one above it)
-__device__ __forceinline__ int boot_weight(uint64_t key, uint64_t b) {
-    const uint64_t h = bmx_mix64(key ^ bmx_mix64(b));
-    int w = 0;
-    while (w < 20 && h >= BOOT_THR[w]) ++w;
-    return w;
-}
-
 struct BootParams {
     RefineParams P;                             // the model, sites, windows and workspace as refine_kernel has them
     const uint64_t *keys; int R;                // one key per replicate (point evaluation: one key, R = 1)
@@ -4158,229 +4066,35 @@ struct BootParams {
     int64_t *o_wsum;                            // point evaluation: [M] (may be nullptr)
 };
 
-struct BootTask {
-    double Tcentre;
-    long long wsc;                              // total weight at the centre's A
-    long long redw[REFINE_WAVES][3];
-};
-
 __global__ __launch_bounds__(REFINE_THREADS) void boot_kernel(BootParams Q) {
     extern __shared__ __attribute__((aligned(16))) double lds_ws[];
     __shared__ RefineState S;
-    __shared__ BootTask U;
     const RefineParams &P = Q.P;
-    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
-    char *ws = P.ws_lds ? (char *)lds_ws : P.slab + (size_t)blockIdx.x * (size_t)P.ws_bytes;
-    double *tab = (double *)ws;                                              // [REFINE_TABS][rows]
-    int32_t *list = (int32_t *)(ws + (size_t)REFINE_TABS * P.rows * sizeof(double));
-    uint8_t *map = (uint8_t *)(list + P.rows);
+    const int tid = threadIdx.x;
+    const CompassWs ws = compass_ws(P, lds_ws);
     const int64_t count = Q.list ? *Q.count * Q.R : P.M;
-    const uint64_t B = (uint64_t)Q.block;
-    const uint64_t qB = REFINE_THREADS / B, rB = REFINE_THREADS % B;
+    BootWeight wt;
+    wt.B = (uint64_t)Q.block;
+    wt.qB = REFINE_THREADS / wt.B; wt.rB = REFINE_THREADS % wt.B;
+    wt.blk = wt.rem = 0;
     for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
         const int64_t t = Q.list ? (int64_t)Q.list[w / Q.R] : w;
-        const uint64_t key = Q.keys[Q.list ? w % Q.R : 0];
+        wt.key = Q.keys[Q.list ? w % Q.R : 0];
         if (tid == 0) {
-            if (Q.list) {           // support_kernel's centre: the refined point, the grid start's own coordinates and steps
-                const int L = P.lin[t], iA = L / P.npairs, p = L % P.npairs, ix = p / P.nab, ia = p % P.nab;
-                const double g0[3] = {P.gA[iA], P.gx[ix], P.gab[ia]}, gc[3] = {P.cu[iA], P.gx[ix], P.cv[ia]};
-                S.nat0[0] = Q.rA[t]; S.nat0[1] = Q.rx[t]; S.nat0[2] = Q.rab[t];
-                for (int k = 0; k < 3; ++k) S.c0[k] = S.nat0[k] == g0[k] ? gc[k] : (k == 1 ? S.nat0[k] : log(S.nat0[k]));
-                S.h[0] = P.h0u[iA]; S.h[1] = P.h0x[ix]; S.h[2] = P.h0v[ia];
-            } else {
-                S.nat0[0] = P.pA[t]; S.nat0[1] = P.px[t]; S.nat0[2] = P.pab[t];
-                S.c0[0] = log(P.pA[t]); S.c0[1] = P.px[t]; S.c0[2] = log(P.pab[t]);
-                S.h[0] = S.h[1] = S.h[2] = 0.0;
-            }
-            for (int k = 0; k < 3; ++k) { S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k]; }
-            S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
-            S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
-            S.tg = P.test_gen[t];
-            S.wlo = max(P.win_lo[t], (int64_t)0);
-            S.whi = min(P.win_hi[t], P.N - 1);
-            U.Tcentre = -INFINITY; U.wsc = 0;
+            if (Q.list) compass_start_refined(P, S, t, Q.rA, Q.rx, Q.rab, S.h);
+            else compass_start_point(P, S, t);
         }
-        __syncthreads();
-        const double tg = S.tg;
-        if (wave == 0) {            // first site at or right of the test position
-            const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
-            if (lane == 0) S.ctr = ctr;
-        }
-        for (;;) {
-            // ---- 1. the round's candidates (thread 0): refine_kernel's
-            if (tid == 0) {
-                for (int e = 0; e < REFINE_EVALS; ++e) S.valid[e] = 0;
-                S.valid[0] = !S.have_c;
-                bool conv = true;
-                for (int k = 0; k < 3; ++k)
-                    if (P.fr[k] && !(S.h[k] < P.tol[k])) conv = false;
-                S.cand = S.rounds < P.max_rounds && !conv;
-                if (S.cand) {
-                    for (int d = 0; d < 6; ++d) {
-                        const int k = d >> 1;
-                        if (!P.fr[k]) continue;
-                        const double v = min(max((d & 1) ? S.c[k] + S.h[k] : S.c[k] - S.h[k], P.lo[k]), P.hi[k]);
-                        if (v == S.c[k]) continue;
-                        S.valid[d + 1] = 1;
-                        for (int q = 0; q < 3; ++q) { S.cc[d + 1][q] = S.c[q]; S.cn[d + 1][q] = S.nat[q]; }
-                        S.cc[d + 1][k] = v;
-                        S.cn[d + 1][k] = refine_nat(S, k, v);
-                    }
-                }
-                bool any = false;
-                for (int e = 0; e < REFINE_EVALS; ++e) any = any || S.valid[e];
-                S.phase = any ? 1 : S.cand ? 2 : 0;
-                S.Aev[0] = S.nat[0];
-                S.Aev[1] = S.valid[1] ? S.cn[1][0] : S.nat[0];
-                S.Aev[2] = S.valid[2] ? S.cn[2][0] : S.nat[0];
-                S.need_tab[0] = S.valid[0] || S.valid[1] || S.valid[2];
-                S.tx[0] = S.nat[1]; S.tab_ab[0] = S.nat[2];
-                for (int q = 1; q < REFINE_TABS; ++q) {
-                    S.need_tab[q] = S.valid[q + 2];
-                    S.tx[q] = S.valid[q + 2] ? S.cn[q + 2][1] : S.nat[1];
-                    S.tab_ab[q] = S.valid[q + 2] ? S.cn[q + 2][2] : S.nat[2];
-                }
-            }
-            __syncthreads();
-            const int phase = S.phase;
-            if (phase == 0) break;
-            if (phase == 2) {       // every candidate clamps onto the centre: halve
-                if (tid == 0) {
-                    for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
-                    S.rounds++;
-                }
-                __syncthreads();
-                continue;
-            }
-            // ---- the site range of the smallest A of the round, and the rows it references
-            double Amin = S.Aev[0];
-            if (S.valid[1]) Amin = min(Amin, S.Aev[1]);
-            if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
-            if (Amin != S.rangeA) {
-                if (wave == 0) {
-                    const double zc = P.zcut;
-                    const int64_t ctr = S.ctr;
-                    const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
-                    const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
-                    if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
-                }
-                for (int r = tid; r < P.rows; r += REFINE_THREADS) map[r] = 0;
-                __syncthreads();
-                for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) map[P.row[i]] = 1;
-                __syncthreads();
-                int base = 0;
-                for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
-                    const int r = r0 + tid;
-                    const bool on = r < P.rows && map[r];
-                    const unsigned long long m = __ballot(on);
-                    if (lane == 0) S.wtot[wave] = __popcll(m);
-                    __syncthreads();
-                    int off = base;
-                    for (int q = 0; q < wave; ++q) off += S.wtot[q];
-                    if (on) list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
-                    for (int q = 0; q < REFINE_WAVES; ++q) base += S.wtot[q];
-                    __syncthreads();
-                }
-                if (tid == 0) { S.nused = base; S.rangeA = Amin; S.rv++; }
-                __syncthreads();
-            }
-            // ---- 2. R entries of the tables this round needs (the centre's only when its (x, alpha_beta) or rows changed)
-            {
-                int qmask = 0, nq = 0;          // the tables to build, as a bit set (an indexed array would live in scratch here)
-                const bool keep0 = S.built_rv0 == S.rv && S.built_x0 == S.tx[0] && S.built_ab0 == S.tab_ab[0];
-                for (int q = 0; q < REFINE_TABS; ++q)
-                    if (S.need_tab[q] && !(q == 0 && keep0)) { qmask |= 1 << q; nq++; }
-                const int nu = S.nused;
-                for (int it = tid; it < nq * nu; it += REFINE_THREADS) {
-                    int m = qmask;
-                    for (int j = it / nu; j > 0; --j) m &= m - 1;
-                    const int q = __ffs(m) - 1, r = list[it % nu];
-                    tab[(size_t)q * P.rows + r] = refine_R(P, r, S.tx[q], S.tab_ab[q]);
-                }
-                __syncthreads();
-                if (tid == 0 && S.need_tab[0]) { S.built_rv0 = S.rv; S.built_x0 = S.tx[0]; S.built_ab0 = S.tab_ab[0]; }
-            }
-            // ---- 3. the weighted site sums, aligned to the site index
-            double acc[REFINE_EVALS];
-            long long ws3[3] = {0, 0, 0};
-            for (int e = 0; e < REFINE_EVALS; ++e) acc[e] = 0.0;
-            {
-                int vmask = 0;
-                for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
-                const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
-                const int64_t lo = S.rlo, hi = S.rhi;
-                int64_t i = lo - (lo % REFINE_THREADS) + tid;
-                if (i < lo) i += REFINE_THREADS;
-                uint64_t blk = 0, rem = 0;          // i / B and i % B, carried along with i
-                if (i <= hi) { blk = (uint64_t)i / B; rem = (uint64_t)i % B; }
-                for (; i <= hi; i += REFINE_THREADS) {
-                    const int wi = boot_weight(key, blk);
-                    blk += qB; rem += rB;
-                    if (rem >= B) { rem -= B; blk++; }
-                    if (wi == 0) continue;
-                    const double wd = (double)wi;
-                    const double gi = P.genpos[i];
-                    const int r = P.row[i];
-                    const double d = fabs(gi - tg);
-                    const bool same = gi == tg;
-                    const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
-                    const bool in0 = z0 <= zc && !same, in1 = z1 <= zc && !same, in2 = z2 <= zc && !same;
-                    const double a0 = exp(-z0);
-                    if (in0) ws3[0] += wi;
-                    if (in1) ws3[1] += wi;
-                    if (in2) ws3[2] += wi;
-                    if (vmask & 1) { const double v = log1p(a0 * tab[r]); if (in0) acc[0] += wd * v; }
-                    if (vmask & 2) { const double v = log1p(exp(-z1) * tab[r]); if (in1) acc[1] += wd * v; }
-                    if (vmask & 4) { const double v = log1p(exp(-z2) * tab[r]); if (in2) acc[2] += wd * v; }
-                    for (int q = 1; q < REFINE_TABS; ++q)
-                        if (vmask & (1 << (q + 2))) { const double v = log1p(a0 * tab[(size_t)q * P.rows + r]); if (in0) acc[q + 2] += wd * v; }
-                }
-            }
-            // ---- 4. fixed-order reduction, the decision
-            for (int off = 1; off < WAVE; off <<= 1) {
-                for (int e = 0; e < REFINE_EVALS; ++e) acc[e] += __shfl_xor(acc[e], off);
-                for (int k = 0; k < 3; ++k) ws3[k] += __shfl_xor(ws3[k], off);
-            }
-            if (lane == 0) {
-                for (int e = 0; e < REFINE_EVALS; ++e) S.red[wave][e] = acc[e];
-                for (int k = 0; k < 3; ++k) U.redw[wave][k] = ws3[k];
-            }
-            __syncthreads();
-            if (tid == 0) {
-                double T[REFINE_EVALS];
-                long long wk[3];
-                for (int k = 0; k < 3; ++k) wk[k] = (U.redw[0][k] + U.redw[1][k]) + (U.redw[2][k] + U.redw[3][k]);
-                for (int e = 0; e < REFINE_EVALS; ++e) {
-                    const double s = (S.red[0][e] + S.red[1][e]) + (S.red[2][e] + S.red[3][e]);
-                    const long long n = e == 1 ? wk[1] : e == 2 ? wk[2] : wk[0];
-                    const double v = 2.0 * s;
-                    T[e] = (n > 0 && isfinite(v)) ? v : -INFINITY;
-                }
-                if (S.valid[0]) { S.Tc = T[0]; U.wsc = wk[0]; S.have_c = 1; U.Tcentre = T[0]; }
-                if (S.cand) {
-                    double best = S.Tc;
-                    int bi = -1;
-                    for (int e = 1; e < REFINE_EVALS; ++e)
-                        if (S.valid[e] && T[e] > best) { best = T[e]; bi = e; }
-                    if (bi >= 0) {
-                        for (int k = 0; k < 3; ++k) { S.c[k] = S.cc[bi][k]; S.nat[k] = S.cn[bi][k]; }
-                        S.Tc = best;
-                        U.wsc = bi == 1 ? wk[1] : bi == 2 ? wk[2] : wk[0];
-                    } else {
-                        for (int k = 0; k < 3; ++k) S.h[k] *= 0.5;
-                    }
-                    S.rounds++;
-                }
-            }
-            __syncthreads();
-        }
+        compass_begin(P, S, t);
+        double Tcentre = -INFINITY;         // thread 0: T_w at the start, which the first summing round evaluates
+        while (compass_round(P, S, P.fr, ws, wt))
+            if (tid == 0 && S.valid[0]) Tcentre = S.T[0];
         if (tid == 0) {
             if (Q.list) {
                 Q.o_A[w] = S.nat[0]; Q.o_x[w] = S.nat[1]; Q.o_ab[w] = S.nat[2];
-                Q.o_T[w] = S.Tc; Q.o_Tc[w] = U.Tcentre; Q.o_rounds[w] = S.rounds;
+                Q.o_T[w] = S.Tc; Q.o_Tc[w] = Tcentre; Q.o_rounds[w] = S.rounds;
             } else {
                 Q.o_T[t] = S.Tc;
-                if (Q.o_wsum) Q.o_wsum[t] = U.wsc;
+                if (Q.o_wsum) Q.o_wsum[t] = S.nsc;
             }
         }
         __syncthreads();

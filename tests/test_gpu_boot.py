@@ -104,6 +104,13 @@ def check_weighted_points(ctx, pb, seed):
         print('single weight %d: j=%d %r vs %r' % (w0, j, T1[j], w0 * T0[j]))
         assert _close(T1[j], w0 * T0[j], 1e-12), (j, T1[j], T0[j], w0)
     assert np.isfinite(T1).sum() > 0
+    # every site at weight 1: the weighted round is the unweighted round, bit for bit, and the weight sum is nSites
+    Ku = boot.replicate_key(1, 0, 0)
+    assert int(boot.block_weights(Ku, 1)[0]) == 1
+    Tu, nsu = ctx.eval_points(A, x, a)
+    Tw, wsw = ctx.eval_points_weighted(Ku, N + 5, A, x, a)
+    print('unit weight: %d points, %d finite, %d differ in bits' % (M, int(np.isfinite(Tu).sum()), int((_bits(Tw) != _bits(Tu)).sum())))
+    assert np.array_equal(_bits(Tw), _bits(Tu)) and np.array_equal(wsw, nsu)
 
 
 # ---------------------------------------------------------------------------------------------------- weighted point evaluation
