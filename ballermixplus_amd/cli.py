@@ -37,6 +37,13 @@ Additions (do not change any reference command line):
                     among them -- at most N of them (default 1000: the N highest CLR); needs --peaks or --surfaceMin.  Writes
                     <out>.surfaces.txt next to each output file: per window a block of rows physPos, genPos, A, x, abeta, T, nSites
                     with the grids ascending.
+  --influence [--influenceBlock B] [--influenceMin C] [--influenceMax N] [--influenceDetail]     delete-block jackknife of the
+                    CLR of selected windows (ballermixplus_amd/influence.py): per window, selected as --surfaces selects them
+                    (CLR >= C, with --peaks only the apexes, at most N: default 1000; needs --peaks or --influenceMin), the grid
+                    maximum of its surface without each block of B consecutive sites (default 1) and the share of the maximum
+                    each block holds; writes <out>.influence.txt (per window: the number of blocks, the jackknife spread, how few
+                    blocks hold half of the maximum, the largest share, the block whose removal costs most) and with
+                    --influenceDetail <out>.influence.blocks.txt (every block) next to each output file.
   --locate R [--locateSeed S] [--locateBlock B] [--locateSpan H] [--locateLevel L] [--locateMin C] [--locateReps]     with
                     --peaks: a block-bootstrap interval for the POSITION of every apex (ballermixplus_amd/locate.py): R replicates
                     resample the sites in blocks of B consecutive sites on the device, repeat the grid scan at the test positions
@@ -193,6 +200,23 @@ def build_parser():
     parser.add_argument('--surfaceMax', dest='surfaceMax', type=int, default=None,
                         help='MI355X build only, with --surfaces: at most N windows per file, the N with the highest CLR '
                              '(default 1000)')
+    parser.add_argument('--influence', dest='influence', action='store_true', default=False,
+                        help='MI355X build only: delete-block jackknife of the CLR of selected windows of the observed scan: the grid '
+                             'maximum of the window\'s surface without each block of --influenceBlock consecutive sites, and each '
+                             'block\'s share of the maximum, summarised per window in <out>.influence.txt next to each output file.  '
+                             'The windows: with --peaks the apexes, with --influenceMin those at or above it, with both the apexes '
+                             'at or above it; one of the two is required; default: off')
+    parser.add_argument('--influenceBlock', dest='influenceBlock', type=int, default=None,
+                        help='MI355X build only, with --influence: sites per block (default 1: single SNPs).  B should span the '
+                             'cluster of sites whose joint removal is in question')
+    parser.add_argument('--influenceMin', dest='influenceMin', type=float, default=None,
+                        help='MI355X build only, with --influence: only windows with CLR >= this value (default 0)')
+    parser.add_argument('--influenceMax', dest='influenceMax', type=int, default=None,
+                        help='MI355X build only, with --influence: at most N windows per file, the N with the highest CLR '
+                             '(default 1000)')
+    parser.add_argument('--influenceDetail', dest='influenceDetail', action='store_true', default=False,
+                        help='MI355X build only, with --influence: also write every block of every selected window to '
+                             '<out>.influence.blocks.txt')
     parser.add_argument('--locate', dest='locate', type=int, default=0,
                         help='MI355X build only, with --peaks: R >= 2 bootstrap replicates of the grid scan around every apex.  Each '
                              'replicate gives every block of --locateBlock consecutive sites a Poisson(1) weight, scans the '
@@ -398,6 +422,33 @@ def write_surfaces(opt, ctx, sel, outfile, ts, called, say):
         say(f'--surfaceMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
 
 
+def influence_refusal(opt):
+    """--influence / --influenceBlock / --influenceMin / --influenceMax / --influenceDetail."""
+    if not opt.influence:
+        return orphan(opt, '--influence', ('influenceBlock', 'influenceMin', 'influenceMax', 'influenceDetail'))
+    from . import influence
+    return (influence.value_refusal(opt.influenceBlock, opt.influenceMin, opt.influenceMax)
+            or when(opt.peaks is None and opt.influenceMin is None,
+                    '--influence needs --peaks G (the jackknife of the apexes) or --influenceMin C (of the windows with CLR >= C): '
+                    'the jackknife of every window of a chromosome is never what is meant.')
+            or helper_mode(opt, '--influence')
+            or no_output(opt, '--influence', 'influence file is')
+            or multi_rank('--influence'))
+
+
+def write_influence(opt, ctx, sel, outfile, ts, data, called, say):
+    """<outfile>.influence.txt (with --influenceDetail <outfile>.influence.blocks.txt) of one file whose observed scan (and peak
+    call: `called`, or None without --peaks) has just run on ctx's selected slot."""
+    from . import influence
+    B = given(opt.influenceBlock, 1)
+    n, dropped = influence.influence_and_write(ctx, outfile, ts, sel, data, B, given(opt.influenceMin, 0.0),
+                                               given(opt.influenceMax, influence.MAX_WINDOWS),
+                                               called[0]['row'] if called is not None else None, opt.influenceDetail)
+    say(f'\n{datetime.now()}. Influence: {n} window/s, blocks of {B} site/s -> {influence.output_name(outfile)}')
+    if dropped:
+        say(f'--influenceMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
+
+
 def peaks_refusal(opt):
     """--peaks / --peakMin / --peakExtent / --atPeaks.  Asked before the refusals of the features that do not need the peaks,
     so that a command line with --peaks is refused in this feature's name."""
@@ -550,6 +601,9 @@ def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
     if opt.surfaces:
         write_surfaces(opt, ctx, sel, outfile, ts, called, say)
         stamp('file %d: surfaces' % (f + 1))
+    if opt.influence:
+        write_influence(opt, ctx, sel, outfile, ts, data, called, say)
+        stamp('file %d: influence' % (f + 1))
     if opt.refine:
         write_refined(opt, ctx, outfile, ts, f)
         stamp('file %d: refine' % (f + 1))
@@ -622,7 +676,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = power_refusal(opt) or locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt)
+    refused = power_refusal(opt) or locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)

@@ -10,6 +10,8 @@
 //       locate_kernel / finalize_kernel: test-site positions, per-slice argmax merge + nSites
 //       surface_kernel             <- the full T[A,x,alpha] surface of one site (v1:449-450 wish)
 //       surfaces_kernel            <- the same surfaces for a list of test sites in one launch (bmx_ctx_surfaces)
+//       influence_kernel           <- every leave-one-block-out maximum of those surfaces (bmx_ctx_influence), with
+//                                     influence_range_kernel and influence_argmax_kernel
 //
 // The shipped library reads ONE environment variable, BMX_TRACE (stage messages on stderr, no effect on results).
 // Tuning knobs for A/B runs (BMX_LDS_PAD, BMX_DENSE_GAP, BMX_SOLO_GAP, BMX_FORCE_J, BMX_FAR_EPS, BMX_MOM_SLOTS, BMX_SPB,
@@ -4646,6 +4648,194 @@ __global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) 
     if (slice == 0 && tid == 0) S.ns[(size_t)q * S.nA + iA] = ns;
 }
 
+// ----------------------------------------------------------- delete-block jackknife of a list of test sites' grid maxima
+// bmx_ctx_influence (the definition is ballermixplus_amd/influence.py).  Per chunk of listed windows four launches on the
+// context's stream: surfaces_kernel gives T and ns, influence_range_kernel every (window, A)'s site range,
+// influence_argmax_kernel T_max and lin*, and influence_kernel the blocks.
+//   influence_kernel: one workgroup of INFL_THREADS per (listed window, run of up to INFL_BLOCKS consecutive blocks of its
+//   range); thread tid owns the pairs p = slice * INFL_THREADS + tid.  For every (iA, slice) the run's sites inside that A's
+//   range are walked in tiles of INFL_THREADS sites exactly as surfaces_kernel walks them (thread tid computes (alpha, row) of
+//   site base + tid into LDS, every thread adds log1p(alpha_s R[row_s][p]) over the `in` sites in increasing site index), with
+//   the sum restarted at every block boundary: S_b has surfaces_kernel's expression and order, so a block that holds every
+//   qualifying site of an A has S_b == S bitwise.  At a boundary the thread forms T - 2 S_b and keeps its running best (value,
+//   lin) of that block in its own column of an LDS table; one fixed-order workgroup reduction per block ends the workgroup.
+// No atomics.  A block's numbers depend on its window and B alone: a run only decides which workgroup computes them.
+constexpr int INFL_THREADS = 256;
+constexpr int INFL_BLOCKS = 8;
+
+// The scan's rule on (value, linear index): a candidate must be > 0 (the start is (0, -1)), the larger value wins, on a tie
+// the smaller index; every comparison is false for a NaN.  l < 0: no candidate.
+__device__ __forceinline__ void infl_take(double &bv, int32_t &bl, double v, int32_t l) {
+    if (l >= 0 && (v > bv || (v == bv && bl >= 0 && l < bl))) { bv = v; bl = l; }
+}
+
+// The workgroup's best in thread 0's (v, l); every thread calls it.
+__device__ __forceinline__ void infl_wg_best(double &v, int32_t &l, double *s_v, int32_t *s_l) {
+    const int tid = threadIdx.x;
+    for (int off = WAVE / 2; off; off >>= 1) {
+        const double ov = __shfl_xor(v, off, WAVE);
+        const int32_t ol = __shfl_xor(l, off, WAVE);
+        infl_take(v, l, ov, ol);
+    }
+    if ((tid & (WAVE - 1)) == 0) { s_v[tid / WAVE] = v; s_l[tid / WAVE] = l; }
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < INFL_THREADS / WAVE; w++) infl_take(v, l, s_v[w], s_l[w]);
+    __syncthreads();
+}
+
+struct InflRangeParams {
+    const double *genpos; int64_t N;
+    const double *A; int nA;
+    const double *test_gen; const int64_t *win_lo, *win_hi;
+    const int32_t *tests; int64_t n;
+    double zcut;
+    int64_t *rng;     // [n][nA][4]: the inclusive range of A (surfaces_kernel's), the first and last QUALIFYING site (first > last: none)
+};
+
+// One wave per (listed window, A): surfaces_kernel's three searches, and the end of the run of sites at the test position.
+__global__ __launch_bounds__(INFL_THREADS) void influence_range_kernel(InflRangeParams S) {
+    const int64_t w = (int64_t)blockIdx.x * (INFL_THREADS / WAVE) + threadIdx.x / WAVE;        // wave-uniform
+    if (w >= S.n * S.nA) return;
+    const int64_t t = S.tests[w / S.nA];
+    const double A = S.A[w % S.nA], tg = S.test_gen[t], zc = S.zcut;
+    const int64_t wlo = max(S.win_lo[t], (int64_t)0), whi = min(S.win_hi[t], S.N - 1);
+    const int64_t ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return S.genpos[i] >= tg; });
+    const int64_t a = wave_first_true(wlo, ctr, [&](int64_t i) { return A * fabs(S.genpos[i] - tg) <= zc; });
+    const int64_t b = wave_first_true(ctr, whi + 1, [&](int64_t i) { return !(A * fabs(S.genpos[i] - tg) <= zc); });
+    const int64_t e = wave_first_true(ctr, b, [&](int64_t i) { return S.genpos[i] > tg; });
+    if (threadIdx.x % WAVE == 0) {
+        int64_t *o = S.rng + (size_t)w * 4;
+        o[0] = a; o[1] = b - 1;
+        o[2] = a < ctr ? a : e;                 // the sites [ctr, e) sit at the test position and do not qualify
+        o[3] = e < b ? b - 1 : ctr - 1;
+    }
+}
+
+// T_max and lin* of every window of a chunk: the scan's rule over T[q][lin], lin = iA * npairs + p.
+__global__ __launch_bounds__(INFL_THREADS) void influence_argmax_kernel(const double *__restrict__ T, int64_t per, double *__restrict__ tmax,
+                                                                         int32_t *__restrict__ lin) {
+    __shared__ double s_v[INFL_THREADS / WAVE];
+    __shared__ int32_t s_l[INFL_THREADS / WAVE];
+    const double *Tq = T + (size_t)blockIdx.x * per;
+    double v = 0.0;
+    int32_t l = -1;
+    for (int64_t i = threadIdx.x; i < per; i += INFL_THREADS) infl_take(v, l, Tq[i], (int32_t)i);
+    infl_wg_best(v, l, s_v, s_l);
+    if (threadIdx.x == 0) { tmax[blockIdx.x] = v; lin[blockIdx.x] = l; }
+}
+
+struct InflItem {
+    int64_t b0, out;        // the run's first block, and where its results go in the chunk's per-block arrays
+    int32_t q, pad;         // the window's place in the chunk
+};
+
+struct InflParams {
+    const double *genpos; RowArray row;
+    const double *Rt; int NP, npairs, nslices;
+    const double *A; int nA, iAmin;
+    const double *test_gen; const int32_t *tests;       // the chunk's listed test sites
+    double zcut;
+    int64_t B;
+    const double *T; const int32_t *ns;                 // the chunk's surfaces: [m][nA][npairs], [m][nA]
+    const int64_t *rng;                                 // [m][nA][4]
+    const int32_t *lin;                                 // lin*[m]
+    const InflItem *items;
+    int32_t *m_out; double *contrib; double *L; int32_t *blin;
+};
+
+__global__ __launch_bounds__(INFL_THREADS) void influence_kernel(InflParams S) {
+    __shared__ double s_alpha[INFL_THREADS];
+    __shared__ int s_row[INFL_THREADS];
+    __shared__ double s_bv[INFL_BLOCKS][INFL_THREADS];
+    __shared__ int32_t s_bl[INFL_BLOCKS][INFL_THREADS];
+    __shared__ double s_rv[INFL_THREADS / WAVE];
+    __shared__ int32_t s_rl[INFL_THREADS / WAVE];
+    const int tid = threadIdx.x;
+    const InflItem it = S.items[blockIdx.x];
+    const int64_t q = it.q, B = S.B;
+    const int64_t *rq = S.rng + (size_t)q * S.nA * 4;
+    const int64_t ifirst = rq[S.iAmin * 4 + 2], ilast = rq[S.iAmin * 4 + 3];
+    const int nblk = (int)min((int64_t)INFL_BLOCKS, ilast / B - it.b0 + 1);
+    const int64_t clo = max(it.b0 * B, ifirst), chi = min((it.b0 + nblk) * B - 1, ilast);      // the run's sites
+    const double tg = S.test_gen[S.tests[q]], zc = S.zcut;
+    const int32_t linstar = S.lin[q];
+    for (int k = 0; k < nblk; ++k) { s_bv[k][tid] = 0.0; s_bl[k][tid] = -1; }       // (a thread's own column: no barrier)
+    // the thread's best T over the A's whose range the run does not reach: there n_b = 0 for every block of the run, so T itself
+    // is a candidate of each of them (the rule is a total order: it may join the blocks' bests at the end)
+    double ov = 0.0;
+    int32_t ol = -1;
+    for (int iA = 0; iA < S.nA; ++iA) {
+        const double A = S.A[iA];
+        const int nsA = S.ns[q * S.nA + iA];
+        const int64_t lo = max(clo, rq[iA * 4]), hi = min(chi, rq[iA * 4 + 1]);
+        for (int slice = 0; slice < S.nslices; ++slice) {
+            const int p = slice * INFL_THREADS + tid;
+            const bool live = p < S.npairs;
+            const int pr = live ? p : 0;            // an idle thread follows the wave at pair 0 and keeps nothing
+            const int32_t lin = iA * S.npairs + p;
+            const double Tp = S.T[((size_t)q * S.nA + iA) * S.npairs + pr];
+            if (lo > hi && iA != S.iAmin) {         // wave-uniform; (the run always has a site at A_min, where m_b is counted)
+                if (live) {
+                    if (lin == linstar)
+                        for (int k = 0; k < nblk; ++k) S.contrib[it.out + k] = 2.0 * 0.0;
+                    if (nsA > 0) infl_take(ov, ol, Tp, lin);
+                }
+                continue;
+            }
+            // block k of the run ends at site kend; (sum, nb) are S_b and n_b of the block being walked
+            int k = 0, nb = 0;
+            int64_t kend = (it.b0 + 1) * B - 1;
+            double sum = 0.0;
+            auto close = [&]() {
+                if (iA == S.iAmin && slice == 0 && tid == 0) S.m_out[it.out + k] = nb;
+                if (live) {
+                    if (lin == linstar) S.contrib[it.out + k] = 2.0 * sum;
+                    if (nsA - nb > 0) {             // the reference skips an A without sites
+                        double bv = s_bv[k][tid];
+                        int32_t bl = s_bl[k][tid];
+                        infl_take(bv, bl, nb ? Tp - 2.0 * sum : Tp, lin);
+                        s_bv[k][tid] = bv; s_bl[k][tid] = bl;
+                    }
+                }
+                ++k; kend += B; nb = 0; sum = 0.0;
+            };
+            for (int64_t base = lo; base <= hi; base += INFL_THREADS) {
+                const int64_t i = base + tid;
+                const bool valid = i <= hi;
+                const double g = valid ? S.genpos[i] : tg;
+                const double z = A * fabs(g - tg);
+                const bool in = valid && z <= zc && g != tg;
+                s_alpha[tid] = in ? exp(-z) : 0.0;
+                s_row[tid] = in ? (int)S.row[i] : -1;
+                __syncthreads();
+                const int cnt = (int)min((int64_t)INFL_THREADS, hi - base + 1);
+                for (int s = 0; s < cnt; ++s) {
+                    while (base + s > kend) close();
+                    const int r_s = s_row[s];
+                    if (r_s >= 0) {                 // wave-uniform: the one log1p of the kernel
+                        sum += log1p(s_alpha[s] * S.Rt[(size_t)r_s * S.NP + pr]);
+                        ++nb;
+                    }
+                }
+                __syncthreads();
+            }
+            while (k < nblk) close();
+        }
+    }
+    for (int k = 0; k < nblk; ++k) {
+        double v = s_bv[k][tid];
+        int32_t l = s_bl[k][tid];
+        infl_take(v, l, ov, ol);
+        infl_wg_best(v, l, s_rv, s_rl);
+        if (tid == 0) {
+            S.L[it.out + k] = v;
+            S.blin[it.out + k] = l;
+            if (linstar < 0) S.contrib[it.out + k] = NAN;
+        }
+    }
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -4954,6 +5144,17 @@ struct bmx_ctx {
     DevBuf<double> sfs_T;
     DevBuf<int32_t> sfs_ns, sfs_list;
     DevTimer sfs;
+    // delete-block jackknife (bmx_ctx_influence): the site ranges of the list at A_min and of one chunk at every A, the chunk's
+    // runs of blocks, T_max / lin* and per-block outputs, the events around a chunk's kernels; the last call's results on the host
+    DevBuf<int64_t> if_rng1, if_rng;
+    DevBuf<InflItem> if_items;
+    DevBuf<double> if_tmax, if_contrib, if_L;
+    DevBuf<int32_t> if_lin, if_m, if_blin;
+    DevTimer ifl;
+    bool if_have = false;
+    std::vector<int64_t> if_first, if_off;
+    std::vector<double> if_h_tmax, if_h_contrib, if_h_L;
+    std::vector<int32_t> if_h_lin, if_h_ns, if_h_m, if_h_blin;
     DevBuf<int64_t> gap_sample;
     // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
     int pl_which = 0;
@@ -5276,6 +5477,9 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->surf_T.release(); c->surf_ns.release();
     c->sfs_T.release(); c->sfs_ns.release(); c->sfs_list.release();
     c->sfs.release();
+    c->if_rng1.release(); c->if_rng.release(); c->if_items.release(); c->if_tmax.release(); c->if_contrib.release();
+    c->if_L.release(); c->if_lin.release(); c->if_m.release(); c->if_blin.release();
+    c->ifl.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
@@ -6327,6 +6531,156 @@ int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out,
 int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
     return c->sfs.get(ms, "no surfaces call yet");
+}
+
+int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (n < 0) return fail(BMX_E_INVALID, "influence: n < 0");
+    if (block < 1) return fail(BMX_E_INVALID, "influence: block < 1");
+    ChromSlot *s = c->cur;
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before influence");
+    if (n > 0 && !tests) return fail(BMX_E_INVALID, "influence: NULL argument");
+    for (int64_t q = 0; q < n; q++)
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "influence: test site index out of range at entry " + std::to_string(q));
+    c->if_have = false;
+    c->if_first.assign((size_t)n, 0);
+    c->if_off.assign((size_t)n + 1, 0);
+    c->if_h_tmax.assign((size_t)n, 0.0); c->if_h_lin.assign((size_t)n, -1); c->if_h_ns.assign((size_t)n, 0);
+    c->if_h_m.clear(); c->if_h_contrib.clear(); c->if_h_L.clear(); c->if_h_blin.clear();
+    c->ifl.ms = 0.0;
+    if (n == 0) { c->if_have = true; return BMX_OK; }
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t B = std::min(block, std::max<int64_t>(s->N, 1));        // i / B is 0 for every site either way
+    const int iAmin = (int)(std::min_element(c->h_A.begin(), c->h_A.end()) - c->h_A.begin());
+    HIP_TRY(c->sfs_list.ensure((size_t)n));
+    HIP_TRY(hipMemcpyAsync(c->sfs_list.p, tests, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    // 1. every listed window's qualifying sites at A_min -> its block range and the offsets of the per-block arrays
+    InflRangeParams Q;
+    Q.genpos = s->genpos.p; Q.N = s->N; Q.test_gen = s->test_gen.p; Q.win_lo = s->win_lo.p; Q.win_hi = s->win_hi.p; Q.zcut = c->zcut;
+    std::vector<int64_t> h_rng((size_t)n * 4);
+    const int64_t rstep = 1 << 20;
+    HIP_TRY(c->if_rng1.ensure((size_t)std::min(rstep, n) * 4));
+    const int wpb = INFL_THREADS / WAVE;
+    for (int64_t q0 = 0; q0 < n; q0 += rstep) {
+        const int64_t m = std::min(rstep, n - q0);
+        Q.A = c->d_A + iAmin; Q.nA = 1; Q.tests = c->sfs_list.p + q0; Q.n = m; Q.rng = c->if_rng1.p;
+        hipLaunchKernelGGL(influence_range_kernel, dim3((unsigned)((m + wpb - 1) / wpb)), dim3(INFL_THREADS), 0, c->stream, Q);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_rng.data() + (size_t)q0 * 4, c->if_rng1.p, (size_t)m * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    for (int64_t q = 0; q < n; q++) {
+        const int64_t first = h_rng[(size_t)q * 4 + 2], last = h_rng[(size_t)q * 4 + 3];
+        const bool any = first <= last;
+        c->if_first[(size_t)q] = any ? first / B : 0;
+        c->if_off[(size_t)q + 1] = c->if_off[(size_t)q] + (any ? last / B - first / B + 1 : 0);
+        if (c->if_off[(size_t)q + 1] > BMX_INFLUENCE_MAX_RESULTS)
+            return fail(BMX_E_LIMIT, "influence: more than BMX_INFLUENCE_MAX_RESULTS blocks in one call; list fewer windows");
+    }
+    const size_t total = (size_t)c->if_off[(size_t)n];
+    c->if_h_m.assign(total, 0); c->if_h_contrib.assign(total, 0.0); c->if_h_L.assign(total, 0.0); c->if_h_blin.assign(total, -1);
+    // 2. chunks of windows: as many as bmx_ctx_surfaces takes at a time, and at most INFL_CHUNK_BLOCKS blocks (one window if it has more)
+    const size_t per = (size_t)c->nA * c->npairs;
+    const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / (per * sizeof(double)), 1);
+    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
+    const int64_t fit = std::max<int64_t>((0xffffffffLL / SURFS_THREADS) / ((int64_t)c->nA * nsl), 1);
+    const int64_t step = std::min(chunk, fit);
+    const int64_t INFL_CHUNK_BLOCKS = 1 << 22;
+    SurfsParams S;
+    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N;
+    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    S.test_gen = s->test_gen.p; S.win_lo = s->win_lo.p; S.win_hi = s->win_hi.p; S.zcut = c->zcut;
+    InflParams P;
+    P.genpos = s->genpos.p; P.row = s->row_array(); P.Rt = c->d_Rt; P.NP = c->NP; P.npairs = c->npairs; P.nslices = nsl;
+    P.A = c->d_A; P.nA = c->nA; P.iAmin = iAmin; P.test_gen = s->test_gen.p; P.zcut = c->zcut; P.B = B;
+    std::vector<InflItem> items;
+    std::vector<int32_t> h_ns;
+    double total_ms = 0.0;
+    for (int64_t q0 = 0; q0 < n;) {
+        int64_t m = 1;
+        while (m < step && q0 + m < n && c->if_off[(size_t)(q0 + m + 1)] - c->if_off[(size_t)q0] <= INFL_CHUNK_BLOCKS) m++;
+        const int64_t o0 = c->if_off[(size_t)q0], nb = c->if_off[(size_t)(q0 + m)] - o0;
+        items.clear();
+        for (int64_t q = 0; q < m; q++) {
+            const int64_t cnt = c->if_off[(size_t)(q0 + q + 1)] - c->if_off[(size_t)(q0 + q)];
+            for (int64_t k = 0; k < cnt; k += INFL_BLOCKS)
+                items.push_back(InflItem{c->if_first[(size_t)(q0 + q)] + k, c->if_off[(size_t)(q0 + q)] - o0 + k, (int32_t)q, 0});
+        }
+        HIP_TRY(c->sfs_T.ensure((size_t)m * per));
+        HIP_TRY(c->sfs_ns.ensure((size_t)m * c->nA));
+        HIP_TRY(c->if_rng.ensure((size_t)m * c->nA * 4));
+        HIP_TRY(c->if_tmax.ensure((size_t)m));
+        HIP_TRY(c->if_lin.ensure((size_t)m));
+        HIP_TRY(c->if_items.ensure(items.size()));
+        HIP_TRY(c->if_m.ensure((size_t)nb));
+        HIP_TRY(c->if_contrib.ensure((size_t)nb));
+        HIP_TRY(c->if_L.ensure((size_t)nb));
+        HIP_TRY(c->if_blin.ensure((size_t)nb));
+        if (!items.empty())
+            HIP_TRY(hipMemcpyAsync(c->if_items.p, items.data(), items.size() * sizeof(InflItem), hipMemcpyHostToDevice, c->stream));
+        S.tests = c->sfs_list.p + q0; S.T = c->sfs_T.p; S.ns = c->sfs_ns.p;
+        Q.A = c->d_A; Q.nA = c->nA; Q.tests = S.tests; Q.n = m; Q.rng = c->if_rng.p;
+        P.tests = S.tests; P.T = c->sfs_T.p; P.ns = c->sfs_ns.p; P.rng = c->if_rng.p; P.lin = c->if_lin.p; P.items = c->if_items.p;
+        P.m_out = c->if_m.p; P.contrib = c->if_contrib.p; P.L = c->if_L.p; P.blin = c->if_blin.p;
+        HIP_TRY(c->ifl.begin(c->stream));
+        hipLaunchKernelGGL(surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
+        hipLaunchKernelGGL(influence_range_kernel, dim3((unsigned)((m * c->nA + wpb - 1) / wpb)), dim3(INFL_THREADS), 0, c->stream, Q);
+        hipLaunchKernelGGL(influence_argmax_kernel, dim3((unsigned)m), dim3(INFL_THREADS), 0, c->stream, (const double *)c->sfs_T.p,
+                           (int64_t)per, c->if_tmax.p, c->if_lin.p);
+        if (!items.empty())
+            hipLaunchKernelGGL(influence_kernel, dim3((unsigned)items.size()), dim3(INFL_THREADS), 0, c->stream, P);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(c->ifl.end(c->stream));
+        h_ns.resize((size_t)m * c->nA);
+        HIP_TRY(hipMemcpyAsync(c->if_h_tmax.data() + q0, c->if_tmax.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->if_h_lin.data() + q0, c->if_lin.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_ns.data(), c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (nb) {
+            HIP_TRY(hipMemcpyAsync(c->if_h_m.data() + o0, c->if_m.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->if_h_contrib.data() + o0, c->if_contrib.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->if_h_L.data() + o0, c->if_L.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->if_h_blin.data() + o0, c->if_blin.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->ifl.read());
+        total_ms += c->ifl.ms;
+        for (int64_t q = 0; q < m; q++) c->if_h_ns[(size_t)(q0 + q)] = h_ns[(size_t)q * c->nA + iAmin];
+        q0 += m;
+    }
+    c->ifl.ms = total_ms;        // the call's figure: its chunks' kernels, the surfaces among them
+    c->if_have = true;
+    return BMX_OK;
+}
+
+int bmx_ctx_influence_count(bmx_ctx *c, int64_t *n_windows, int64_t *first_block, int64_t *offset) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (!c->if_have) return fail(BMX_E_STATE, "no influence call yet");
+    const size_t n = c->if_first.size();
+    if (n_windows) *n_windows = (int64_t)n;
+    if (first_block) std::copy(c->if_first.begin(), c->if_first.end(), first_block);
+    if (offset) std::copy(c->if_off.begin(), c->if_off.end(), offset);
+    return BMX_OK;
+}
+
+int bmx_ctx_fetch_influence(bmx_ctx *c, double *t_max, int32_t *lin, int32_t *ns_min, int32_t *m, double *contrib, double *L,
+                            int32_t *block_lin) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (!c->if_have) return fail(BMX_E_STATE, "no influence call yet");
+    if (t_max) std::copy(c->if_h_tmax.begin(), c->if_h_tmax.end(), t_max);
+    if (lin) std::copy(c->if_h_lin.begin(), c->if_h_lin.end(), lin);
+    if (ns_min) std::copy(c->if_h_ns.begin(), c->if_h_ns.end(), ns_min);
+    if (m) std::copy(c->if_h_m.begin(), c->if_h_m.end(), m);
+    if (contrib) std::copy(c->if_h_contrib.begin(), c->if_h_contrib.end(), contrib);
+    if (L) std::copy(c->if_h_L.begin(), c->if_h_L.end(), L);
+    if (block_lin) std::copy(c->if_h_blin.begin(), c->if_h_blin.end(), block_lin);
+    return BMX_OK;
+}
+
+int bmx_ctx_influence_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    if (!c->if_have) return fail(BMX_E_STATE, "no influence call yet");
+    *ms = c->ifl.ms;
+    return BMX_OK;
 }
 
 }  // extern "C"

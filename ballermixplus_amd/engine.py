@@ -487,6 +487,31 @@ class Context:
         """Device milliseconds of the kernels of the context's last surfaces() call."""
         return self._ms(self._L.bmx_ctx_surfaces_ms)
 
+    def influence(self, tests, block):
+        """The delete-block jackknife (ballermixplus_amd/influence.py) of the listed test sites of the selected slot (any order,
+        repeats allowed) with blocks of `block` consecutive sites.  Returns a dict: per window T_max f64[n], lin i32[n], ns_min
+        i32[n], first_block i64[n], offset i64[n + 1]; per block of the windows' ranges, window w's at offset[w]:offset[w + 1],
+        m i32, contrib f64, L f64, blin i32."""
+        t = _lib.i32(tests)
+        if t.ndim != 1:
+            raise ValueError('a flat list of test site indices is needed')
+        _lib.check(self._L.bmx_ctx_influence(self._h, len(t), _lib.as_ip(t), int(block)))
+        n = C.c_int64()
+        first, off = np.empty(len(t), dtype=np.int64), np.empty(len(t) + 1, dtype=np.int64)
+        _lib.check(self._L.bmx_ctx_influence_count(self._h, C.byref(n), _lib.as_lp(first), _lib.as_lp(off)))
+        nb = int(off[-1])
+        out = {'T_max': np.empty(len(t)), 'lin': np.empty(len(t), dtype=np.int32), 'ns_min': np.empty(len(t), dtype=np.int32),
+               'first_block': first, 'offset': off, 'm': np.empty(nb, dtype=np.int32), 'contrib': np.empty(nb), 'L': np.empty(nb),
+               'blin': np.empty(nb, dtype=np.int32)}
+        i, d = _lib.as_ip, _lib.as_dp
+        _lib.check(self._L.bmx_ctx_fetch_influence(self._h, d(out['T_max']), i(out['lin']), i(out['ns_min']), i(out['m']),
+                                                   d(out['contrib']), d(out['L']), i(out['blin'])))
+        return out
+
+    def influence_ms(self):
+        """Device milliseconds of the kernels of the context's last influence() call (the surfaces' kernel among them)."""
+        return self._ms(self._L.bmx_ctx_influence_ms)
+
     def fetch_lut(self):
         m = self.model
         shape = (len(m.x), len(m.abeta), m.rows)

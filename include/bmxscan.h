@@ -197,6 +197,29 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
 int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out, int32_t *nsites_out);
 /* Milliseconds the last bmx_ctx_surfaces spent in its kernels (HIP events on the context's stream). */
 int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms);
+/* Delete-block jackknife of the grid maximum of n test sites of the selected slot (listed as for bmx_ctx_surfaces: any order,
+ * repeats allowed); the definition is ballermixplus_amd/influence.py.  Block of site i: i / block.  A window's block range runs
+ * from the block of its first to the block of its last site that qualifies at the smallest A of the grid (empty without one).
+ * Per window: T_max and lin* = the scan's argmax rule on the window's surface (bitwise bmx_ctx_surfaces'; lin = (iA * nx + ix) *
+ * nab + ia, -1 and T_max 0 when nothing is > 0) and the number of qualifying sites at the smallest A.  Per block b of the range:
+ * m = its qualifying sites at the smallest A, contrib = 2 S_b(lin*) (NaN when lin* < 0), L and lin = maximum and argmax, under
+ * the same rule, of T - 2 S_b over the grid points whose A keeps a site outside the block (0 and -1 when nothing is > 0).
+ * The results stay in the context until the next call: bmx_ctx_influence_count gives the number of listed windows, every
+ * window's first block and the exclusive prefix offset[n + 1] of the windows' blocks in the per-block arrays;
+ * bmx_ctx_fetch_influence copies t_max[n], lin[n], ns_min[n] and m, contrib, L, block_lin [offset[n]] (any pointer may be NULL).
+ * A NULL context, n < 0, block < 1, a NULL list with n > 0 or an index outside [0, M) is BMX_E_INVALID and nothing is read;
+ * without model, sites and test sites BMX_E_STATE; more than BMX_INFLUENCE_MAX_RESULTS blocks in one call BMX_E_LIMIT (list
+ * fewer windows per call); count / fetch / ms before a successful call BMX_E_STATE.  n == 0 succeeds.  No atomics: a window's
+ * numbers depend on that window and `block` alone.  Uses the surfaces' buffers and its own; leaves sites, test sites, scan
+ * results, records, profiles, refinement, bootstrap, peak and null state of every slot untouched.  Blocks.
+ * bmx_ctx_influence_ms: milliseconds the last call spent in its kernels (the surfaces' kernel among them).
+ * Added without a bump of BMX_ABI_VERSION_MINOR, as the groups above: look the symbols up to find out. */
+#define BMX_INFLUENCE_MAX_RESULTS (1LL << 26)
+int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block);
+int bmx_ctx_influence_count(bmx_ctx *c, int64_t *n_windows, int64_t *first_block, int64_t *offset);
+int bmx_ctx_fetch_influence(bmx_ctx *c, double *t_max, int32_t *lin, int32_t *ns_min, int32_t *m, double *contrib, double *L,
+                            int32_t *block_lin);
+int bmx_ctx_influence_ms(bmx_ctx *c, double *ms);
 /* Choose the scan kernel variant (0 = default). For A/B measurements only. */
 int bmx_ctx_set_variant(bmx_ctx *c, int variant);
 /* Select (creating it on first use) chromosome slot `slot`, 0 <= slot < 4096. */
