@@ -19,7 +19,7 @@ lo, hi = np.zeros(M, np.int64), np.full(M, N - 1, np.int64)
 rows = model.rows_of(k, nn)
 As_sorted = sorted(As)
 print('A grid:', As_sorted)
-zcut = 18.420680743952367
+zcut = 18.420680743952364
 groups = [('all', As), ('A<1e3', [a for a in As if a < 1e3]), ('1e3<=A<1e4', [a for a in As if 1e3 <= a < 1e4]),
           ('1e4<=A<1e5', [a for a in As if 1e4 <= a < 1e5]), ('A>=1e5', [a for a in As if a >= 1e5])]
 if len(sys.argv) > 2 and sys.argv[2] == 'each':

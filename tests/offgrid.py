@@ -159,7 +159,10 @@ def tests_of(name):
     return gen[idx], idx, lo, hi, np.ones(len(idx), bool)
 
 
-ZCUT = -np.log(1e-8)                              # alpha >= 1e-8: the reference's window (A |g - t| <= zcut)
+# alpha >= 1e-8, the reference's window, as A |g - t| <= zcut: bmx_alpha_cut(), the largest double z with exp(-z) >= 1e-8.  (Not
+# -np.log(1e-8): that is 18.420680743952367, one ulp above it, and exp(-18.420680743952367) < 1e-8.  test_cutedge_cpu.py holds
+# this constant to the oracle's bisection.)
+ZCUT = 18.420680743952364
 
 
 def window_at(gen, tg, A, lo, hi):

@@ -15,7 +15,7 @@ from ballermixplus_amd import _lib, cli, influence, surfaces
 
 EX1 = os.path.join(REFT, 'Example1_fullSweep_200kya_DAF.txt')
 SPECT = os.path.join(REFT, 'HC_CEU_Neut_DAF_spect_for_B2.txt')
-ZCUT = 18.420680743952367
+ZCUT = 18.420680743952364
 
 
 # ------------------------------------------------------------------------------------- the restatement against deletion
