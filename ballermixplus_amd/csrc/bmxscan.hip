@@ -6092,12 +6092,12 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
 // before the launches of a scan: the profile set it computes (the slot's profile arrays sized for it), or BMX_E_LIMIT where the
 // plan's kernels have no profile form.  The slot's profiles are valid again once every range has been launched.
 int begin_profiles(bmx_ctx *c, ChromSlot *s) {
-    s->pl_have = 0;
     const int w = c->pl_which;
-    if (!w) return BMX_OK;
-    if (!s->plan.fn_pl)
+    if (w && !s->plan.fn_pl)       // refused before anything is launched: the last scan's results and profiles stay as they are
         return fail(BMX_E_LIMIT, "profile likelihoods need the prepared or solo scan kernels; this plan uses a round-2 kernel "
                                  "(a table of 4 GiB or more, 2^31 sites or more, or a diagnostic variant)");
+    s->pl_have = 0;
+    if (!w) return BMX_OK;
     const int n[3] = {c->nA, c->nx, c->nab};
     for (int k = 0; k < 3; ++k)
         if (w & (1 << k)) HIP_TRY(s->pl_out[k].ensure((size_t)s->M * n[k]));
@@ -6900,7 +6900,8 @@ int bmx_ctx_fetch_support(bmx_ctx *c, double *end, double *witness, double *witn
                           int32_t *censored, double *T_star, double *T_best, int32_t *rounds, int32_t *evals) {
     if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
     ChromSlot *s = c->cur;
-    if (!s->sp_have) return fail(BMX_E_STATE, "no support intervals of the slot's test sites: call bmx_ctx_support after bmx_ctx_refine");
+    if (!s->sp_have || !s->has_refinement_of_last_scan(c))      // a new scan drops them, as it drops the bootstrap
+        return fail(BMX_E_STATE, "no support intervals of the slot's test sites: call bmx_ctx_support after bmx_ctx_refine");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t M = (size_t)s->M, nt = M * SUPPORT_TASKS;

@@ -86,6 +86,7 @@ class Context:
         self.M = 0
         self.slot = 0
         self._slot_M = {}
+        self._locate_shape = {}      # slot -> (R, K) of its locate_begin
         self._keep = []
 
     def close(self):
@@ -119,28 +120,29 @@ class Context:
 
     def set_model(self, model, As):
         A = _lib.f64(As)
-        self.model, self.nA = model, len(A)
+        _lib.check(self._L.bmx_ctx_set_model(self._h, C.byref(model.c), _lib.as_dp(A), len(A)))
+        self.model, self.nA = model, len(A)        # (after the call: a refused one leaves the library, and so this object, as it was)
         self.As = A.copy()
         self._slot_M = {}
+        self._locate_shape = {}      # a new model ends every slot's position bootstrap
         self.M = 0
-        _lib.check(self._L.bmx_ctx_set_model(self._h, C.byref(model.c), _lib.as_dp(A), len(A)))
 
     def set_sites(self, genpos, rows):
         g, r = _lib.f64(genpos), _lib.i32(rows)
+        _lib.check(self._L.bmx_ctx_set_sites(self._h, len(g), _lib.as_dp(g), _lib.as_ip(r)))
         self.N = len(g)
         self._sites_replaced()
-        _lib.check(self._L.bmx_ctx_set_sites(self._h, len(g), _lib.as_dp(g), _lib.as_ip(r)))
 
     def set_tests(self, test_gen, win_lo=None, win_hi=None):
         """Test positions and their inclusive index windows; no windows = all sites of the chromosome (the reference's default mode)."""
         t = _lib.f64(test_gen)
-        self.M = len(t)
-        self._slot_M[self.slot] = self.M
         if win_lo is None and win_hi is None:
             _lib.check(self._L.bmx_ctx_set_tests(self._h, len(t), _lib.as_dp(t), None, None))
-            return
-        lo, hi = _lib.i64(win_lo), _lib.i64(win_hi)
-        _lib.check(self._L.bmx_ctx_set_tests(self._h, len(t), _lib.as_dp(t), _lib.as_lp(lo), _lib.as_lp(hi)))
+        else:
+            lo, hi = _lib.i64(win_lo), _lib.i64(win_hi)
+            _lib.check(self._L.bmx_ctx_set_tests(self._h, len(t), _lib.as_dp(t), _lib.as_lp(lo), _lib.as_lp(hi)))
+        self.M = len(t)
+        self._slot_M[self.slot] = self.M
 
     def set_variant(self, v):
         _lib.check(self._L.bmx_ctx_set_variant(self._h, int(v)))
@@ -365,8 +367,8 @@ class Context:
         (ballermixplus_amd/locate.py: np.repeat of positions and rows by boot.site_weights), built on the device; the slot is
         then as after set_sites of those arrays.  Returns the number of resampled sites (0: the slot has no sites)."""
         n = C.c_int64()
-        self._sites_replaced()
         _lib.check(self._L.bmx_ctx_resample_sites(self._h, int(src_slot), self._key64(key), int(block), C.byref(n)))
+        self._sites_replaced()
         self.N = n.value
         return n.value
 
@@ -384,8 +386,8 @@ class Context:
         lo, hi = _lib.i32(lo), _lib.i32(hi)
         if lo.shape != hi.shape or lo.ndim != 1:
             raise ValueError('one (lo, hi) pair per peak is needed')
-        self._locate_shape = (int(R), len(lo))
         _lib.check(self._L.bmx_ctx_locate_begin(self._h, len(lo), _lib.as_ip(lo), _lib.as_ip(hi), int(R)))
+        self._locate_shape[self.slot] = (int(R), len(lo))
 
     def locate_accumulate(self, r):
         """After the scan of replicate r: per peak, the argmax row of its range and the CLR there."""
@@ -393,7 +395,7 @@ class Context:
 
     def fetch_locate(self):
         """(row i32[R, K], clr f64[R, K]) of the reduction begun by locate_begin: row -1 where a replicate has no argmax."""
-        R, K = self._locate_shape
+        R, K = self._locate_shape.get(self.slot, (0, 0))       # (none: the library refuses the call)
         row, clr = np.empty((R, K), dtype=np.int32), np.empty((R, K), dtype=np.float64)
         _lib.check(self._L.bmx_ctx_fetch_locate(self._h, _lib.as_ip(row), _lib.as_dp(clr)))
         return row, clr
@@ -409,9 +411,9 @@ class Context:
             raise ValueError('a flat list of centres and one weight per table row are needed')
         first, count = np.zeros(len(c), dtype=np.int32), np.zeros(len(c), dtype=np.int32)
         changed = C.c_int64()
-        self._sites_replaced()
         _lib.check(self._L.bmx_ctx_plant_sites(self._h, int(src_slot), self._key64(key), len(c), _lib.as_dp(c), int(iA), int(ix),
                                                int(ia), _lib.as_dp(w), _lib.as_ip(first), _lib.as_ip(count), C.byref(changed)))
+        self._sites_replaced()
         return first, count, changed.value
 
     def plant_ms(self):

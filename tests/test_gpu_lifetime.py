@@ -1,0 +1,522 @@
+"""One long-lived context against fresh ones, across every call group (tests/lifetime.py holds the worlds, the state model and
+the scripts; tests/test_lifetime_cpu.py shows on the host what the scripts reach).
+
+Every test runs one script in ONE engine.Context that is closed only at the end.  Per op:
+  * predicted to succeed: the op runs, everything it defines is fetched and compared AS BYTES (NaNs by bit pattern) with a clean
+    room -- a context created for this one comparison, brought to the state by the shortest route (set_model, set_sites with the
+    arrays the state model expects, permute_rows where the rows are permuted, set_tests, then only the calls the result depends on:
+    scan, peaks, refine, the replicates of a null or locate run) and closed again.  No tolerance anywhere.  Clean rooms are never
+    pooled or reused.  set_sites, permute_rows, restore_rows, resample_sites and plant_sites are also compared with the host
+    restatements (null.block_permutation, locate.resampled, power.planted_rows on the device's own table).
+  * predicted to be refused: BmxError with exactly the predicted code, and the slot's results fetched before and after are equal.
+  * after every op one OTHER slot that holds results is fetched again and must be what it was when it was scanned.
+  * at three checkpoints per script (one of them after the last set_model) the long-lived context's scan is compared with
+    util.c_scan on the device's own table: integer fields exact outside the oracle's near-ties (gridshape.decide, at most 2 % of
+    the windows), CLR within rtol 1e-9 / atol 1e-12 on every window -- so that the two contexts cannot be wrong together.
+"""
+import collections
+import time
+
+import numpy as np
+import pytest
+
+import gridshape as gs
+import lifetime as lt
+from util import c_oracle, c_scan
+
+pytestmark = pytest.mark.gpu
+
+
+def _bytes(v):
+    """Anything an op returns, as something == compares bit for bit."""
+    if v is None or isinstance(v, (int, str, bytes)):
+        return v
+    if isinstance(v, float):
+        return np.float64(v).tobytes()
+    if isinstance(v, dict):
+        return {k: _bytes(x) for k, x in sorted(v.items())}
+    if isinstance(v, (tuple, list)):
+        return tuple(_bytes(x) for x in v)
+    a = np.ascontiguousarray(v)
+    return (a.dtype.str, a.shape, a.tobytes())
+
+
+def _differs(a, b, path=''):
+    """Where two _bytes() values differ (for the assertion message)."""
+    if type(a) is not type(b):
+        return path + ': types'
+    if isinstance(a, dict):
+        return next((_differs(a[k], b[k], path + '.' + str(k)) for k in a if a[k] != b.get(k)), path + ': keys')
+    if isinstance(a, tuple) and len(a) == 3 and isinstance(a[2], bytes):
+        if a[:2] != b[:2]:
+            return '%s: %r against %r' % (path, a[:2], b[:2])
+        x, y = np.frombuffer(a[2], dtype=np.uint8), np.frombuffer(b[2], dtype=np.uint8)
+        at = np.nonzero(x != y)[0]
+        return '%s: %d of %d bytes differ, the first at element %d' % (path, len(at), len(x), at[0] // np.dtype(a[0]).itemsize)
+    if isinstance(a, tuple):
+        return next((_differs(p, q, '%s[%d]' % (path, i)) for i, (p, q) in enumerate(zip(a, b)) if p != q), path + ': length')
+    return '%s: %r against %r' % (path, a, b)
+
+
+_TABLES = {}
+
+
+def device_table(name):
+    """R[nx][nab][rows] of a model as a fresh context builds it."""
+    if name not in _TABLES:
+        from ballermixplus_amd import engine
+        w = lt.world(name)
+        ctx = engine.Context(0)
+        try:
+            ctx.set_model(w.model, w.As)
+            R = ctx.fetch_lut()[1]
+        finally:
+            ctx.close()
+        R.setflags(write=False)
+        _TABLES[name] = R
+    return _TABLES[name]
+
+
+def _results(ctx, profiles):
+    """Everything a scan defines: the five result arrays, the records, every profile that is on."""
+    out = {'fetch': ctx.fetch(), 'records': ctx.fetch_records()}
+    for bit in (1, 2, 4):
+        if profiles & bit:
+            out['profile%d' % bit] = ctx.fetch_profile(bit)
+    return out
+
+
+def _kept(snapshot, now):
+    """A slot's results are what they were when it was scanned (set_profiles(0) may have released its profiles since)."""
+    return {'fetch', 'records'} <= set(now) and all(now[k] == snapshot[k] for k in now)
+
+
+class Runner:
+    def __init__(self, tmp_path):
+        from ballermixplus_amd import engine, _lib
+        self.engine, self.BmxError = engine, _lib.BmxError
+        self.ctx = engine.Context(0)
+        self.st = lt.State(R_of=device_table)
+        self.tmp, self.files = tmp_path, 0
+        self.snap = {}                       # slot -> _bytes(_results) of its last scan
+        self.rot = 0
+        self.compared, self.refused, self.refetched = collections.Counter(), collections.Counter(), 0
+        self.plans, self.kernels, self.wide_scans, self.anchors = set(), set(), 0, []
+        self.rooms, self.t_rooms, self.t_anchors = 0, 0.0, 0.0
+        self.slow = collections.Counter()    # (op, model) -> seconds, the op and its clean room together
+
+    # ---- the arrays of an op, from its plain arguments and the state BEFORE it
+    def args(self, o):
+        name, a = o
+        st, s = self.st, self.st.slot
+        w = st.w if st.model else None
+        if name == 'set_model':
+            if a['model'] == 'bad':
+                w0 = lt.world('g1')
+                return {'model': w0.model, 'As': [5000.0, 0.0]}
+            w1 = lt.world(a['model'])
+            return {'model': w1.model, 'As': w1.As}
+        if name == 'set_sites':
+            gen, rows = (w or lt.world('g1')).chroms['S' if a['chrom'] == 'bad' else a['chrom']]
+            return {'gen': gen[::-1] if a['chrom'] == 'bad' else gen, 'rows': rows}
+        if name == 'set_tests':
+            if a['stride'] == 0 or s.sites is None:
+                return {'tg': np.zeros(0 if a['stride'] == 0 else 3), 'lo': None, 'hi': None}
+            gen = s.sites['gen']
+            idx = lt.test_index(len(gen), a['stride'])
+            lo, hi = lt.windows_of(gen, idx, a['windows'])
+            return {'tg': gen[idx], 'lo': lo, 'hi': hi}
+        if name in ('surfaces', 'influence', 'fetch_at'):
+            v = lt.index_list(a['kind'], s.M)
+            if a.get('bad'):
+                v[-1] = s.M
+            return {'list': v}
+        if name == 'plant_sites':
+            src = st.slots.get(a['src'])
+            have = src is not None and src.sites is not None and 0 <= a['iA'] < w.nA if w else False
+            c = st.plant_args(a, src)[1] if have else np.arange(a['K'], dtype=np.float64)
+            return {'centres': c, 'gw': w.gw if w else np.zeros(lt.world('g1').model.rows)}
+        if name == 'peaks_track':
+            return dict(zip(('gen', 'clr'), lt.track_of(a['n'], a['seed'])))
+        if name in ('eval_points', 'eval_points_weighted'):
+            return {'point': lt.eval_point(w) if w else (1.0, 0.3, 1.0)}
+        if name == 'locate_begin':
+            return dict(zip(('lo', 'hi'), lt.locate_ranges(a['K'], a['step'], a['width'])))
+        if name == 'scan_write':
+            self.files += 1
+            return {'labels': (np.arange(s.M, dtype=np.int64) * 3 + 7, s.tests['tg'] if s.tests else np.zeros(0)),
+                    'grids': ([repr(v) for v in w.xs], [repr(v) for v in w.abetas], [repr(v) for v in w.As]) if w else (['0.3'], ['1.0'], ['1.0'])}
+        if name == 'pack_records':
+            return {'total': sum(x.M for x in st.slots.values() if x.scan is not None)}
+        return {}
+
+    # ---- one op on one context (the long-lived one or a clean room); st: the state before the op
+    def do(self, ctx, o, g, N=None, M=None, profiles=0, tag='live'):
+        name, a = o
+        f = lambda v: float(v)
+        if name == 'set_model':
+            ctx.set_model(g['model'], g['As'])
+            return ctx.fetch_lut()[1]
+        if name == 'set_sites':
+            ctx.set_sites(g['gen'], g['rows'])
+            return ctx.fetch_sites(len(g['gen']))
+        if name == 'set_tests':
+            ctx.set_tests(g['tg'], g['lo'], g['hi'])
+            return ctx.plan(), ctx.launch_ranges()
+        if name == 'select_slot':
+            return ctx.select_slot(a['slot'])
+        if name == 'set_variant':
+            ctx.set_variant(a['variant'])
+            return (ctx.plan(), ctx.launch_ranges()) if M else None
+        if name == 'set_profiles':
+            return ctx.set_profiles(a['which'])
+        if name == 'fetch_profile':
+            return ctx.fetch_profile(a['which'])
+        if name == 'scan':
+            ctx.scan()
+            return _results(ctx, profiles)
+        if name == 'scan_write':
+            path = str(self.tmp / ('%s_%d.txt' % (tag, self.files)))
+            ctx.scan_write(path, g['labels'][0], g['labels'][1], *g['grids'], chunk=a['chunk'])
+            out = _results(ctx, profiles)
+            with open(path, 'rb') as fh:
+                out['file'] = fh.read()
+            return out
+        if name == 'permute_rows':
+            ctx.permute_rows(a['key'], a['block'])
+            return ctx.fetch_sites(N)
+        if name == 'restore_rows':
+            ctx.restore_rows()
+            return ctx.fetch_sites(N)
+        if name == 'null_begin':
+            ctx.null_begin()
+            return ctx.null_fetch()
+        if name == 'null_accumulate':
+            return ctx.null_accumulate(), ctx.null_fetch()
+        if name == 'null_fetch':
+            return ctx.null_fetch()
+        if name == 'refine_at_peaks':
+            return ctx.refine_at_peaks(a['on'])
+        if name == 'refine':
+            ctx.refine(f(a['min_clr']))
+            return ctx.fetch_refined()
+        if name == 'fetch_refined':
+            return ctx.fetch_refined()
+        if name == 'support':
+            ctx.support(a['drop'], f(a['min_clr']))
+            return ctx.fetch_support()
+        if name == 'fetch_support':
+            return ctx.fetch_support()
+        if name == 'boot':
+            ctx.boot(lt.boot_keys(a['key'], a['R']), a['block'], f(a['min_clr']))
+            return ctx.fetch_boot()
+        if name == 'fetch_boot':
+            return ctx.fetch_boot()
+        if name == 'eval_points':
+            return ctx.eval_points(*g['point'])
+        if name == 'eval_points_weighted':
+            return ctx.eval_points_weighted(a['key'], a['block'], *g['point'])
+        if name == 'peaks':
+            return ctx.peaks(f(a['sep']), f(a['min_clr']), f(a['frac']))
+        if name == 'peaks_track':
+            return ctx.peaks_track(g['gen'], g['clr'], f(a['sep']), f(a['min_clr']), f(a['frac']))
+        if name == 'fetch_peaks':
+            return ctx.fetch_peaks()
+        if name == 'surfaces':
+            return ctx.surfaces(g['list'])
+        if name == 'influence':
+            return ctx.influence(g['list'], a['block'])
+        if name == 'resample_sites':
+            n = ctx.resample_sites(a['src'], a['key'], a['block'])
+            return n, (ctx.fetch_sites(n) if n else None)
+        if name == 'plant_sites':
+            out = ctx.plant_sites(a['src'], a['key'], g['centres'], a['iA'], a['ix'], a['ia'], g['gw'])
+            return out, ctx.fetch_sites(N)
+        if name == 'fetch_at':
+            return ctx.fetch_at(g['list'])
+        if name == 'locate_begin':
+            ctx.locate_begin(g['lo'], g['hi'], a['R'])
+            return ctx.fetch_locate()
+        if name == 'locate_accumulate':
+            ctx.locate_accumulate(a['r'])
+            return ctx.fetch_locate()
+        if name == 'fetch_locate':
+            return ctx.fetch_locate()
+        if name == 'pack_records':
+            if a.get('short'):
+                return ctx.pack_records(out=np.empty(max(g['total'] - 1, 0), dtype=self.engine._lib.RECORD_DTYPE))
+            return ctx.pack_records()
+        raise AssertionError(name)
+
+    # ---- clean rooms
+    def _setup(self, room, d, tests=True):
+        """A fresh context up to a scan description's model, switches, sites, permutation and test sites."""
+        w = lt.world(d['model'])
+        room.set_model(w.model, w.As)
+        room.set_variant(d['variant'])
+        room.set_profiles(d['profiles'])
+        room.set_sites(d['gen'], d['given'])
+        if d['perm'] is not None:
+            room.permute_rows(*d['perm'])
+        if tests and d['tests'] is not None:
+            room.set_tests(d['tests']['tg'], d['tests']['lo'], d['tests']['hi'])
+
+    @staticmethod
+    def _to_perm(room, have, want):
+        if have != want:
+            room.restore_rows() if want is None else room.permute_rows(*want)
+
+    def _refined(self, room, rf):
+        self._setup(room, rf['scan'])
+        room.scan()
+        if rf['peaks'] is not None:
+            room.peaks(*rf['peaks'])
+            room.refine_at_peaks(True)
+        self._to_perm(room, rf['scan']['perm'], rf['perm'])
+        room.refine(float(rf['min_clr']))
+
+    def clean(self, o, g):
+        """What a context created for this one comparison returns for op o (the state is the one AFTER the op)."""
+        name, a = o
+        st, s = self.st, self.st.slot
+        room = self.engine.Context(0)
+        self.rooms += 1
+        N = None if s.sites is None else len(s.sites['gen'])
+        kw = dict(N=N, M=s.M, profiles=st.profiles, tag='room')
+        try:
+            if name in ('set_model', 'peaks_track'):
+                return self.do(room, o, g, **kw)
+            if name == 'fetch_peaks' and s.pk['kind'] == 'track':
+                t = lt.track_of(*s.pk['track'])
+                room.peaks_track(t[0], t[1], *s.pk['args'])
+                return room.fetch_peaks()
+            if name in ('locate_begin', 'locate_accumulate', 'fetch_locate'):
+                if st.model is not None:
+                    room.set_model(st.w.model, st.w.As)
+                lc = s.lc
+                room.locate_begin(*lt.locate_ranges(lc['K'], lc['step'], lc['width']), lc['R'])
+                for r, d in lc['acc']:
+                    room.set_variant(d['variant'])
+                    room.set_profiles(d['profiles'])
+                    room.set_sites(d['gen'], d['given'])
+                    if d['perm'] is not None:
+                        room.permute_rows(*d['perm'])
+                    room.set_tests(d['tests']['tg'], d['tests']['lo'], d['tests']['hi'])
+                    room.scan()
+                    room.locate_accumulate(r)
+                return room.fetch_locate()
+            if name in ('resample_sites', 'plant_sites'):
+                src = st.slots[a['src']]
+                room.set_model(st.w.model, st.w.As)
+                room.set_sites(src.sites['gen'], src.sites['given'])
+                if src.perm is not None:
+                    room.permute_rows(*src.perm)
+                room.select_slot(1)
+                return self.do(room, (name, dict(a, src=0)), g, **kw)
+            if name in ('null_begin', 'null_accumulate', 'null_fetch'):
+                nl = s.null
+                self._setup(room, nl['obs'])
+                room.scan()
+                room.null_begin()
+                have, mx = nl['obs']['perm'], None
+                for d in nl['reps']:
+                    room.set_variant(d['variant'])
+                    room.set_profiles(d['profiles'])
+                    self._to_perm(room, have, d['perm'])
+                    have = d['perm']
+                    room.scan()
+                    mx = room.null_accumulate()
+                return (mx, room.null_fetch()) if name == 'null_accumulate' else room.null_fetch()
+            if name in ('refine', 'fetch_refined'):
+                self._refined(room, s.rf)
+                return room.fetch_refined()
+            if name in ('support', 'fetch_support'):
+                self._refined(room, s.rf)
+                self._to_perm(room, s.rf['perm'], s.sp['perm'])
+                room.support(s.sp['drop'], float(s.sp['min_clr']))
+                return room.fetch_support()
+            if name in ('boot', 'fetch_boot'):
+                self._refined(room, s.rf)
+                self._to_perm(room, s.rf['perm'], s.bt['perm'])
+                room.boot(lt.boot_keys(s.bt['key'], s.bt['R']), s.bt['block'], float(s.bt['min_clr']))
+                return room.fetch_boot()
+            if name in ('peaks', 'fetch_peaks'):
+                self._setup(room, s.pk['scan'])
+                room.scan()
+                return room.peaks(*s.pk['args'])
+            if name in ('fetch_profile', 'fetch_at'):
+                self._setup(room, s.scan)
+                room.scan()
+                return self.do(room, o, g, **kw)
+            # the ops that need the model, the slot's sites as they are now and (but for the first three) its test sites
+            d = st.describe() if s.sites is not None else None
+            if name == 'set_sites':
+                room.set_model(st.w.model, st.w.As)
+            elif name in ('permute_rows', 'restore_rows'):
+                self._setup(room, dict(d, perm=self.perm_before if name == 'restore_rows' else None), tests=False)
+            elif name == 'set_tests':
+                self._setup(room, d, tests=False)
+            elif name == 'set_variant':
+                self._setup(room, dict(d, variant=0))
+            else:
+                assert name in ('scan', 'scan_write', 'surfaces', 'influence', 'eval_points', 'eval_points_weighted'), name
+                self._setup(room, d)
+            return self.do(room, o, g, **kw)
+        finally:
+            room.close()
+
+    # ---- the host restatements, where an op leaves site arrays
+    def host_sites(self, o, got):
+        s = self.st.slot
+        name = o[0]
+        if name in ('set_sites', 'permute_rows', 'restore_rows'):
+            sites = got
+        elif name == 'resample_sites':
+            assert got[0] == (0 if s.sites is None else len(s.sites['gen'])), o
+            sites = got[1]
+        elif name == 'plant_sites':
+            sites = got[1]
+        else:
+            return
+        if sites is not None:
+            assert np.array_equal(sites[0].view(np.uint64), s.sites['gen'].view(np.uint64)), o
+            assert np.array_equal(sites[1], s.rows_now()), (o, int((sites[1] != s.rows_now()).sum()))
+
+    def fetch_now(self):
+        """The selected slot's last results, the profiles it computed included (None without results)."""
+        s = self.st.slot
+        return _bytes(_results(self.ctx, s.pl)) if s.scan is not None else None
+
+    def anchor(self, i):
+        """The long-lived context's scan against the C oracle on the device's own table."""
+        st, s = self.st, self.st.slot
+        w, gen, rows, t = st.w, s.sites['gen'], s.rows_now(), s.tests
+        R = np.where(np.isfinite(device_table(st.model)), device_table(st.model), 0.0)
+        M, N = s.M, len(gen)
+        lo = np.zeros(M, np.int64) if t['lo'] is None else t['lo']
+        hi = np.full(M, N - 1, np.int64) if t['hi'] is None else t['hi']
+        got = self.ctx.fetch()
+        ref = c_scan(c_oracle(), R, w.As, gen, rows, t['tg'], lo, hi)
+        S, ns = gs.surface_sums(c_oracle(), R, w.As, gen, rows, t['tg'], lo, hi)
+        tied = gs.decide(S, ns)[3]
+        keep = ~tied
+        worst = float(np.max(np.abs(got[0] - ref[0]) / np.maximum(np.abs(ref[0]), 1e-300)))
+        print('  oracle anchor at op %d: model %s, %d sites, %d windows (%d near-ties left out of the exact comparison), variant %d, worst relative dCLR %.2e'
+              % (i, st.model, N, M, int(tied.sum()), st.variant, worst))
+        assert tied.sum() <= max(1, 0.02 * M)
+        for q in (1, 2, 3, 4):
+            assert np.array_equal(got[q][keep], ref[q][keep]), (i, q, np.nonzero(got[q] != ref[q])[0][:8])
+        assert np.allclose(got[0], ref[0], rtol=1e-9, atol=1e-12), (i, worst)
+        self.anchors.append(i)
+
+    def run(self, ops, anchors):
+        st, ctx = self.st, self.ctx
+        for i, o in enumerate(ops):
+            name, a = o
+            if i:
+                self.slow[(ops[i - 1][0], st.model)] += time.perf_counter() - t_op
+            t_op = time.perf_counter()
+            want = st.predict(o)
+            g = self.args(o)
+            s = st.slot
+            N = None if s.sites is None else len(s.sites['gen'])
+            if want:
+                before = self.fetch_now()
+                with pytest.raises(self.BmxError) as e:
+                    self.do(ctx, o, g, N=N, M=s.M, profiles=st.profiles)
+                assert e.value.code == want, (i, o, lt.CODE_NAMES[want], str(e.value))
+                assert self.fetch_now() == before, (i, o, 'a refused call changed the results')
+                self.refused[want] += 1
+            else:
+                self.perm_before = s.perm
+                after_profiles = st.profiles
+                got = self.do(ctx, o, g, N=N if name != 'plant_sites' else len(st.slots[a['src']].sites['gen']), M=s.M, profiles=after_profiles)
+                assert st.step(o) == 0
+                s = st.slot
+                self.host_sites(o, got)
+                if name == 'select_slot':
+                    if s.scan is not None:
+                        assert _kept(self.snap[st.cur], _bytes(_results(ctx, s.pl))), (i, o)
+                elif name == 'pack_records':
+                    want_rec = b''.join(self.snap[k]['records'][2] for k in st.with_results())
+                    assert got.tobytes() == want_rec, (i, o)
+                elif lt.is_compared(o, st):
+                    t0 = time.perf_counter()
+                    ref = self.clean(o, g)
+                    self.t_rooms += time.perf_counter() - t0
+                    assert _bytes(got) == _bytes(ref), (i, o, _differs(_bytes(got), _bytes(ref)))
+                if lt.is_compared(o, st):
+                    self.compared[lt.GROUP_OF[name]] += 1
+                if name in ('scan', 'scan_write'):
+                    pl = ctx.plan()
+                    self.plans.add((pl['mode'], pl['J']))
+                    self.kernels.add(pl['kernel'])
+                    self.wide_scans += st.w.model.rows > 65535
+                    self.snap[st.cur] = _bytes({k: v for k, v in got.items() if k != 'file'})
+                    if i in anchors:
+                        t0 = time.perf_counter()
+                        self.anchor(i)
+                        self.t_anchors += time.perf_counter() - t0
+                for k in list(self.snap):
+                    if st.slots[k].scan is None:
+                        del self.snap[k]
+            # one other slot that holds results must be what it was
+            others = [k for k in st.with_results() if k != st.cur]
+            if others:
+                k = others[self.rot % len(others)]
+                self.rot += 1
+                ctx.select_slot(k)
+                assert _kept(self.snap[k], _bytes(_results(ctx, st.slots[k].pl))), (i, o, 'slot %d changed' % k)
+                ctx.select_slot(st.cur)
+                self.refetched += 1
+
+    def close(self):
+        self.ctx.close()
+
+
+def _anchor_points(ops):
+    """Three scans to compare with the oracle: the cheapest successful one of the first third, of the middle, and after the
+    last set_model."""
+    tr = lt.trace(ops)
+    last_model = max(i for i, r in enumerate(tr) if r['name'] == 'set_model' and r['code'] == 0)
+    scans = [(i, r) for i, r in enumerate(tr) if r['name'] == 'scan' and r['code'] == 0]
+    cost = lambda r: lt.scan_cost(lt.world(r['model']), r['N'], r['tests'][0], r['tests'][1])
+    third = len(ops) // 3
+    parts = [[(i, r) for i, r in scans if i < third], [(i, r) for i, r in scans if third <= i < last_model],
+             [(i, r) for i, r in scans if i > last_model]]
+    assert all(parts), [len(p) for p in parts]
+    return {min(p, key=lambda ir: cost(ir[1]))[0] for p in parts}
+
+
+def _run_script(name, tmp_path):
+    ops = lt.scripts()[name]
+    anchors = _anchor_points(ops)
+    run = Runner(tmp_path)
+    t0 = time.perf_counter()
+    try:
+        run.run(ops, anchors)
+    finally:
+        run.close()
+    dt = time.perf_counter() - t0
+    print('%s: %d ops in %.2f s (%.2f s in the clean rooms, %.2f s in the oracle); %d clean rooms; compared per group %s; refused %s; %d re-fetches of another slot; plans %s; 4-byte-row scans %d'
+          % (name, len(ops), dt, run.t_rooms, run.t_anchors, run.rooms, dict(run.compared), {lt.CODE_NAMES[c]: n for c, n in run.refused.items()}, run.refetched,
+             sorted(run.plans), run.wide_scans))
+    print('  kernels: %s' % sorted(run.kernels))
+    print('  slowest (op, model): %s' % ', '.join('%s/%s %.2f s' % (k[0], k[1], v) for k, v in run.slow.most_common(8)))
+    assert len(run.anchors) >= 3 and max(run.anchors) > max(i for i, o in enumerate(ops) if o[0] == 'set_model')
+    return run
+
+
+def test_hand_written_script(tmp_path):
+    """The required transitions; it also meets the three default plans, a kernel that reads the table from L2 and a scan on
+    4-byte row indices."""
+    run = _run_script('hand', tmp_path)
+    assert {(4, 16), (4, 8), (5, 1)} <= run.plans, run.plans
+    assert any(k.endswith(',false>') or k.endswith('<false>') for k in run.kernels), run.kernels
+    assert run.wide_scans >= 1
+
+
+@pytest.mark.parametrize('seed', lt.WALK_SEEDS)
+def test_random_walk(seed, tmp_path):
+    run = _run_script('walk%d' % seed, tmp_path)
+    assert sum(run.refused.values()) >= lt.WALK_LENGTH // 16
