@@ -44,6 +44,14 @@ Additions (do not change any reference command line):
                     each block holds; writes <out>.influence.txt (per window: the number of blocks, the jackknife spread, how few
                     blocks hold half of the maximum, the largest share, the block whose removal costs most) and with
                     --influenceDetail <out>.influence.blocks.txt (every block) next to each output file.
+  --fit [--fitBins D] [--fitClasses F] [--fitMin C] [--fitMax N] [--fitMinExp E] [--fitDetail]     goodness of fit of selected
+                    windows (ballermixplus_amd/fit.py): per window, selected as --surfaces selects them (CLR >= C, with --peaks only
+                    the apexes, at most N: default 1000; needs --peaks or --fitMin), the sites of the window at its scan argmax
+                    counted by distance bin (D bins of z = A |g - t| up to the cut, default 8) and frequency class (F classes of
+                    k / n, default 10) against the counts the fitted mixture and neutrality expect; writes <out>.fit.txt (per
+                    window: the two chi-square sums over the cells with an expected count >= E, default 5, their degrees of
+                    freedom and the worst cell) and with --fitDetail <out>.fit.cells.txt (every cell) next to each output file.
+                    Sites are linked: the sums describe, they are no calibrated test.
   --locate R [--locateSeed S] [--locateBlock B] [--locateSpan H] [--locateLevel L] [--locateMin C] [--locateReps]     with
                     --peaks: a block-bootstrap interval for the POSITION of every apex (ballermixplus_amd/locate.py): R replicates
                     resample the sites in blocks of B consecutive sites on the device, repeat the grid scan at the test positions
@@ -217,6 +225,27 @@ def build_parser():
     parser.add_argument('--influenceDetail', dest='influenceDetail', action='store_true', default=False,
                         help='MI355X build only, with --influence: also write every block of every selected window to '
                              '<out>.influence.blocks.txt')
+    parser.add_argument('--fit', dest='fit', action='store_true', default=False,
+                        help='MI355X build only: goodness of fit of selected windows of the observed scan: the sites of each window '
+                             'at its scan argmax, counted by distance bin and frequency class, against the counts expected under '
+                             'the fitted mixture and under neutrality, summarised per window in <out>.fit.txt next to each output '
+                             'file.  The windows: with --peaks the apexes, with --fitMin those at or above it, with both the apexes '
+                             'at or above it.  The chi-square sums describe (sites are linked); they are no calibrated test')
+    parser.add_argument('--fitBins', dest='fitBins', type=int, default=None,
+                        help='MI355X build only, with --fit: distance bins of equal width in z = A |g - t| up to the cut (default 8: '
+                             'about one per decade of alpha)')
+    parser.add_argument('--fitClasses', dest='fitClasses', type=int, default=None,
+                        help='MI355X build only, with --fit: frequency classes min(F - 1, (k F) // n) (default 10; --noFreq: the '
+                             'two classes substitution / polymorphism are 0 and 1); bins times classes at most 256')
+    parser.add_argument('--fitMin', dest='fitMin', type=float, default=None,
+                        help='MI355X build only, with --fit: only windows with CLR >= this value (default 0)')
+    parser.add_argument('--fitMax', dest='fitMax', type=int, default=None,
+                        help='MI355X build only, with --fit: at most N windows per file, the N with the highest CLR (default 1000)')
+    parser.add_argument('--fitMinExp', dest='fitMinExp', type=float, default=None,
+                        help='MI355X build only, with --fit: cells with an expected count below this value are pooled per bin '
+                             '(default 5)')
+    parser.add_argument('--fitDetail', dest='fitDetail', action='store_true', default=False,
+                        help='MI355X build only, with --fit: also write every cell of every selected window to <out>.fit.cells.txt')
     parser.add_argument('--locate', dest='locate', type=int, default=0,
                         help='MI355X build only, with --peaks: R >= 2 bootstrap replicates of the grid scan around every apex.  Each '
                              'replicate gives every block of --locateBlock consecutive sites a Poisson(1) weight, scans the '
@@ -449,6 +478,32 @@ def write_influence(opt, ctx, sel, outfile, ts, data, called, say):
         say(f'--influenceMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
 
 
+def fit_refusal(opt):
+    """--fit / --fitBins / --fitClasses / --fitMin / --fitMax / --fitMinExp / --fitDetail."""
+    if not opt.fit:
+        return orphan(opt, '--fit', ('fitBins', 'fitClasses', 'fitMin', 'fitMax', 'fitMinExp', 'fitDetail'))
+    from . import fit
+    return (fit.value_refusal(opt.fitBins, opt.fitClasses, opt.fitMin, opt.fitMax, opt.fitMinExp, opt.nofreq)
+            or when(opt.peaks is None and opt.fitMin is None,
+                    '--fit needs --peaks G (the fit of the apexes) or --fitMin C (of the windows with CLR >= C): '
+                    'the table of every window of a chromosome is never what is meant.')
+            or helper_mode(opt, '--fit')
+            or no_output(opt, '--fit', 'fit file is')
+            or multi_rank('--fit'))
+
+
+def write_fit(opt, ctx, sel, outfile, ts, called, say):
+    """<outfile>.fit.txt (with --fitDetail <outfile>.fit.cells.txt) of one file whose observed scan (and peak call: `called`, or
+    None without --peaks) has just run on ctx's selected slot."""
+    from . import fit
+    D, F = given(opt.fitBins, fit.BINS), given(opt.fitClasses, fit.CLASSES)
+    n, dropped = fit.fit_and_write(ctx, outfile, ts, sel, D, F, given(opt.fitMin, 0.0), given(opt.fitMax, fit.MAX_WINDOWS),
+                                   given(opt.fitMinExp, fit.MIN_EXP), called[0]['row'] if called is not None else None, opt.fitDetail)
+    say(f'\n{datetime.now()}. Fit: {n} window/s, {D} distance bin/s x {F} frequency class/es -> {fit.output_name(outfile)}')
+    if dropped:
+        say(f'--fitMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
+
+
 def peaks_refusal(opt):
     """--peaks / --peakMin / --peakExtent / --atPeaks.  Asked before the refusals of the features that do not need the peaks,
     so that a command line with --peaks is refused in this feature's name."""
@@ -604,6 +659,9 @@ def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
     if opt.influence:
         write_influence(opt, ctx, sel, outfile, ts, data, called, say)
         stamp('file %d: influence' % (f + 1))
+    if opt.fit:
+        write_fit(opt, ctx, sel, outfile, ts, called, say)
+        stamp('file %d: fit' % (f + 1))
     if opt.refine:
         write_refined(opt, ctx, outfile, ts, f)
         stamp('file %d: refine' % (f + 1))
@@ -676,7 +734,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = power_refusal(opt) or locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt)
+    refused = power_refusal(opt) or locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)

@@ -12,6 +12,7 @@
 //       surfaces_kernel            <- the same surfaces for a list of test sites in one launch (bmx_ctx_surfaces)
 //       influence_kernel           <- every leave-one-block-out maximum of those surfaces (bmx_ctx_influence), with
 //                                     influence_range_kernel and influence_argmax_kernel
+//       fit_kernel                 <- observed against expected spectrum by distance of listed windows (bmx_ctx_fit)
 //
 // The shipped library reads ONE environment variable, BMX_TRACE (stage messages on stderr, no effect on results).
 // Tuning knobs for A/B runs (BMX_LDS_PAD, BMX_DENSE_GAP, BMX_SOLO_GAP, BMX_FORCE_J, BMX_FAR_EPS, BMX_MOM_SLOTS, BMX_SPB,
@@ -4836,6 +4837,146 @@ __global__ __launch_bounds__(INFL_THREADS) void influence_kernel(InflParams S) {
     }
 }
 
+// ------------------------------------------------------------ goodness of fit of a list of test sites: spectrum by distance
+// bmx_ctx_fit (the definition is ballermixplus_amd/fit.py; include/bmxscan.h states the entry point).  One workgroup of
+// FIT_THREADS per listed window q = (test site, grid point lin).
+//   1. prologue: per (size block j, class c), in ascending row order over the block's rows of that class with gw > 0,
+//        Gn = sum gw,   Gs = sum gw over the rows with a finite R,   H = sum gw R over the same rows
+//      with R the (ix, ia) row of the resident table [pair][rows], then per j their totals over the classes in ascending c (kept
+//      at c = F).  m_r = gw (1 + alpha R) is linear in alpha, and with 0 <= gw <= 1 (the host refuses anything else), R >= -1 and
+//      1e-8 <= alpha <= 1 it is non-finite exactly where R is, for every site alike: those rows count as 0 in the selected sums
+//      and stay in the neutral ones.  The three tables of n_sizes * (F + 1) doubles live in LDS (LDS = true) or in the
+//      window's own part of a workspace in device memory.
+//   2. wave 0 finds the site range with surfaces_kernel's three searches: the sites are exactly its sites.
+//   3. the range is walked in tiles of FIT_THREADS sites: thread tid computes (bin, alpha, size block, own class, tot,
+//      neutral total) of site base + tid into LDS (bin -1: not `in`; tot = 0: the site is skipped, its tot or its neutral
+//      total is not finite and > 0); then thread d * F + c owns cell (d, c) and adds the tile's sites of bin d IN INCREASING SITE
+//      INDEX: same-address LDS reads of the site's numbers, neighbouring addresses of the tables across c.
+// No atomics: a window's numbers are a function of that window and the per-row arrays alone.
+constexpr int FIT_THREADS = 256;
+
+struct FitParams {
+    const double *genpos; RowArray row; int64_t N;
+    const double *R; int rows, npairs;                  // the table [pair][rows]
+    const double *A;
+    const int32_t *row_off; int n_sizes;
+    const double *test_gen; const int64_t *win_lo, *win_hi;
+    const int32_t *tests, *lin;                         // the listed windows of this launch
+    const double *gw; const int32_t *cls; int F;
+    const double *edges; int D;
+    double zcut;
+    double *ws;                                         // [n][3][n_sizes * (F + 1)] when the tables do not live in LDS
+    int32_t *O; double *Esel, *Eneu;                    // [n][D][F]
+    int32_t *skipped;                                   // [n]
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitParams S) {
+    extern __shared__ double fit_tab[];                 // LDS: Gn, Gs, H
+    __shared__ double s_edge[BMX_FIT_MAX_CELLS];
+    __shared__ double s_alpha[FIT_THREADS], s_tot[FIT_THREADS], s_neu[FIT_THREADS];
+    __shared__ int s_bin[FIT_THREADS], s_blk[FIT_THREADS], s_cls[FIT_THREADS];
+    __shared__ int64_t s_range[2];
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    const int F = S.F, D = S.D, W = F + 1, cells = D * F, ntab = S.n_sizes * W;
+    const int32_t lin = S.lin[q];
+    if (lin < 0) {                                      // workgroup-uniform
+        if (tid < cells) {
+            S.O[q * cells + tid] = 0;
+            S.Esel[q * cells + tid] = NAN;
+            S.Eneu[q * cells + tid] = NAN;
+        }
+        if (tid == 0) S.skipped[q] = 0;
+        return;
+    }
+    double *Gn = LDS ? fit_tab : S.ws + (size_t)q * 3 * ntab;
+    double *Gs = Gn + ntab, *H = Gs + ntab;
+    const double *Rs = S.R + (size_t)(lin % S.npairs) * S.rows;
+    const int64_t t = S.tests[q];
+    const double A = S.A[lin / S.npairs], tg = S.test_gen[t], zc = S.zcut;
+    for (int e = tid; e < S.n_sizes * F; e += FIT_THREADS) {
+        const int j = e / F, c = e - j * F;
+        double gn = 0.0, gs = 0.0, h = 0.0;
+        for (int r = S.row_off[j]; r < S.row_off[j + 1]; ++r) {
+            if (S.cls[r] != c) continue;
+            const double w = S.gw[r];
+            if (!(w > 0.0)) continue;
+            gn += w;
+            const double Rr = Rs[r];
+            if (Rr - Rr == 0.0) { gs += w; h += w * Rr; }
+        }
+        Gn[j * W + c] = gn; Gs[j * W + c] = gs; H[j * W + c] = h;
+    }
+    for (int k = tid; k < D - 1; k += FIT_THREADS) s_edge[k] = S.edges[k];
+    if (tid < WAVE) {
+        const int64_t wlo = max(S.win_lo[t], (int64_t)0), whi = min(S.win_hi[t], S.N - 1);
+        const int64_t ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return S.genpos[i] >= tg; });
+        const int64_t a = wave_first_true(wlo, ctr, [&](int64_t i) { return A * fabs(S.genpos[i] - tg) <= zc; });
+        const int64_t b = wave_first_true(ctr, whi + 1, [&](int64_t i) { return !(A * fabs(S.genpos[i] - tg) <= zc); });
+        if (tid == 0) { s_range[0] = a; s_range[1] = b - 1; }
+    }
+    __syncthreads();
+    for (int j = tid; j < S.n_sizes; j += FIT_THREADS) {
+        double gn = 0.0, gs = 0.0, h = 0.0;
+        for (int c = 0; c < F; ++c) { gn += Gn[j * W + c]; gs += Gs[j * W + c]; h += H[j * W + c]; }
+        Gn[j * W + F] = gn; Gs[j * W + F] = gs; H[j * W + F] = h;
+    }
+    __syncthreads();
+    const int64_t rlo = s_range[0], rhi = s_range[1];
+    const bool cell = tid < cells;
+    const int d = tid / F, c = tid - d * F;
+    int o = 0, nskip = 0;
+    double es = 0.0, en = 0.0;
+    for (int64_t base = rlo; base <= rhi; base += FIT_THREADS) {
+        const int64_t i = base + tid;
+        const bool valid = i <= rhi;
+        const double g = valid ? S.genpos[i] : tg;
+        const double z = A * fabs(g - tg);
+        const bool in = valid && z <= zc && g != tg;
+        int bin = -1, j = 0, own = 0;
+        double alpha = 0.0, tot = 0.0, neu = 0.0;
+        if (in) {
+            bin = 0;
+            for (int k = 0; k < D - 1; ++k) bin += z > s_edge[k] ? 1 : 0;
+            const int r0 = min((int)S.row[i], S.rows - 1);       // (set_sites checked every row)
+            int jb = S.n_sizes - 1;                     // the size block of the row: the last j with row_off[j] <= r0
+            while (j < jb) {
+                const int mid = (j + jb + 1) >> 1;
+                if (S.row_off[mid] <= r0) j = mid; else jb = mid - 1;
+            }
+            own = S.cls[r0];
+            alpha = exp(-z);
+            tot = Gs[j * W + F] + alpha * H[j * W + F];
+            neu = Gn[j * W + F];
+            if (!(tot > 0.0 && tot <= DBL_MAX && neu > 0.0 && neu <= DBL_MAX)) tot = 0.0;
+        }
+        s_bin[tid] = bin; s_blk[tid] = j; s_cls[tid] = own;
+        s_alpha[tid] = alpha; s_tot[tid] = tot; s_neu[tid] = neu;
+        nskip += __syncthreads_count(in && !(tot > 0.0));
+        if (cell) {
+            const int cnt = (int)min((int64_t)FIT_THREADS, rhi - base + 1);
+            for (int s = 0; s < cnt; ++s) {
+                if (s_bin[s] != d) continue;
+                o += s_cls[s] == c ? 1 : 0;
+                const double tot_s = s_tot[s];
+                if (tot_s > 0.0) {
+                    const int k = s_blk[s] * W + c;
+                    es += (Gs[k] + s_alpha[s] * H[k]) / tot_s;
+                    en += Gn[k] / s_neu[s];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (cell) {
+        S.O[q * cells + tid] = o;
+        S.Esel[q * cells + tid] = es;
+        S.Eneu[q * cells + tid] = en;
+    }
+    if (tid == 0) S.skipped[q] = nskip;
+}
+
 // Largest double z with exp(-z) >= 1e-8 under correct rounding of exp: bisection on the host.
 double compute_zcut() {
     double lo = 18.0, hi = 19.0;
@@ -5155,6 +5296,11 @@ struct bmx_ctx {
     std::vector<int64_t> if_first, if_off;
     std::vector<double> if_h_tmax, if_h_contrib, if_h_L;
     std::vector<int32_t> if_h_lin, if_h_ns, if_h_m, if_h_blin;
+    // goodness of fit (bmx_ctx_fit): the windows' grid points, the per-row arrays and the bin edges, the workspace of the
+    // windows whose prologue sums do not fit LDS, one chunk's outputs, the events around a chunk's kernel
+    DevBuf<double> ft_gw, ft_edges, ft_ws, ft_Es, ft_En;
+    DevBuf<int32_t> ft_lin, ft_cls, ft_O, ft_skip;
+    DevTimer ft;
     DevBuf<int64_t> gap_sample;
     // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
     int pl_which = 0;
@@ -5480,6 +5626,9 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->if_rng1.release(); c->if_rng.release(); c->if_items.release(); c->if_tmax.release(); c->if_contrib.release();
     c->if_L.release(); c->if_lin.release(); c->if_m.release(); c->if_blin.release();
     c->ifl.release();
+    c->ft_gw.release(); c->ft_edges.release(); c->ft_ws.release(); c->ft_Es.release(); c->ft_En.release();
+    c->ft_lin.release(); c->ft_cls.release(); c->ft_O.release(); c->ft_skip.release();
+    c->ft.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
@@ -6681,6 +6830,85 @@ int bmx_ctx_influence_ms(bmx_ctx *c, double *ms) {
     if (!c->if_have) return fail(BMX_E_STATE, "no influence call yet");
     *ms = c->ifl.ms;
     return BMX_OK;
+}
+
+int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin, const double *gw, const int32_t *cls, int32_t F,
+                const double *edges, int32_t D, int32_t *O_out, double *Esel_out, double *Eneu_out, int32_t *skipped_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (n < 0) return fail(BMX_E_INVALID, "fit: n < 0");
+    if (F < 1 || D < 1 || (int64_t)D * F > BMX_FIT_MAX_CELLS)
+        return fail(BMX_E_INVALID, "fit: F >= 1, D >= 1 and D * F <= BMX_FIT_MAX_CELLS are needed");
+    ChromSlot *s = c->cur;
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before fit");
+    if (n > 0 && (!tests || !lin || !gw || !cls || (D > 1 && !edges) || !O_out || !Esel_out || !Eneu_out))
+        return fail(BMX_E_INVALID, "fit: NULL argument");
+    if (n > 0) {
+        for (int32_t k = 0; k + 1 < D; k++)
+            if (!(edges[k] - edges[k] == 0.0) || !(edges[k] > (k ? edges[k - 1] : 0.0)))
+                return fail(BMX_E_INVALID, "fit: the edges must be finite, > 0 and strictly ascending");
+        for (int r = 0; r < c->rows; r++) {
+            if (cls[r] < 0 || cls[r] >= F) return fail(BMX_E_INVALID, "fit: a class outside [0, F) at row " + std::to_string(r));
+            if (!(gw[r] >= 0.0 && gw[r] <= 1.0)) return fail(BMX_E_INVALID, "fit: gw outside [0, 1] at row " + std::to_string(r));
+        }
+    }
+    const int64_t points = (int64_t)c->nA * c->npairs;
+    for (int64_t q = 0; q < n; q++) {
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "fit: test site index out of range at entry " + std::to_string(q));
+        if (lin[q] >= points) return fail(BMX_E_INVALID, "fit: grid point outside the model's grids at entry " + std::to_string(q));
+    }
+    c->ft.ms = 0.0;
+    if (n == 0) return BMX_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t cells = (size_t)D * F, tab = (size_t)c->n_sizes * (F + 1) * 3;       // doubles of one window's prologue sums
+    const bool in_lds = tab * sizeof(double) <= (size_t)BMX_FIT_LDS_BYTES && c->variant != 1;
+    // a chunk's outputs stay at or below 64 MiB, its workspace (if any) at or below BMX_SURFACES_CHUNK_BYTES
+    int64_t step = std::max<int64_t>((64LL << 20) / (int64_t)(cells * 20), 1);
+    if (!in_lds) step = std::min(step, std::max<int64_t>(BMX_SURFACES_CHUNK_BYTES / (int64_t)(tab * sizeof(double)), 1));
+    step = std::min(step, n);
+    int rc;
+    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
+    if ((rc = upload(c->ft_lin, lin, (size_t)n, c->stream))) return rc;
+    if ((rc = upload(c->ft_gw, gw, (size_t)c->rows, c->stream))) return rc;
+    if ((rc = upload(c->ft_cls, cls, (size_t)c->rows, c->stream))) return rc;
+    if ((rc = upload(c->ft_edges, edges, (size_t)(D - 1), c->stream))) return rc;
+    HIP_TRY(c->ft_O.ensure((size_t)step * cells));
+    HIP_TRY(c->ft_Es.ensure((size_t)step * cells));
+    HIP_TRY(c->ft_En.ensure((size_t)step * cells));
+    HIP_TRY(c->ft_skip.ensure((size_t)step));
+    if (!in_lds) HIP_TRY(c->ft_ws.ensure((size_t)step * tab));
+    FitParams P;
+    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N;
+    P.R = c->d_R; P.rows = c->rows; P.npairs = c->npairs; P.A = c->d_A;
+    P.row_off = c->d_row_off; P.n_sizes = c->n_sizes;
+    P.test_gen = s->test_gen.p; P.win_lo = s->win_lo.p; P.win_hi = s->win_hi.p;
+    P.gw = c->ft_gw.p; P.cls = c->ft_cls.p; P.F = F; P.edges = c->ft_edges.p; P.D = D; P.zcut = c->zcut;
+    P.ws = in_lds ? nullptr : c->ft_ws.p;
+    P.O = c->ft_O.p; P.Esel = c->ft_Es.p; P.Eneu = c->ft_En.p; P.skipped = c->ft_skip.p;
+    double total = 0.0;
+    for (int64_t q0 = 0; q0 < n; q0 += step) {
+        const int64_t m = std::min(step, n - q0);
+        P.tests = c->sfs_list.p + q0; P.lin = c->ft_lin.p + q0;
+        HIP_TRY(c->ft.begin(c->stream));
+        if (in_lds) hipLaunchKernelGGL(fit_kernel<true>, dim3((unsigned)m), dim3(FIT_THREADS), tab * sizeof(double), c->stream, P);
+        else hipLaunchKernelGGL(fit_kernel<false>, dim3((unsigned)m), dim3(FIT_THREADS), 0, c->stream, P);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(c->ft.end(c->stream));
+        HIP_TRY(hipMemcpyAsync(O_out + (size_t)q0 * cells, c->ft_O.p, (size_t)m * cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(Esel_out + (size_t)q0 * cells, c->ft_Es.p, (size_t)m * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(Eneu_out + (size_t)q0 * cells, c->ft_En.p, (size_t)m * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (skipped_out)
+            HIP_TRY(hipMemcpyAsync(skipped_out + q0, c->ft_skip.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->ft.read());
+        total += c->ft.ms;
+    }
+    c->ft.ms = total;        // the call's figure: its chunks' kernels
+    return BMX_OK;
+}
+
+int bmx_ctx_fit_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    return c->ft.get(ms, "no fit call yet");
 }
 
 }  // extern "C"

@@ -514,6 +514,29 @@ class Context:
         """Device milliseconds of the kernels of the context's last influence() call (the surfaces' kernel among them)."""
         return self._ms(self._L.bmx_ctx_influence_ms)
 
+    def fit(self, tests, lin, gw, cls, F, edges):
+        """Observed against expected frequency spectrum by distance (ballermixplus_amd/fit.py) of the listed test sites of the
+        selected slot (any order, repeats allowed), window q at the grid point lin[q] = (iA * nx + ix) * nab + ia (< 0: O all 0,
+        E NaN).  gw f64[rows]: power.allowed_rows(); cls i32[rows] in [0, F): fit.classes(); edges f64[D - 1] ascending.
+        Returns (O i32[n, D, F], E_sel f64[n, D, F], E_neu f64[n, D, F], skipped i32[n])."""
+        t, l = _lib.i32(tests), _lib.i32(lin)
+        if t.ndim != 1 or l.shape != t.shape:
+            raise ValueError('a flat list of test site indices and one grid point per entry are needed')
+        gw, cls, edges = _lib.f64(gw), _lib.i32(cls), _lib.f64(edges)
+        if gw.shape != (self.model.rows,) or cls.shape != gw.shape or edges.ndim != 1:
+            raise ValueError('gw and cls need one entry per table row, edges a flat list')
+        F, D = int(F), len(edges) + 1
+        shape = (len(t), D, max(F, 0))
+        O, skipped = np.empty(shape, dtype=np.int32), np.empty(len(t), dtype=np.int32)
+        Es, En = np.empty(shape), np.empty(shape)
+        _lib.check(self._L.bmx_ctx_fit(self._h, len(t), _lib.as_ip(t), _lib.as_ip(l), _lib.as_dp(gw), _lib.as_ip(cls), F,
+                                       _lib.as_dp(edges), D, _lib.as_ip(O), _lib.as_dp(Es), _lib.as_dp(En), _lib.as_ip(skipped)))
+        return O, Es, En, skipped
+
+    def fit_ms(self):
+        """Device milliseconds of the kernel of the context's last fit() call."""
+        return self._ms(self._L.bmx_ctx_fit_ms)
+
     def fetch_lut(self):
         m = self.model
         shape = (len(m.x), len(m.abeta), m.rows)

@@ -220,6 +220,44 @@ int bmx_ctx_influence_count(bmx_ctx *c, int64_t *n_windows, int64_t *first_block
 int bmx_ctx_fetch_influence(bmx_ctx *c, double *t_max, int32_t *lin, int32_t *ns_min, int32_t *m, double *contrib, double *L,
                             int32_t *block_lin);
 int bmx_ctx_influence_ms(bmx_ctx *c, double *ms);
+/* Goodness of fit of n test sites of the selected slot (listed as for bmx_ctx_surfaces: any order, repeats allowed): the observed
+ * frequency spectrum by distance bin against the counts expected under ONE grid point per window and under neutrality; the
+ * definition is ballermixplus_amd/fit.py.  Window q is test site tests[q] (tg, win_lo, win_hi) with the grid point lin[q] =
+ * (iA * nx + ix) * nab + ia.  Its sites are the surfaces' sites at that A: win_lo <= i <= win_hi, z_i = A * |g_i - tg| <=
+ * bmx_alpha_cut() (that single product), g_i != tg.
+ *   gw[rows]   the caller's: the neutral probability (0 <= gw <= 1) of every admissible (count, sample size), 0 elsewhere
+ *              (power.allowed_rows);  cls[rows] in [0, F): the frequency class of every table row
+ *   edges[D-1] strictly ascending, finite, > 0;  bin(z) = #{k : z > edges[k]} (a site on an edge belongs to the lower bin; the
+ *              last bin runs to the cut)
+ *   for a site of size block j with rows a..b, alpha = exp(-z), R = the table's column of (ix, ia):
+ *       m_r = gw[r] * (1 + alpha * R[r]) where gw[r] > 0, else 0 (the product is not formed: R is NaN where g is); a non-finite
+ *       m_r counts as 0;  tot = sum_r m_r, p_r = m_r / tot;  neutral: q_r = gw[r] / sum_{a..b} gw
+ *   O_out[n][D][F]     the sites per (bin, class of the site's own row)
+ *   Esel_out[n][D][F]  sum over the bin's sites of sum_{r in class} p_r;   Eneu_out[n][D][F] the same of q_r
+ *   skipped_out[n] (may be NULL): the sites whose tot or neutral total is not finite and > 0: counted in O, added to neither E
+ * lin[q] < 0: O all 0, both E NaN, skipped 0.
+ * fit_kernel: one workgroup of 256 per listed window, no atomics; a window's numbers depend on that window and the per-row
+ * arrays alone (bitwise the same alone, in a list, or twice).  With 0 <= gw <= 1, R >= -1 and 0 < alpha <= 1 a product m_r is
+ * non-finite exactly where R[r] is, whatever alpha: such a row is left out of the selected sums for every site (it stays in the
+ * neutral ones), and the class sums are linear in alpha.  The prologue forms, per (size block j, class c) and in ascending
+ * row order, Gn = sum gw, Gs = sum gw over the rows with a finite R and H = sum gw R over the same rows, and their totals over
+ * the classes in ascending c; a site then adds (Gs[j][c] + alpha H[j][c]) / tot, tot = Gs[j][.] + alpha H[j][.], and Gn[j][c] /
+ * Gn[j][.] to the cells of its bin, the sites of a cell in increasing site index.  The sums are staged in LDS while n_sizes *
+ * (F + 1) * 24 bytes fit BMX_FIT_LDS_BYTES and in a per-window workspace in device memory past it (also with
+ * bmx_ctx_set_variant(c, 1), for cross-checks).
+ * BMX_E_INVALID and nothing is written: a NULL context, n < 0, a NULL tests / lin / gw / cls / edges (D > 1) / O_out / Esel_out /
+ * Eneu_out with n > 0, an index outside [0, M), lin >= nA * nx * nab, F < 1, D < 1, D * F > BMX_FIT_MAX_CELLS, an edge that is
+ * not finite, not > 0 or not above the one before, a cls outside [0, F), a gw outside [0, 1] (NaN included).  BMX_E_STATE
+ * without model, sites and test sites; bmx_ctx_fit_ms (milliseconds the last call spent in its kernels) before a successful call
+ * is BMX_E_STATE.  n == 0 succeeds.  Blocks.  Leaves sites, test sites, scan results, records, profiles, refinement, support,
+ * bootstrap, peak, null, influence and locate state of every slot untouched.
+ * Added without a bump of BMX_ABI_VERSION_MINOR, as the groups above: look the symbols up to find out. */
+#define BMX_FIT_MAX_CELLS 256            /* D * F */
+#define BMX_FIT_LDS_BYTES (40 << 10)     /* the prologue's sums of one window in LDS up to here */
+int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin, const double *gw, const int32_t *cls, int32_t F,
+                const double *edges, int32_t D, int32_t *O_out, double *Esel_out, double *Eneu_out,
+                int32_t *skipped_out /* [n], may be NULL */);
+int bmx_ctx_fit_ms(bmx_ctx *c, double *ms);
 /* Choose the scan kernel variant (0 = default). For A/B measurements only. */
 int bmx_ctx_set_variant(bmx_ctx *c, int variant);
 /* Select (creating it on first use) chromosome slot `slot`, 0 <= slot < 4096. */
