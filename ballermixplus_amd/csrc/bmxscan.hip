@@ -3417,6 +3417,10 @@ constexpr int REFINE_TABS = 5;                   // R entries of: the centre, x-
 constexpr int REFINE_EVALS = 7;                  // T of: the centre, u-, u+, x-, x+, v-, v+
 constexpr int REFINE_GRID_MAX = 2048;            // workgroups of a refinement launch (grid-stride over the windows)
 
+// A slot's sites and its windows, as the compass, surfaces, influence and fit kernels take them (window_range, tile_site)
+struct SiteView { const double *genpos; RowArray row; int64_t N; };
+struct WindowView { const double *test_gen; const int64_t *win_lo, *win_hi; double zcut; };
+
 struct RefineParams {
     int stat, min_count, n_sizes, rows;
     const int32_t *sizes, *row_off;
@@ -3428,9 +3432,7 @@ struct RefineParams {
     double lo[3], hi[3], tol[3];       // hull and tolerance of u, x, v
     int fr[3];                         // 1: the coordinate is free
     int max_rounds;
-    const double *genpos; RowArray row; int64_t N;
-    const double *test_gen; const int64_t *win_lo, *win_hi;
-    double zcut;
+    SiteView sites; WindowView win;
     const int32_t *list; const int64_t *count;     // refine: the windows to refine; point evaluation: nullptr (all M)
     int64_t M;
     const int32_t *lin; const double *clr;         // refine: the last scan
@@ -3539,6 +3541,36 @@ __device__ __forceinline__ int64_t wave_first_true(int64_t a, int64_t b, F pred)
     return b;
 }
 
+// ---- the sites of window t at one A: i in [max(win_lo, 0), min(win_hi, N - 1)] with A |g_i - tg| <= zcut and g_i != tg, stated
+// once for the surfaces, influence and fit kernels.  (The scan kernels, surface_kernel -- the single-window cross-check -- and the
+// compass kernels keep their own text: compass_begin and compass_round run these searches apart, and sharing them through a
+// split helper moved refine_kernel's schedule and cost it time, profiles/listed_window_fold.txt.)
+// All 64 lanes of a wave: the first site of the clipped window at or right of tg (ctr), and around it -- A |g_i - tg| being
+// monotone on either side -- the sites [a, b) that A's cut can hold.
+struct SiteRange { int64_t ctr, a, b; };
+__device__ __forceinline__ SiteRange window_range(const SiteView &V, const WindowView &W, int64_t t, double tg, double A) {
+    const int64_t wlo = max(W.win_lo[t], (int64_t)0), whi = min(W.win_hi[t], V.N - 1);
+    const double zc = W.zcut;
+    SiteRange R;
+    R.ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return V.genpos[i] >= tg; });
+    R.a = wave_first_true(wlo, R.ctr, [&](int64_t i) { return A * fabs(V.genpos[i] - tg) <= zc; });
+    R.b = wave_first_true(R.ctr, whi + 1, [&](int64_t i) { return !(A * fabs(V.genpos[i] - tg) <= zc); });
+    return R;
+}
+
+// Site i = base + tid of a tile over [.., hi]: is it one of A's sites (`in`), and its z = A |g_i - tg|; its (alpha, row) into the
+// workgroup's tile (row -1: not `in`); the term a pair p adds for the tile's entry (alpha_s, r_s >= 0)
+__device__ __forceinline__ bool tile_site(const double *genpos, int64_t i, int64_t hi, double tg, double A, double zc, double &z) {
+    const bool valid = i <= hi;
+    const double g = valid ? genpos[i] : tg;
+    z = A * fabs(g - tg);
+    return valid && z <= zc && g != tg;
+}
+__device__ __forceinline__ void tile_store(const RowArray &row, int64_t i, bool in, double z, double *s_alpha, int *s_row) {
+    s_alpha[threadIdx.x] = in ? exp(-z) : 0.0; s_row[threadIdx.x] = in ? (int)row[i] : -1;
+}
+__device__ __forceinline__ double tile_term(double alpha_s, int r_s, const double *Rt, int NP, int p) { return log1p(alpha_s * Rt[(size_t)r_s * NP + p]); }
+
 __device__ const uint64_t BOOT_THR[20] = {     // floor(2^64 * Poisson(1).cdf(k)), k = 0..19 (boot.py THR)
     6786177901268885274ull, 13572355802537770549ull, 16965444753172213186ull, 18096474403383694065ull, 18379231815936564285ull,
     18435783298447138329ull, 18445208545532234003ull, 18446555009401533385ull, 18446723317385195808ull, 18446742018272269410ull,
@@ -3641,14 +3673,14 @@ __device__ __forceinline__ void compass_begin(const RefineParams &P, RefineState
         for (int k = 0; k < 3; ++k) { S.c[k] = S.c0[k]; S.nat[k] = S.nat0[k]; }
         S.Tc = -INFINITY; S.nsc = 0; S.have_c = 0; S.rounds = 0;
         S.built_rv0 = -1; S.rangeA = 0.0; S.rv = 0; S.nused = 0;
-        S.tg = P.test_gen[t];
-        S.wlo = max(P.win_lo[t], (int64_t)0);
-        S.whi = min(P.win_hi[t], P.N - 1);
+        S.tg = P.win.test_gen[t];
+        S.wlo = max(P.win.win_lo[t], (int64_t)0);
+        S.whi = min(P.win.win_hi[t], P.sites.N - 1);
     }
     __syncthreads();
     if (threadIdx.x / WAVE == 0) {
         const double tg = S.tg;
-        const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.genpos[i] >= tg; });
+        const int64_t ctr = wave_first_true(S.wlo, S.whi + 1, [&](int64_t i) { return P.sites.genpos[i] >= tg; });
         if (threadIdx.x % WAVE == 0) S.ctr = ctr;
     }
 }
@@ -3712,15 +3744,15 @@ __device__ __forceinline__ bool compass_round(const RefineParams &P, RefineState
     if (S.valid[2]) Amin = min(Amin, S.Aev[2]);
     if (Amin != S.rangeA) {
         if (wave == 0) {
-            const double zc = P.zcut;
+            const double zc = P.win.zcut;
             const int64_t ctr = S.ctr;
-            const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.genpos[i] - tg) <= zc; });
-            const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.genpos[i] - tg) <= zc); });
+            const int64_t a = wave_first_true(S.wlo, ctr, [&](int64_t i) { return Amin * fabs(P.sites.genpos[i] - tg) <= zc; });
+            const int64_t b = wave_first_true(ctr, S.whi + 1, [&](int64_t i) { return !(Amin * fabs(P.sites.genpos[i] - tg) <= zc); });
             if (lane == 0) { S.rlo = a; S.rhi = b - 1; }
         }
         for (int r = tid; r < P.rows; r += REFINE_THREADS) ws.map[r] = 0;
         __syncthreads();
-        for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) ws.map[P.row[i]] = 1;
+        for (int64_t i = S.rlo + tid; i <= S.rhi; i += REFINE_THREADS) ws.map[P.sites.row[i]] = 1;
         __syncthreads();
         int base = 0;
         for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
@@ -3761,7 +3793,7 @@ __device__ __forceinline__ bool compass_round(const RefineParams &P, RefineState
     {
         int vmask = 0;
         for (int e = 0; e < REFINE_EVALS; ++e) vmask |= S.valid[e] << e;
-        const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.zcut;
+        const double A0 = S.Aev[0], A1 = S.Aev[1], A2 = S.Aev[2], zc = P.win.zcut;
         const int64_t lo = S.rlo, hi = S.rhi;
         int64_t i = lo - (lo % REFINE_THREADS) + tid;
         if (i < lo) i += REFINE_THREADS;
@@ -3770,8 +3802,8 @@ __device__ __forceinline__ bool compass_round(const RefineParams &P, RefineState
             const int wi = wt.next();
             if (wi == 0) continue;
             const double wd = (double)wi;
-            const double gi = P.genpos[i];
-            const int r = P.row[i];
+            const double gi = P.sites.genpos[i];
+            const int r = P.sites.row[i];
             const double d = fabs(gi - tg);
             const bool same = gi == tg;
             const double z0 = A0 * d, z1 = A1 * d, z2 = A2 * d;
@@ -4582,24 +4614,20 @@ __global__ __launch_bounds__(PEAK_THREADS) void peak_extent_kernel(const double 
 // surface_kernel's T[iA][pair] for a LIST of test sites of the slot in one launch (bmx_ctx_surfaces; the definition and the
 // CLI's selection rule are ballermixplus_amd/surfaces.py).  One workgroup of SURFS_THREADS per (listed window q, iA, slice of
 // SURFS_THREADS pairs); thread tid owns pair p = slice * SURFS_THREADS + tid.
-//   1. wave 0 finds the inclusive site range of this A inside the window -- A |g_i - tg| <= zcut, monotone in |g_i - tg| on
-//      either side of the first site at or right of tg -- with wave_first_true, as refine_kernel does: a window at A = 1e8
-//      reads a few dozen positions, not the chromosome.  The range goes to the workgroup through LDS.
-//   2. the range is walked in tiles of SURFS_THREADS sites: thread tid computes (alpha, row, in) of site base + tid into LDS
-//      (row -1: not `in`), the barrier counts the `in` sites, and every thread then adds log1p(alpha_s R[row_s][p]) over the
-//      tile's `in` sites IN INCREASING SITE INDEX: same-address LDS reads, R reads coalesced across p.
+//   1. wave 0 finds the inclusive site range of this A inside the window (window_range: a window at A = 1e8 reads a few dozen
+//      positions, not the chromosome); it goes to the workgroup through LDS.
+//   2. the range is walked in tiles of SURFS_THREADS sites: tile_site and tile_store put (alpha, row) of site base + tid into LDS, the
+//      barrier counts the `in` sites, every thread adds tile_term over them IN INCREASING SITE INDEX (same-address LDS reads, R coalesced).
 // Each pair's sum therefore runs over surface_kernel's sites in surface_kernel's order with surface_kernel's expression (the
 // sites outside the range are exactly those it skips), so T and nSites are bitwise what bmx_ctx_surface returns for the
 // window.  No atomics: a window's result is a function of that window alone.
 constexpr int SURFS_THREADS = 256;
 
 struct SurfsParams {
-    const double *genpos; RowArray row; int64_t N;
+    SiteView sites; WindowView win;
     const double *Rt; int NP, npairs, nslices;      // nslices: slices of SURFS_THREADS pairs
     const double *A; int nA;
-    const double *test_gen; const int64_t *win_lo, *win_hi;
     const int32_t *tests;                            // the listed test sites of this launch
-    double zcut;
     double *T;        // [n][nA][npairs]
     int32_t *ns;      // [n][nA]
 };
@@ -4615,32 +4643,24 @@ __global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) 
     const int p = slice * SURFS_THREADS + tid;
     const bool live = p < S.npairs;                 // (p may lie beyond the padded row of R: an idle thread reads nothing)
     const int64_t t = S.tests[q];
-    const double A = S.A[iA], tg = S.test_gen[t], zc = S.zcut;
+    const double A = S.A[iA], tg = S.win.test_gen[t];
     if (tid < WAVE) {
-        const int64_t wlo = max(S.win_lo[t], (int64_t)0), whi = min(S.win_hi[t], S.N - 1);
-        const int64_t ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return S.genpos[i] >= tg; });
-        const int64_t a = wave_first_true(wlo, ctr, [&](int64_t i) { return A * fabs(S.genpos[i] - tg) <= zc; });
-        const int64_t b = wave_first_true(ctr, whi + 1, [&](int64_t i) { return !(A * fabs(S.genpos[i] - tg) <= zc); });
-        if (tid == 0) { s_range[0] = a; s_range[1] = b - 1; }
+        const SiteRange R = window_range(S.sites, S.win, t, tg, A);
+        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
     }
     __syncthreads();
     const int64_t rlo = s_range[0], rhi = s_range[1];
-    double sum = 0.0;
+    double sum = 0.0, z;
     int ns = 0;
     for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
-        const int64_t i = base + tid;
-        const bool valid = i <= rhi;
-        const double g = valid ? S.genpos[i] : tg;
-        const double z = A * fabs(g - tg);
-        const bool in = valid && z <= zc && g != tg;
-        s_alpha[tid] = in ? exp(-z) : 0.0;
-        s_row[tid] = in ? (int)S.row[i] : -1;
+        const bool in = tile_site(S.sites.genpos, base + tid, rhi, tg, A, S.win.zcut, z);
+        tile_store(S.sites.row, base + tid, in, z, s_alpha, s_row);
         ns += __syncthreads_count(in);
         if (live) {
             const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
             for (int s = 0; s < cnt; ++s) {
                 const int r_s = s_row[s];
-                if (r_s >= 0) sum += log1p(s_alpha[s] * S.Rt[(size_t)r_s * S.NP + p]);
+                if (r_s >= 0) sum += tile_term(s_alpha[s], r_s, S.Rt, S.NP, p);
             }
         }
         __syncthreads();
@@ -4655,11 +4675,11 @@ __global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) 
 // influence_argmax_kernel T_max and lin*, and influence_kernel the blocks.
 //   influence_kernel: one workgroup of INFL_THREADS per (listed window, run of up to INFL_BLOCKS consecutive blocks of its
 //   range); thread tid owns the pairs p = slice * INFL_THREADS + tid.  For every (iA, slice) the run's sites inside that A's
-//   range are walked in tiles of INFL_THREADS sites exactly as surfaces_kernel walks them (thread tid computes (alpha, row) of
-//   site base + tid into LDS, every thread adds log1p(alpha_s R[row_s][p]) over the `in` sites in increasing site index), with
-//   the sum restarted at every block boundary: S_b has surfaces_kernel's expression and order, so a block that holds every
-//   qualifying site of an A has S_b == S bitwise.  At a boundary the thread forms T - 2 S_b and keeps its running best (value,
-//   lin) of that block in its own column of an LDS table; one fixed-order workgroup reduction per block ends the workgroup.
+//   range are walked in tiles of INFL_THREADS sites through surfaces_kernel's helpers (tile_site, tile_store, then tile_term over
+//   the `in` sites in increasing site index), the sum restarted at every block boundary: S_b has surfaces_kernel's expression by
+//   construction and its order, so a block that holds every qualifying site of an A has S_b == S bitwise.  At a boundary the thread
+//   forms T - 2 S_b and keeps its running best (value, lin) of that block in its own column of an LDS table; one fixed-order
+//   workgroup reduction per block ends the workgroup.
 // No atomics.  A block's numbers depend on its window and B alone: a run only decides which workgroup computes them.
 constexpr int INFL_THREADS = 256;
 constexpr int INFL_BLOCKS = 8;
@@ -4686,25 +4706,20 @@ __device__ __forceinline__ void infl_wg_best(double &v, int32_t &l, double *s_v,
 }
 
 struct InflRangeParams {
-    const double *genpos; int64_t N;
+    SiteView sites; WindowView win;
     const double *A; int nA;
-    const double *test_gen; const int64_t *win_lo, *win_hi;
     const int32_t *tests; int64_t n;
-    double zcut;
-    int64_t *rng;     // [n][nA][4]: the inclusive range of A (surfaces_kernel's), the first and last QUALIFYING site (first > last: none)
+    int64_t *rng;     // [n][nA][4]: the inclusive range of A (window_range's), the first and last QUALIFYING site (first > last: none)
 };
 
-// One wave per (listed window, A): surfaces_kernel's three searches, and the end of the run of sites at the test position.
+// One wave per (listed window, A): window_range, and the end of the run of sites at the test position.
 __global__ __launch_bounds__(INFL_THREADS) void influence_range_kernel(InflRangeParams S) {
     const int64_t w = (int64_t)blockIdx.x * (INFL_THREADS / WAVE) + threadIdx.x / WAVE;        // wave-uniform
     if (w >= S.n * S.nA) return;
     const int64_t t = S.tests[w / S.nA];
-    const double A = S.A[w % S.nA], tg = S.test_gen[t], zc = S.zcut;
-    const int64_t wlo = max(S.win_lo[t], (int64_t)0), whi = min(S.win_hi[t], S.N - 1);
-    const int64_t ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return S.genpos[i] >= tg; });
-    const int64_t a = wave_first_true(wlo, ctr, [&](int64_t i) { return A * fabs(S.genpos[i] - tg) <= zc; });
-    const int64_t b = wave_first_true(ctr, whi + 1, [&](int64_t i) { return !(A * fabs(S.genpos[i] - tg) <= zc); });
-    const int64_t e = wave_first_true(ctr, b, [&](int64_t i) { return S.genpos[i] > tg; });
+    const double A = S.A[w % S.nA], tg = S.win.test_gen[t];
+    const SiteRange R = window_range(S.sites, S.win, t, tg, A);
+    const int64_t ctr = R.ctr, a = R.a, b = R.b, e = wave_first_true(ctr, b, [&](int64_t i) { return S.sites.genpos[i] > tg; });
     if (threadIdx.x % WAVE == 0) {
         int64_t *o = S.rng + (size_t)w * 4;
         o[0] = a; o[1] = b - 1;
@@ -4732,11 +4747,10 @@ struct InflItem {
 };
 
 struct InflParams {
-    const double *genpos; RowArray row;
+    SiteView sites; WindowView win;
     const double *Rt; int NP, npairs, nslices;
     const double *A; int nA, iAmin;
-    const double *test_gen; const int32_t *tests;       // the chunk's listed test sites
-    double zcut;
+    const int32_t *tests;                               // the chunk's listed test sites
     int64_t B;
     const double *T; const int32_t *ns;                 // the chunk's surfaces: [m][nA][npairs], [m][nA]
     const int64_t *rng;                                 // [m][nA][4]
@@ -4759,7 +4773,7 @@ __global__ __launch_bounds__(INFL_THREADS) void influence_kernel(InflParams S) {
     const int64_t ifirst = rq[S.iAmin * 4 + 2], ilast = rq[S.iAmin * 4 + 3];
     const int nblk = (int)min((int64_t)INFL_BLOCKS, ilast / B - it.b0 + 1);
     const int64_t clo = max(it.b0 * B, ifirst), chi = min((it.b0 + nblk) * B - 1, ilast);      // the run's sites
-    const double tg = S.test_gen[S.tests[q]], zc = S.zcut;
+    const double tg = S.win.test_gen[S.tests[q]];
     const int32_t linstar = S.lin[q];
     for (int k = 0; k < nblk; ++k) { s_bv[k][tid] = 0.0; s_bl[k][tid] = -1; }       // (a thread's own column: no barrier)
     // the thread's best T over the A's whose range the run does not reach: there n_b = 0 for every block of the run, so T itself
@@ -4787,7 +4801,7 @@ __global__ __launch_bounds__(INFL_THREADS) void influence_kernel(InflParams S) {
             // block k of the run ends at site kend; (sum, nb) are S_b and n_b of the block being walked
             int k = 0, nb = 0;
             int64_t kend = (it.b0 + 1) * B - 1;
-            double sum = 0.0;
+            double sum = 0.0, z;
             auto close = [&]() {
                 if (iA == S.iAmin && slice == 0 && tid == 0) S.m_out[it.out + k] = nb;
                 if (live) {
@@ -4802,20 +4816,15 @@ __global__ __launch_bounds__(INFL_THREADS) void influence_kernel(InflParams S) {
                 ++k; kend += B; nb = 0; sum = 0.0;
             };
             for (int64_t base = lo; base <= hi; base += INFL_THREADS) {
-                const int64_t i = base + tid;
-                const bool valid = i <= hi;
-                const double g = valid ? S.genpos[i] : tg;
-                const double z = A * fabs(g - tg);
-                const bool in = valid && z <= zc && g != tg;
-                s_alpha[tid] = in ? exp(-z) : 0.0;
-                s_row[tid] = in ? (int)S.row[i] : -1;
+                const bool in = tile_site(S.sites.genpos, base + tid, hi, tg, A, S.win.zcut, z);
+                tile_store(S.sites.row, base + tid, in, z, s_alpha, s_row);
                 __syncthreads();
                 const int cnt = (int)min((int64_t)INFL_THREADS, hi - base + 1);
                 for (int s = 0; s < cnt; ++s) {
                     while (base + s > kend) close();
                     const int r_s = s_row[s];
                     if (r_s >= 0) {                 // wave-uniform: the one log1p of the kernel
-                        sum += log1p(s_alpha[s] * S.Rt[(size_t)r_s * S.NP + pr]);
+                        sum += tile_term(s_alpha[s], r_s, S.Rt, S.NP, pr);
                         ++nb;
                     }
                 }
@@ -4847,24 +4856,22 @@ __global__ __launch_bounds__(INFL_THREADS) void influence_kernel(InflParams S) {
 //      1e-8 <= alpha <= 1 it is non-finite exactly where R is, for every site alike: those rows count as 0 in the selected sums
 //      and stay in the neutral ones.  The three tables of n_sizes * (F + 1) doubles live in LDS (LDS = true) or in the
 //      window's own part of a workspace in device memory.
-//   2. wave 0 finds the site range with surfaces_kernel's three searches: the sites are exactly its sites.
+//   2. wave 0 finds the site range with window_range: the sites are exactly surfaces_kernel's.
 //   3. the range is walked in tiles of FIT_THREADS sites: thread tid computes (bin, alpha, size block, own class, tot,
-//      neutral total) of site base + tid into LDS (bin -1: not `in`; tot = 0: the site is skipped, its tot or its neutral
+//      neutral total) of site base + tid into LDS (bin -1: not `in` by tile_site; tot = 0: the site is skipped, its tot or its neutral
 //      total is not finite and > 0); then thread d * F + c owns cell (d, c) and adds the tile's sites of bin d IN INCREASING SITE
 //      INDEX: same-address LDS reads of the site's numbers, neighbouring addresses of the tables across c.
 // No atomics: a window's numbers are a function of that window and the per-row arrays alone.
 constexpr int FIT_THREADS = 256;
 
 struct FitParams {
-    const double *genpos; RowArray row; int64_t N;
+    SiteView sites; WindowView win;
     const double *R; int rows, npairs;                  // the table [pair][rows]
     const double *A;
     const int32_t *row_off; int n_sizes;
-    const double *test_gen; const int64_t *win_lo, *win_hi;
     const int32_t *tests, *lin;                         // the listed windows of this launch
     const double *gw; const int32_t *cls; int F;
     const double *edges; int D;
-    double zcut;
     double *ws;                                         // [n][3][n_sizes * (F + 1)] when the tables do not live in LDS
     int32_t *O; double *Esel, *Eneu;                    // [n][D][F]
     int32_t *skipped;                                   // [n]
@@ -4894,7 +4901,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitParams S) {
     double *Gs = Gn + ntab, *H = Gs + ntab;
     const double *Rs = S.R + (size_t)(lin % S.npairs) * S.rows;
     const int64_t t = S.tests[q];
-    const double A = S.A[lin / S.npairs], tg = S.test_gen[t], zc = S.zcut;
+    const double A = S.A[lin / S.npairs], tg = S.win.test_gen[t];
     for (int e = tid; e < S.n_sizes * F; e += FIT_THREADS) {
         const int j = e / F, c = e - j * F;
         double gn = 0.0, gs = 0.0, h = 0.0;
@@ -4910,11 +4917,8 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitParams S) {
     }
     for (int k = tid; k < D - 1; k += FIT_THREADS) s_edge[k] = S.edges[k];
     if (tid < WAVE) {
-        const int64_t wlo = max(S.win_lo[t], (int64_t)0), whi = min(S.win_hi[t], S.N - 1);
-        const int64_t ctr = wave_first_true(wlo, whi + 1, [&](int64_t i) { return S.genpos[i] >= tg; });
-        const int64_t a = wave_first_true(wlo, ctr, [&](int64_t i) { return A * fabs(S.genpos[i] - tg) <= zc; });
-        const int64_t b = wave_first_true(ctr, whi + 1, [&](int64_t i) { return !(A * fabs(S.genpos[i] - tg) <= zc); });
-        if (tid == 0) { s_range[0] = a; s_range[1] = b - 1; }
+        const SiteRange R = window_range(S.sites, S.win, t, tg, A);
+        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
     }
     __syncthreads();
     for (int j = tid; j < S.n_sizes; j += FIT_THREADS) {
@@ -4927,19 +4931,15 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitParams S) {
     const bool cell = tid < cells;
     const int d = tid / F, c = tid - d * F;
     int o = 0, nskip = 0;
-    double es = 0.0, en = 0.0;
+    double es = 0.0, en = 0.0, z;
     for (int64_t base = rlo; base <= rhi; base += FIT_THREADS) {
-        const int64_t i = base + tid;
-        const bool valid = i <= rhi;
-        const double g = valid ? S.genpos[i] : tg;
-        const double z = A * fabs(g - tg);
-        const bool in = valid && z <= zc && g != tg;
+        const bool in = tile_site(S.sites.genpos, base + tid, rhi, tg, A, S.win.zcut, z);
         int bin = -1, j = 0, own = 0;
         double alpha = 0.0, tot = 0.0, neu = 0.0;
         if (in) {
             bin = 0;
             for (int k = 0; k < D - 1; ++k) bin += z > s_edge[k] ? 1 : 0;
-            const int r0 = min((int)S.row[i], S.rows - 1);       // (set_sites checked every row)
+            const int r0 = min((int)S.sites.row[base + tid], S.rows - 1);       // (set_sites checked every row)
             int jb = S.n_sizes - 1;                     // the size block of the row: the last j with row_off[j] <= r0
             while (j < jb) {
                 const int mid = (j + jb + 1) >> 1;
@@ -5394,6 +5394,26 @@ hipError_t flag_prefix(bmx_ctx *c, const int32_t *flag, int64_t n) {
 hipError_t flag_compact(bmx_ctx *c, const int32_t *flag, int64_t n, int32_t *list) {
     hipLaunchKernelGGL(refine_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, flag, (const int64_t *)c->rf_pre.p, n, list);
     return hipGetLastError();
+}
+
+// ---- shared by the entry points over windows listed by test-site index: a slot's sites and windows for their kernels ...
+SiteView site_view(const ChromSlot *s) { return SiteView{s->genpos.p, s->row_array(), s->N}; }
+WindowView window_view(const bmx_ctx *c, const ChromSlot *s) { return WindowView{s->test_gen.p, s->win_lo.p, s->win_hi.p, c->zcut}; }
+// ... what bmx_ctx_surfaces, _influence and _fit refuse before they look at the list's entries, in their common order, `who` in
+// front: n < 0, the entry point's own argument refusal (`own`, nullptr: none), the slot's state, with n > 0 a NULL argument ...
+int list_ready(bmx_ctx *c, const std::string &who, int64_t n, const char *own, bool null_arg) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    if (n < 0) return fail(BMX_E_INVALID, who + ": n < 0");
+    if (own) return fail(BMX_E_INVALID, who + ": " + own);
+    if (!c->cur->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before " + who);
+    if (n > 0 && null_arg) return fail(BMX_E_INVALID, who + ": NULL argument");
+    return BMX_OK;
+}
+// ... and the windows per launch of surfaces_kernel (nsl slices of SURFS_THREADS pairs): their surfaces within BMX_SURFACES_CHUNK_BYTES,
+// their workgroups within a launch's 2^32 threads (set_model bounds nA * npairs below 2^31, so one window's always fit)
+int64_t surfaces_step(const bmx_ctx *c, int nsl) {
+    const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / ((size_t)c->nA * c->npairs * sizeof(double)), 1);
+    return std::min(chunk, std::max<int64_t>((0xffffffffLL / SURFS_THREADS) / ((int64_t)c->nA * nsl), 1));
 }
 
 int validate_model(const bmx_model *m) {
@@ -6632,30 +6652,22 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
 }
 
 int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out, int32_t *nsites_out) {
-    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
-    if (n < 0) return fail(BMX_E_INVALID, "surfaces: n < 0");
-    ChromSlot *s = c->cur;
-    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before surfaces");
+    int rc;
+    if ((rc = list_ready(c, "surfaces", n, nullptr, !tests || !T_out))) return rc;
     if (n == 0) return BMX_OK;
-    if (!tests || !T_out) return fail(BMX_E_INVALID, "surfaces: NULL argument");
+    ChromSlot *s = c->cur;
     for (int64_t q = 0; q < n; q++)
         if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "surfaces: test site index out of range at entry " + std::to_string(q));
     HIP_TRY(hipSetDevice(c->device));
     const size_t per = (size_t)c->nA * c->npairs;              // doubles of one window's surface
-    const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / (per * sizeof(double)), 1);
     const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
-    // a launch holds fewer than 2^32 threads, i.e. fewer than 2^24 workgroups of SURFS_THREADS: a chunk's workgroups must fit
-    // (set_model bounds nA * npairs below 2^31, so one window's always do)
-    const int64_t fit = std::max<int64_t>((0xffffffffLL / SURFS_THREADS) / ((int64_t)c->nA * nsl), 1);
-    const int64_t step = std::min(chunk, fit);
-    HIP_TRY(c->sfs_list.ensure((size_t)n));
+    const int64_t step = surfaces_step(c, nsl);
     HIP_TRY(c->sfs_T.ensure((size_t)std::min<int64_t>(step, n) * per));
     HIP_TRY(c->sfs_ns.ensure((size_t)std::min<int64_t>(step, n) * c->nA));
-    HIP_TRY(hipMemcpyAsync(c->sfs_list.p, tests, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
     SurfsParams S;
-    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N;
+    S.sites = site_view(s); S.win = window_view(c, s);
     S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
-    S.test_gen = s->test_gen.p; S.win_lo = s->win_lo.p; S.win_hi = s->win_hi.p; S.zcut = c->zcut;
     S.T = c->sfs_T.p; S.ns = c->sfs_ns.p;
     double total = 0.0;
     for (int64_t q0 = 0; q0 < n; q0 += step) {
@@ -6683,12 +6695,9 @@ int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms) {
 }
 
 int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block) {
-    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
-    if (n < 0) return fail(BMX_E_INVALID, "influence: n < 0");
-    if (block < 1) return fail(BMX_E_INVALID, "influence: block < 1");
+    int rc;
+    if ((rc = list_ready(c, "influence", n, block < 1 ? "block < 1" : nullptr, !tests))) return rc;
     ChromSlot *s = c->cur;
-    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before influence");
-    if (n > 0 && !tests) return fail(BMX_E_INVALID, "influence: NULL argument");
     for (int64_t q = 0; q < n; q++)
         if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "influence: test site index out of range at entry " + std::to_string(q));
     c->if_have = false;
@@ -6701,11 +6710,10 @@ int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block
     HIP_TRY(hipSetDevice(c->device));
     const int64_t B = std::min(block, std::max<int64_t>(s->N, 1));        // i / B is 0 for every site either way
     const int iAmin = (int)(std::min_element(c->h_A.begin(), c->h_A.end()) - c->h_A.begin());
-    HIP_TRY(c->sfs_list.ensure((size_t)n));
-    HIP_TRY(hipMemcpyAsync(c->sfs_list.p, tests, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
     // 1. every listed window's qualifying sites at A_min -> its block range and the offsets of the per-block arrays
     InflRangeParams Q;
-    Q.genpos = s->genpos.p; Q.N = s->N; Q.test_gen = s->test_gen.p; Q.win_lo = s->win_lo.p; Q.win_hi = s->win_hi.p; Q.zcut = c->zcut;
+    Q.sites = site_view(s); Q.win = window_view(c, s);
     std::vector<int64_t> h_rng((size_t)n * 4);
     const int64_t rstep = 1 << 20;
     HIP_TRY(c->if_rng1.ensure((size_t)std::min(rstep, n) * 4));
@@ -6730,18 +6738,15 @@ int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block
     c->if_h_m.assign(total, 0); c->if_h_contrib.assign(total, 0.0); c->if_h_L.assign(total, 0.0); c->if_h_blin.assign(total, -1);
     // 2. chunks of windows: as many as bmx_ctx_surfaces takes at a time, and at most INFL_CHUNK_BLOCKS blocks (one window if it has more)
     const size_t per = (size_t)c->nA * c->npairs;
-    const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / (per * sizeof(double)), 1);
     const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
-    const int64_t fit = std::max<int64_t>((0xffffffffLL / SURFS_THREADS) / ((int64_t)c->nA * nsl), 1);
-    const int64_t step = std::min(chunk, fit);
+    const int64_t step = surfaces_step(c, nsl);
     const int64_t INFL_CHUNK_BLOCKS = 1 << 22;
     SurfsParams S;
-    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N;
+    S.sites = Q.sites; S.win = Q.win;
     S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
-    S.test_gen = s->test_gen.p; S.win_lo = s->win_lo.p; S.win_hi = s->win_hi.p; S.zcut = c->zcut;
     InflParams P;
-    P.genpos = s->genpos.p; P.row = s->row_array(); P.Rt = c->d_Rt; P.NP = c->NP; P.npairs = c->npairs; P.nslices = nsl;
-    P.A = c->d_A; P.nA = c->nA; P.iAmin = iAmin; P.test_gen = s->test_gen.p; P.zcut = c->zcut; P.B = B;
+    P.sites = Q.sites; P.win = Q.win; P.Rt = c->d_Rt; P.NP = c->NP; P.npairs = c->npairs; P.nslices = nsl;
+    P.A = c->d_A; P.nA = c->nA; P.iAmin = iAmin; P.B = B;
     std::vector<InflItem> items;
     std::vector<int32_t> h_ns;
     double total_ms = 0.0;
@@ -6834,14 +6839,11 @@ int bmx_ctx_influence_ms(bmx_ctx *c, double *ms) {
 
 int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin, const double *gw, const int32_t *cls, int32_t F,
                 const double *edges, int32_t D, int32_t *O_out, double *Esel_out, double *Eneu_out, int32_t *skipped_out) {
-    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
-    if (n < 0) return fail(BMX_E_INVALID, "fit: n < 0");
-    if (F < 1 || D < 1 || (int64_t)D * F > BMX_FIT_MAX_CELLS)
-        return fail(BMX_E_INVALID, "fit: F >= 1, D >= 1 and D * F <= BMX_FIT_MAX_CELLS are needed");
+    const bool cells_ok = F >= 1 && D >= 1 && (int64_t)D * F <= BMX_FIT_MAX_CELLS;
+    int rc = list_ready(c, "fit", n, cells_ok ? nullptr : "F >= 1, D >= 1 and D * F <= BMX_FIT_MAX_CELLS are needed",
+                        !tests || !lin || !gw || !cls || (D > 1 && !edges) || !O_out || !Esel_out || !Eneu_out);
+    if (rc) return rc;
     ChromSlot *s = c->cur;
-    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before fit");
-    if (n > 0 && (!tests || !lin || !gw || !cls || (D > 1 && !edges) || !O_out || !Esel_out || !Eneu_out))
-        return fail(BMX_E_INVALID, "fit: NULL argument");
     if (n > 0) {
         for (int32_t k = 0; k + 1 < D; k++)
             if (!(edges[k] - edges[k] == 0.0) || !(edges[k] > (k ? edges[k - 1] : 0.0)))
@@ -6865,7 +6867,6 @@ int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin,
     int64_t step = std::max<int64_t>((64LL << 20) / (int64_t)(cells * 20), 1);
     if (!in_lds) step = std::min(step, std::max<int64_t>(BMX_SURFACES_CHUNK_BYTES / (int64_t)(tab * sizeof(double)), 1));
     step = std::min(step, n);
-    int rc;
     if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
     if ((rc = upload(c->ft_lin, lin, (size_t)n, c->stream))) return rc;
     if ((rc = upload(c->ft_gw, gw, (size_t)c->rows, c->stream))) return rc;
@@ -6877,11 +6878,10 @@ int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin,
     HIP_TRY(c->ft_skip.ensure((size_t)step));
     if (!in_lds) HIP_TRY(c->ft_ws.ensure((size_t)step * tab));
     FitParams P;
-    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N;
+    P.sites = site_view(s); P.win = window_view(c, s);
     P.R = c->d_R; P.rows = c->rows; P.npairs = c->npairs; P.A = c->d_A;
     P.row_off = c->d_row_off; P.n_sizes = c->n_sizes;
-    P.test_gen = s->test_gen.p; P.win_lo = s->win_lo.p; P.win_hi = s->win_hi.p;
-    P.gw = c->ft_gw.p; P.cls = c->ft_cls.p; P.F = F; P.edges = c->ft_edges.p; P.D = D; P.zcut = c->zcut;
+    P.gw = c->ft_gw.p; P.cls = c->ft_cls.p; P.F = F; P.edges = c->ft_edges.p; P.D = D;
     P.ws = in_lds ? nullptr : c->ft_ws.p;
     P.O = c->ft_O.p; P.Esel = c->ft_Es.p; P.Eneu = c->ft_En.p; P.skipped = c->ft_skip.p;
     double total = 0.0;
@@ -6954,8 +6954,7 @@ int refine_setup(bmx_ctx *c, ChromSlot *s, RefineParams &P, int max_rounds) {
     P.sizes = c->d_sizes; P.row_off = c->d_row_off; P.g = c->d_g; P.prop = c->d_prop;
     P.gA = c->d_A; P.gx = c->d_x; P.gab = c->d_abeta; P.npairs = c->npairs; P.nab = nab;
     P.max_rounds = max_rounds;
-    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N;
-    P.test_gen = s->test_gen.p; P.win_lo = s->win_lo.p; P.win_hi = s->win_hi.p; P.zcut = c->zcut;
+    P.sites = site_view(s); P.win = window_view(c, s);
     P.M = s->M;
     P.list = nullptr; P.count = nullptr; P.lin = nullptr; P.clr = nullptr; P.pA = P.px = P.pab = nullptr;
     P.o_A = P.o_x = P.o_ab = nullptr; P.o_rounds = nullptr;
