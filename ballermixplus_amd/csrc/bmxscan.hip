@@ -1471,7 +1471,14 @@ __global__ __launch_bounds__(SCAN_THREADS_MAX) void clr_scan_grouped_kernel(Scan
 //
 //   blob(group)  = for iA in 0..nA-1: near(iA, right), near(iA, left), far(iA, right), far(iA, left);   16-byte units,
 //                  padded to a multiple of 4
-//   near(zone)   = header (3 units): {magic | rag, n_pair, n_quad, n_occ} {n_far, n_rag, end index | ZONE_DONE, n_ser | class counts << 8} {n_j bytes}
+//   near(zone)   = header (prep_hdr(J, first) units: 12 / 28 at J = 16):
+//                    {magic | rag, n_pair, n_quad, n_occ} {n_far, n_rag, end index | ZONE_DONE, n_ser | class counts << 8} {n_j bytes}
+//                    {span8 of the pair list | triangle flag << 16, 12 bytes: span8q / 8 of quad entries 0.., 64.., 128.., ...}
+//                    J / 2 units: F_j = exp_neg(A |t_near - t_j|), j = 0 .. J - 1
+//                    right zone only (the first of an A): J / 2 units G_k, J / 2 units H_k of the triangle (0 where the flag is 0)
+//                  -- everything the eight slice-waves of a group used to recompute per A although it is the same in all of
+//                  them; the consumer takes it with wave-uniform scalar loads straight from the blob, not through the ring.
+//                  (Quad entries from 64 * 12 on have no budget byte: the consumer works those out itself, as before.)
 //                  near list: n_pair entries with alpha > 1/2 (padded to whole blocks), then n_quad entries (multiple of 4),
 //                             each (E_i f64, row offset i32), in walk order; 8 neutral guard entries (what the block loops
 //                             request one block ahead)
@@ -1516,7 +1523,10 @@ __device__ constexpr double P_W[8] = {0.9999999999998467, 0.4999999999996164, 0.
 __device__ constexpr double P_D[6] = {7.94, 5.13, 3.462, 2.357, 1.571, 0.985};
 #endif
 constexpr double P_RAG_D = P_ORDER == 16 ? 6.74 : P_ORDER == 12 ? 6.23 : 5.13;     // log(P_EPS / 3e-4): the ragged end's third-order test
-constexpr int PREP_HDR = 3, PREP_GUARD = 8, PREP_MOM = 1 + P_ORDER / 2, PREP_RAG_GUARD = 1;     // a moment entry: (M_1, row) + M_2 .. M_K in pairs
+constexpr int PREP_GUARD = 8, PREP_MOM = 1 + P_ORDER / 2, PREP_RAG_GUARD = 1;     // a moment entry: (M_1, row) + M_2 .. M_K in pairs
+// header of a zone: 4 units of integers, F_j in pairs, and with the first (right) zone of an A G_k and H_k of the triangle
+constexpr int PREP_HDR_INT = 4, PREP_QB = 12;                     // PREP_QB: quad-list budgets in the header (one byte per started 64 entries)
+__host__ __device__ constexpr int prep_hdr(int J, bool first) { return PREP_HDR_INT + J / 2 + (first ? J : 0); }
 // Far sites of rows WITHOUT a moment slot (rare rows: fewer than ~1.3 sites per zone, so a slot's fold would cost more than it
 // saves): not multiplied either -- they go into the stream as "series entries" (E, row, order class) and the scan kernel adds
 // their (E R)^k to the same power sums p_k the moments feed, up to the order their alpha max|R| needs (2, 3, 5 or 8):
@@ -1541,6 +1551,7 @@ struct PrepParams {
     const int64_t *win_lo, *win_hi, *center, *center_hi;
     int64_t M;
     double zcut;
+    double rmax;                  // the consumer's P.rmax (list budgets)
     const double *rowthr;         // [rows]: A d from which a site of the row is far, the row's moment slot in the low byte
     int thr_in_lds;
     const uint8_t *kmom;
@@ -1612,6 +1623,16 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(PrepParams P) {
     }
     int L_int = min(c0, hi_min + 1), R_int = max(cU, lo_max);
     if (hi_min < lo_max) { L_int = c0; R_int = c0; hi_min = -1; lo_max = N; }   // no bulk zone
+    // the consumer's triangle form applies to the group (its `mid_tri`): the J sites between L_int and R_int ARE the test sites
+    bool mid_tri = false;
+    if (BMX_MIDTRI) {
+        const bool same = R_int - L_int <= MID_CAP && R_int - L_int == J && nvalid == J && lo_max <= L_int && hi_min >= R_int - 1;
+        if (same) {
+            const double gm = P.genpos[min(L_int + jl, N - 1)];
+            const double tprev = __shfl_up(tj, 1);
+            mid_tri = __ballot(!(gm == tj && (jl == 0 || tj > tprev))) == 0ull;
+        }
+    }
 
     int wpos = 0;                                   // units of the blob written (counted) so far
     ScratchEnt *out = nullptr;
@@ -1625,8 +1646,27 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(PrepParams P) {
         auto zone_near = [&](int base, int dir, double tnear, double tfar, double *mom, ScratchEnt *ser, int &zbase_o, int &npp_o, int &nqp_o,
                              int &nfar_o, int &base_o, double &m1p_o, double &m2p_o, int &nragv_o, int &nrmax_o, int &rag_o, double &zr_o,
                              int &rr_o, int &nser_o) {
-            const int zbase = wpos, nbase = zbase + PREP_HDR;
+            const bool first = dir > 0;
+            const int zbase = wpos, nbase = zbase + prep_hdr(J, first);
             int n_pair = 0, n_pair_pad = 0, n_quad = 0, nfar_tot = 0, pad_ro = 0, n_ser = 0;
+            // what the slice-waves no longer work out: F_j (lane j), with the first zone G_k / H_k of the triangle and its flag,
+            // the exponent budgets of the pair list (from its first, largest alpha) and of every 64 quad entries
+            const bool tri = first && mid_tri && A * (tL - t0) <= P.zcut;
+            double e0p = 0.0;
+            int qb0 = 0, qb1 = 0, qb2 = 0;
+            if (FILL) {
+                double *hd = reinterpret_cast<double *>(out + zbase + PREP_HDR_INT);
+                const double fv = exp_neg(A * fabs(tnear - tj));
+                if (lane < J) hd[lane] = fv;
+                if (first) {
+                    double Gk = 0.0, Hk = 0.0;
+                    if (tri) {
+                        const double xk = A * (tj - t0);
+                        exp_neg2(xk, -xk, Gk, Hk);
+                    }
+                    if (lane < J) { hd[J + lane] = Gk; hd[2 * J + lane] = Hk; }
+                }
+            }
             bool pair_open = true, seen = false;
             double m1p = 0.0, m2p = 0.0;
             auto close_pairs = [&]() {
@@ -1698,11 +1738,24 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(PrepParams P) {
                     }
                     if (pair_open) {
                         if (FILL && pairl) out[nbase + n_pair + rank(mp)] = ScratchEnt{Ev, rraw * P.rowmul, 0};
+                        if (FILL && n_pair == 0 && mp != 0ull) e0p = readlane_f64(Ev, __ffsll((long long)mp) - 1);      // entry 0 of the list
                         n_pair += __popcll(mp);
                         if (__ballot(bulk && !(zn < LN2)) != 0ull || cnt < WAVE) close_pairs();
                     }
                     if (!pair_open) {
                         if (FILL && nearl && !pairl) out[nbase + n_pair_pad + n_quad + rank(mq)] = ScratchEnt{Ev, rraw * P.rowmul, 0};
+                        if (FILL) {
+                            // quad entry 64 k (at most one per pass): every factor of the 64 entries from it lies in [1/2, 1 + E Rmax]
+                            const unsigned long long mz = __ballot(nearl && !pairl && ((n_quad + rank(mq)) & 63) == 0);
+                            if (mz != 0ull) {
+                                const int lz = __ffsll((long long)mz) - 1;
+                                const int k = (n_quad + __popcll(mq & ((1ull << lz) - 1ull))) >> 6;
+                                const double op = fma(readlane_f64(Ev, lz), P.rmax, 1.0);
+                                const int hi = ((__builtin_amdgcn_readfirstlane(__double2hiint(op)) >> 20) & 0x7ff) - 1022;
+                                const int qb = min(max(hi, 2), 125) << (8 * (k & 3));
+                                if (k < 4) qb0 |= qb; else if (k < 8) qb1 |= qb; else if (k < PREP_QB) qb2 |= qb;
+                            }
+                        }
                         n_quad += __popcll(mq);
                     }
                 }
@@ -1715,6 +1768,14 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(PrepParams P) {
             if (FILL) {
                 if (lane < n_quad_pad - n_quad) out[nbase + n_pair_pad + n_quad + lane] = ScratchEnt{0.0, pad_ro, 0};
                 if (lane < PREP_GUARD) out[nbase + n_pair_pad + n_quad_pad + lane] = ScratchEnt{0.0, pad_ro, 0};
+                int span8 = 0;
+                if (n_pair > 0) {
+                    const double om = 1.0 - e0p, op = fma(e0p, P.rmax, 1.0);
+                    const int pend_lo = 1024 - ((__builtin_amdgcn_readfirstlane(__double2hiint(om)) >> 20) & 0x7ff);
+                    const int pend_hi = ((__builtin_amdgcn_readfirstlane(__double2hiint(op)) >> 20) & 0x7ff) - 1022;
+                    span8 = 8 * min(max(pend_hi, pend_lo), 125);
+                }
+                if (lane == 0) reinterpret_cast<int4 *>(out + zbase)[3] = int4{span8 | (tri ? 1 << 16 : 0), qb0, qb1, qb2};
             }
             wpos = nbase + n_pair_pad + n_quad_pad + PREP_GUARD;
 
@@ -2165,7 +2226,6 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
         int lo_j = (int)max(P.win_lo[tb + jj], (int64_t)0);
         int hi_j = (int)min(P.win_hi[tb + jj], (int64_t)N - 1);
         if (jl >= nvalid) { lo_j = 1; hi_j = 0; }
-        const double t0 = readlane_f64(tj, 0), tL = readlane_f64(tj, J - 1);
         const int c0 = (int)P.center[tb], cU = (int)P.center_hi[tb + nvalid - 1];
         int lo_max = 0, hi_min = N - 1;
 #pragma unroll
@@ -2181,20 +2241,35 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
             mid_ro[lane_g] = (int)P.row[L_int + lane_g] * rowmul;
         }
         __builtin_amdgcn_wave_barrier();
-        bool mid_tri = false;
-        if (BMX_MIDTRI) {
-            const bool same = staged && (R_int - L_int == J) && nvalid == J && lo_max <= L_int && hi_min >= R_int - 1;
-            if (same) {
-                const double gm = mid_g[jl_g];
-                const double tprev = __shfl_up(tj, 1);
-                mid_tri = __ballot(!(gm == tj && (jl_g == 0 || tj > tprev))) == 0ull;
-            }
-        }
+        // (whether the triangle form applies -- the J staged sites ARE the test sites, and A (t_L - t_0) <= zcut -- is the producer's
+        // word in the first header of every A; here only what keeps a corrupt word from reading unstaged sites)
+        const bool tri_staged = staged && R_int - L_int == J;
 
         // the group's blob, streamed through the ring: `pos` units consumed, [.., staged_u) in the ring, the next 64 in flight
         // (the unit in flight is held as two doubles -- bit patterns, never arithmetic -- so that it stays in registers)
         const double2 *src = reinterpret_cast<const double2 *>(V.arena + (V.blob_prefix[V.grp_base + grp] - V.prefix_base));
         double2 *ring2 = reinterpret_cast<double2 *>(ring);
+        // the zone headers' scalars (integers, F_j, G_k / H_k) do not go through the ring: they are the same for the whole wave, so
+        // they come by scalar loads straight from the blob -- constant address space: the arena is written by the preceding kernel only
+        typedef const __attribute__((address_space(4))) int *HdrPtr;
+        typedef const __attribute__((address_space(4))) double *HdrPtr2;
+        const HdrPtr ksrc = (HdrPtr)src;
+        auto load_hdr = [&](int at, int4 &h0, int4 &h1, int4 &h3) {
+            const HdrPtr hp = ksrc + 4 * at;
+            h0 = int4{hp[0], hp[1], hp[2], hp[3]}; h1 = int4{hp[4], hp[5], hp[6], hp[7]}; h3 = int4{hp[12], hp[13], hp[14], hp[15]};
+        };
+        auto hdr_ok = [&](const int4 h0, const int4 h1, const int4 h3) -> bool {
+            const int magic = h0.x, n_pair = h0.y, n_quad = h0.z, n_occ = h0.w, nrmax = h1.y, ser_w = h1.w;
+            const int n_ser = ser_w & 0xff, c8 = (ser_w >> 8) & 0xff, c5 = (ser_w >> 16) & 0xff, c3 = (ser_w >> 24) & 0xff;
+            return !((magic & ~3) != PREP_MAGIC || (magic & 3) == 2 || n_pair < 0 || n_quad < 0 || n_pair > N + 8 || n_quad > N + 8 || n_occ < 0 ||
+                     n_occ > MOM_SLOTS || nrmax < 0 || nrmax >= WAVE || n_ser > SER_CAP || (n_ser & 3) || c8 > c5 || c5 > c3 || c3 > n_ser ||
+                     (h3.x & 0xffff) > 1000 || (h3.x >> 17) != 0);
+        };
+        auto load_f = [&](int at, double (&F)[J]) {       // J doubles from unit `at` on
+            const HdrPtr2 fp = (HdrPtr2)(ksrc + 4 * at);
+#pragma unroll
+            for (int j = 0; j < J; ++j) F[j] = fp[j];
+        };
         int pos = 0, staged_u = 0;
         double nx_a, nx_b;
         {
@@ -2298,48 +2373,35 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
 
             // One zone of the blob, first half: header and near-list products; returns where the generic walk goes on.  What
             // the far half needs later (after BOTH near lists) comes back through the references; fv: lane j holds F_j.
-            auto zone_near = [&](auto dirk, double tnear, double &fv_o, int &nocc_o, int &nfar_o, int &nrmax_o, int &rag_o, int &nser_o,
-                                 FargVec &farg) -> int {
+            // The header's integers (h0, h1, h3: units 0, 1 and 3) come from the caller, in scalar registers; F_j comes from the
+            // units behind them -- computed once per group by prep_kernel, not once per slice here.
+            auto zone_near = [&](auto dirk, const int4 h0, const int4 h1, const int4 h3, int &zpos_o, int &nocc_o, int &nfar_o, int &nrmax_o,
+                                 int &rag_o, int &nser_o, FargVec &farg) -> int {
                 constexpr int dirc = decltype(dirk)::value;       // compile-time: farg[j] and F[j] of the ragged-end walk are registers
                 int nragv_o = 0;
                 nocc_o = 0; nfar_o = 0; nrmax_o = 0; rag_o = 0; nser_o = 0;
-                fv_o = 0.0;
+                zpos_o = pos;
                 if (bad) return PREP_ZONE_DONE;
                 double F[J];
-                {
-                    const double fv = exp_neg(A * fabs(tnear - tj));
-                    fv_o = fv;
-#pragma unroll
-                    for (int j = 0; j < J; ++j) F[j] = readlane_f64(fv, j);
-                }
+                load_f(pos + PREP_HDR_INT, F);
                 need();
-                const int4 *hp = reinterpret_cast<const int4 *>(ring + (pos & (RING_UNITS - 1)));
-                const int4 h0 = hp[0], h1 = hp[1];
-                const int magic = __builtin_amdgcn_readfirstlane(h0.x);
-                const int n_pair = __builtin_amdgcn_readfirstlane(h0.y), n_quad = __builtin_amdgcn_readfirstlane(h0.z);
-                const int n_occ = __builtin_amdgcn_readfirstlane(h0.w);
-                const int nfar_tot = __builtin_amdgcn_readfirstlane(h1.x), nrmax = __builtin_amdgcn_readfirstlane(h1.y);
-                const int base_end = __builtin_amdgcn_readfirstlane(h1.z), ser_w = __builtin_amdgcn_readfirstlane(h1.w);
-                const int n_ser = ser_w & 0xff, c8 = (ser_w >> 8) & 0xff, c5 = (ser_w >> 16) & 0xff, c3 = (ser_w >> 24) & 0xff;
+                const int magic = h0.x;
+                const int n_pair = h0.y, n_quad = h0.z, n_occ = h0.w;
+                const int nfar_tot = h1.x, nrmax = h1.y, base_end = h1.z, ser_w = h1.w;
                 const int rag = magic & 3;
-                if ((magic & ~3) != PREP_MAGIC || rag == 2 || n_pair < 0 || n_quad < 0 || n_pair > N + 8 || n_quad > N + 8 || n_occ < 0 || n_occ > MOM_SLOTS ||
-                    nrmax < 0 || nrmax >= WAVE || n_ser > SER_CAP || (n_ser & 3) || c8 > c5 || c5 > c3 || c3 > n_ser) {
+                const int span8 = h3.x & 0xffff;                  // exponent budget of a pair entry, from the list's largest alpha
+                if (!hdr_ok(h0, h1, h3)) {
                     bad = true;
                     return PREP_ZONE_DONE;
                 }
                 // n_j of this lane's test site (ragged end)
-                nragv_o = (int)reinterpret_cast<const unsigned char *>(hp + 2)[jl];
+                nragv_o = (int)reinterpret_cast<const unsigned char *>(ring + ((pos + 2) & (RING_UNITS - 1)))[jl];
                 nocc_o = n_occ; nfar_o = nfar_tot; nrmax_o = nrmax; rag_o = rag; nser_o = ser_w;
-                pos += PREP_HDR;
+                pos += prep_hdr(J, dirc > 0);
                 PROF_MARK(1);
 
                 if (n_pair > 0) {
                     need();
-                    const double e0 = ring[pos & (RING_UNITS - 1)].e;       // the nearest site: the largest alpha of the list
-                    const double om = 1.0 - e0, op = fma(e0, P.rmax, 1.0);
-                    const int pend_lo = 1024 - ((__builtin_amdgcn_readfirstlane(__double2hiint(om)) >> 20) & 0x7ff);
-                    const int pend_hi = ((__builtin_amdgcn_readfirstlane(__double2hiint(op)) >> 20) & 0x7ff) - 1022;
-                    const int span8 = 8 * min(max(pend_hi, pend_lo), 125);
                     double Rp[BS], ep[BS];
                     if (BMX_PPAIR_PREFETCH) {
                         const ScratchEnt *rp = ring + (pos & (RING_UNITS - 1));
@@ -2398,10 +2460,17 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                         need();
                         const ScratchEnt *rp = ring + (pos & (RING_UNITS - 1));
                         if ((l0 & 63) == 0) {
-                            // every factor of the next 64 entries lies in [1/2, 1 + e0 Rmax], e0 the first (largest) alpha among them
-                            const double op = fma(rp[0].e, P.rmax, 1.0);
-                            const int hi = ((__builtin_amdgcn_readfirstlane(__double2hiint(op)) >> 20) & 0x7ff) - 1022;
-                            span8q = 8 * min(max(hi, 2), 125);
+                            // every factor of the next 64 entries lies in [1/2, 1 + e0 Rmax], e0 the first (largest) alpha among them:
+                            // the producer's byte for the first PREP_QB * 64 entries; a longer list (unbounded: no room in a
+                            // header of fixed size) goes on with the computation itself
+                            const int k = l0 >> 6;
+                            if (k < PREP_QB) {
+                                span8q = 8 * (((k < 4 ? h3.y : k < 8 ? h3.z : h3.w) >> (8 * (k & 3))) & 0xff);
+                            } else {
+                                const double op = fma(rp[0].e, P.rmax, 1.0);
+                                const int hi = ((__builtin_amdgcn_readfirstlane(__double2hiint(op)) >> 20) & 0x7ff) - 1022;
+                                span8q = 8 * min(max(hi, 2), 125);
+                            }
                         }
                         spend(span8q / 2);
                         double v[4];
@@ -2495,12 +2564,13 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
 
             // ... second half, after both zones' near lists: fold the zone's moments, walk its ragged end, and ADD the log of
             // the factor each test site's product has to pick up to farg (the exp is taken once for both zones)
-            auto zone_far = [&](double fv, int n_occ, int ser_w, int nfar_tot, FargVec &farg) {
+            auto zone_far = [&](int zpos, int n_occ, int ser_w, int nfar_tot, FargVec &farg) {
                 const int n_ser = ser_w & 0xff, ser_cls = ser_w >> 8;        // entries; cumulative class counts (8, 5, 3), 8 bits each
                 if (bad || !nfar_tot) return;
+                // F_j again, by a second scalar load from the zone's header (requested here, used by the Horner chains below:
+                // the folds in between hide it) -- not 32 scalar registers kept across both near lists
                 double F[J];
-#pragma unroll
-                for (int j = 0; j < J; ++j) F[j] = readlane_f64(fv, j);
+                load_f(zpos + PREP_HDR_INT, F);
                 double pk[P_ORDER];
 #pragma unroll
                 for (int k = 0; k < P_ORDER; ++k) pk[k] = 0.0;
@@ -2620,15 +2690,20 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
 
             // sites between / at the test sites (and any part of the windows not covered by bulk)
             PROF_MARK(9);
-            if (BMX_MIDTRI && mid_tri && A * (tL - t0) <= P.zcut) {
-                const double xk = A * (tj - t0);
-                double Gk, Hk;
-                exp_neg2(xk, -xk, Gk, Hk);
+            // the right zone's header (the left zone's is read where that zone starts: requesting either one earlier, across the
+            // best-tracking or the right zone's near list, cost more scalar registers spilled than the wait it saved)
+            int4 hR0, hR1, hR3, hL0, hL1, hL3;
+            load_hdr(pos, hR0, hR1, hR3);
+            const int posR = pos;
+            const bool okR = !bad && hdr_ok(hR0, hR1, hR3);      // (zone_near sets `bad` from the same test; nothing of a bad header is used)
+            // triangle: the producer's word says whether the form applies at this A, and brings G_k, H_k
+            if (BMX_MIDTRI && tri_staged && okR && (hR3.x >> 16) == 1) {
+                const double *gh = reinterpret_cast<const double *>(src + posR + PREP_HDR_INT + J / 2);
+                const double Gk = gh[jl], Hk = gh[J + jl];
                 const int ro_k = mid_ro[jl];
                 spend((J - 1) * span_generic);
                 double Fs[J];
-#pragma unroll
-                for (int j = 0; j < J; ++j) Fs[j] = readlane_f64(Hk, j);
+                load_f(posR + PREP_HDR_INT + J, Fs);              // H_k
                 if (lane < J) scr[lane] = ScratchEnt{Gk, ro_k, 0};
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -2644,8 +2719,7 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                     acc[i] *= fma(Fs[i], v1, 1.0);
                 }
                 __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int j = 0; j < J; ++j) Fs[j] = readlane_f64(Gk, j);
+                load_f(posR + PREP_HDR_INT + J / 2, Fs);          // G_k
                 if (lane < J) scr[lane] = ScratchEnt{Hk, ro_k, 0};
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -2666,16 +2740,17 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
             }
             PROF_MARK(0);
             // right side, left side: near lists and whatever the zones do not cover
-            double fvR, fvL;
+            int zposR, zposL;
             int noccR, nfarR, nrmR, nserR, noccL, nfarL, nrmL, nserL;
             int ragR, ragL;
             FargVec farg;               // per test site: minus the log of the factor its product picks up from the far fields (exp_neg's argument)
 #pragma unroll
             for (int j = 0; j < J; ++j) farg[j] = 0.0;
-            int b = zone_near(std::integral_constant<int, +1>{}, tL, fvR, noccR, nfarR, nrmR, ragR, nserR, farg);
+            int b = zone_near(std::integral_constant<int, +1>{}, hR0, hR1, hR3, zposR, noccR, nfarR, nrmR, ragR, nserR, farg);
             if (b != PREP_ZONE_DONE) { while (!generic_pass(b, +1, N, false)) b += SP; }
             PROF_MARK(4);
-            b = zone_near(std::integral_constant<int, -1>{}, t0, fvL, noccL, nfarL, nrmL, ragL, nserL, farg);
+            load_hdr(pos, hL0, hL1, hL3);
+            b = zone_near(std::integral_constant<int, -1>{}, hL0, hL1, hL3, zposL, noccL, nfarL, nrmL, ragL, nserL, farg);
             if (b != PREP_ZONE_DONE) { while (!generic_pass(b, -1, -1, false)) b -= SP; }
             PROF_MARK(4);
             // the far fields of both zones: ONE exp per test site -- test sites in pairs, two interleaved exp chains, each pair
@@ -2699,16 +2774,15 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                 const int bitsR = 2 + (int)((float)(nfarR + nrmR) * P.far_bits), bitsL = 2 + (int)((float)(nfarL + nrmL) * P.far_bits);
                 // (one copy of each zone's code: this kernel's per-A path is about as large as the instruction cache)
                 const bool split = bitsR + bitsL > 900;
-                zone_far(fvR, noccR, nserR, nfarR, farg);
+                zone_far(zposR, noccR, nserR, nfarR, farg);
                 if (split) {
                     spend(bitsR);
                     apply_far();
                 }
-                zone_far(fvL, noccL, nserL, nfarL, farg);
+                zone_far(zposL, noccL, nserL, nfarL, farg);
                 spend(split ? bitsL : bitsR + bitsL);
                 apply_far();
             }
-
             renorm_all();
 #pragma unroll
             for (int j = 0; j < J; ++j) {
@@ -6108,7 +6182,7 @@ PrepParams prep_params(bmx_ctx *c, ChromSlot *s, const ScanPlan &pl) {
     Q.rows = c->rows; Q.rowmul = pl.use_lds ? WAVE : c->NP;
     Q.A = c->d_A; Q.nA = c->nA;
     Q.test_gen = s->test_gen.p; Q.win_lo = s->win_lo.p; Q.win_hi = s->win_hi.p; Q.center = s->center.p; Q.center_hi = s->center_hi.p;
-    Q.M = s->M; Q.zcut = c->zcut;
+    Q.M = s->M; Q.zcut = c->zcut; Q.rmax = pl.P.rmax;
     Q.rowthr = s->rowthr.p; Q.thr_in_lds = pl.thr_in_lds;
     // series entries only where they are cheaper than the product: groups of 16 (a product entry costs 1.5 instructions per test site)
     const bool series = pl.mode == 4 && pl.J == 16;
