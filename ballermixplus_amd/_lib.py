@@ -84,6 +84,8 @@ PROTOTYPES = {
     'bmx_ctx_influence_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_fit': (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, _ip, C.c_int32, _dp, C.c_int32, _ip, _dp, _dp, _ip]),
     'bmx_ctx_fit_ms': (C.c_int, [_vp, _dp]),
+    'bmx_ctx_cond_surfaces': (C.c_int, [_vp, C.c_int64, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _ip]),
+    'bmx_ctx_cond_surfaces_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_permute_rows': (C.c_int, [_vp, C.c_uint64, C.c_int64]),
     'bmx_ctx_restore_rows': (C.c_int, [_vp]),
     'bmx_ctx_null_begin': (C.c_int, [_vp]),

@@ -52,6 +52,15 @@ Additions (do not change any reference command line):
                     window: the two chi-square sums over the cells with an expected count >= E, default 5, their degrees of
                     freedom and the worst cell) and with --fitDetail <out>.fit.cells.txt (every cell) next to each output file.
                     Sites are linked: the sums describe, they are no calibrated test.
+  --conditional [--condSpan H] [--condMin C] [--condSurfaces]     with --peaks: are two nearby apexes two loci, or one locus and
+                    its shoulder (ballermixplus_amd/conditional.py)?  Every apex gets as parent the highest apex above it within H
+                    (default: the sum of the two fitted reaches, alpha_cut / A_hat each); the apex's surface is then computed
+                    again with the parent's fitted model, held at its grid argmax, in place of neutrality at the sites the two
+                    share, and the parent's given the apex.  Writes <out>.conditional.txt next to each output file: per apex with
+                    CLR >= C (default: all) the parent, the shared sites, the conditional maximum and where it sits, the share
+                    of the unconditional maximum it retains, and the same for the parent given the apex; with --condSurfaces
+                    <out>.conditional.surfaces.txt (the conditional surfaces, in --surfaces' format).  One locus, not refitted;
+                    sites are linked: `retained` describes, it is no test.
   --locate R [--locateSeed S] [--locateBlock B] [--locateSpan H] [--locateLevel L] [--locateMin C] [--locateReps]     with
                     --peaks: a block-bootstrap interval for the POSITION of every apex (ballermixplus_amd/locate.py): R replicates
                     resample the sites in blocks of B consecutive sites on the device, repeat the grid scan at the test positions
@@ -246,6 +255,23 @@ def build_parser():
                              '(default 5)')
     parser.add_argument('--fitDetail', dest='fitDetail', action='store_true', default=False,
                         help='MI355X build only, with --fit: also write every cell of every selected window to <out>.fit.cells.txt')
+    parser.add_argument('--conditional', dest='conditional', action='store_true', default=False,
+                        help='MI355X build only, with --peaks: conditional CLRs of neighbouring apexes of the observed scan.  Every '
+                             'apex gets as parent the highest apex above it within --condSpan; its surface is computed again with '
+                             'the parent\'s fitted model, held at its grid argmax and not refitted, in place of neutrality at the '
+                             'sites both reach, and the parent\'s given the apex.  <out>.conditional.txt next to each output file '
+                             'gives per apex the parent, the shared sites, the conditional maximum and the share of the '
+                             'unconditional maximum it retains.  Sites are linked: the share describes, it is no test')
+    parser.add_argument('--condSpan', dest='condSpan', type=float, default=None,
+                        help='MI355X build only, with --conditional: a parent lies within this distance, in the units of the test '
+                             'positions (default: the sum of the two fitted reaches alpha_cut / A_hat, so the footprints can share '
+                             'a site)')
+    parser.add_argument('--condMin', dest='condMin', type=float, default=None,
+                        help='MI355X build only, with --conditional: only apexes with CLR >= this value get a row (parents are '
+                             'still chosen among all apexes)')
+    parser.add_argument('--condSurfaces', dest='condSurfaces', action='store_true', default=False,
+                        help='MI355X build only, with --conditional: also write the conditional surface of every apex that has a '
+                             'parent to <out>.conditional.surfaces.txt, in the format of --surfaces')
     parser.add_argument('--locate', dest='locate', type=int, default=0,
                         help='MI355X build only, with --peaks: R >= 2 bootstrap replicates of the grid scan around every apex.  Each '
                              'replicate gives every block of --locateBlock consecutive sites a Poisson(1) weight, scans the '
@@ -504,6 +530,26 @@ def write_fit(opt, ctx, sel, outfile, ts, called, say):
         say(f'--fitMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
 
 
+def conditional_refusal(opt):
+    """--conditional / --condSpan / --condMin / --condSurfaces."""
+    if not opt.conditional:
+        return orphan(opt, '--conditional', ('condSpan', 'condMin', 'condSurfaces'))
+    from . import conditional
+    return (conditional.value_refusal(opt.condSpan, opt.condMin)
+            or when(opt.peaks is None, '--conditional needs --peaks G: it conditions every apex of the peak call on its neighbour.')
+            or helper_mode(opt, '--conditional')
+            or no_output(opt, '--conditional', 'conditional file is')
+            or multi_rank('--conditional'))
+
+
+def write_conditional(opt, ctx, sel, outfile, ts, called, say):
+    """<outfile>.conditional.txt (with --condSurfaces <outfile>.conditional.surfaces.txt) of one file whose observed scan and
+    peak call (`called`) have just run on ctx's selected slot."""
+    from . import conditional
+    n, with_parent = conditional.conditional_and_write(ctx, outfile, ts, sel, called[0]['row'], opt.condSpan, opt.condMin, opt.condSurfaces)
+    say(f'\n{datetime.now()}. Conditional: {n} apex/es, {with_parent} with a parent -> {conditional.output_name(outfile)}')
+
+
 def peaks_refusal(opt):
     """--peaks / --peakMin / --peakExtent / --atPeaks.  Asked before the refusals of the features that do not need the peaks,
     so that a command line with --peaks is refused in this feature's name."""
@@ -662,6 +708,9 @@ def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
     if opt.fit:
         write_fit(opt, ctx, sel, outfile, ts, called, say)
         stamp('file %d: fit' % (f + 1))
+    if opt.conditional:
+        write_conditional(opt, ctx, sel, outfile, ts, called, say)
+        stamp('file %d: conditional' % (f + 1))
     if opt.refine:
         write_refined(opt, ctx, outfile, ts, f)
         stamp('file %d: refine' % (f + 1))
@@ -734,7 +783,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = power_refusal(opt) or locate_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt)
+    refused = power_refusal(opt) or locate_refusal(opt) or conditional_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)

@@ -13,6 +13,8 @@
 //       influence_kernel           <- every leave-one-block-out maximum of those surfaces (bmx_ctx_influence), with
 //                                     influence_range_kernel and influence_argmax_kernel
 //       fit_kernel                 <- observed against expected spectrum by distance of listed windows (bmx_ctx_fit)
+//       cond_surfaces_kernel       <- the surfaces of listed windows given one fitted neighbouring locus each
+//                                     (bmx_ctx_cond_surfaces), with influence_argmax_kernel for their maxima
 //
 // The shipped library reads ONE environment variable, BMX_TRACE (stage messages on stderr, no effect on results).
 // Tuning knobs for A/B runs (BMX_LDS_PAD, BMX_DENSE_GAP, BMX_SOLO_GAP, BMX_FORCE_J, BMX_FAR_EPS, BMX_MOM_SLOTS, BMX_SPB,
@@ -4743,6 +4745,84 @@ __global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) 
     if (slice == 0 && tid == 0) S.ns[(size_t)q * S.nA + iA] = ns;
 }
 
+// ------------------------------------------------------ surfaces of listed test sites given one fitted neighbouring locus
+// bmx_ctx_cond_surfaces (the definition is ballermixplus_amd/conditional.py).  Pair q is the window of test site tests[q] and a
+// conditioning locus: test site ctest[q] held at the grid point clin[q] = iA_c * npairs + p_c (either < 0: none).
+// surfaces_kernel's decomposition, range and tiles; the thread that stages site base + tid also decides whether the site is
+// SHARED -- inside the conditioning site's clipped window, A_c |g_i - tc| <= zcut, g_i != tc -- and then gathers the one entry
+// of the conditioning column: d = exp(-zc) R[row_i][p_c], else d = 0.0 exactly.  It stores u = alpha / (1.0 + d) and d beside
+// the row, so the conditioning side costs one exp, one gather and one division per site per tile, and a pair adds
+// log1p(u (R - d)) per site: a subtract more than tile_term.  With d = 0.0, u is alpha and R - 0.0 is R: a pair without a
+// conditioning locus, or with one out of reach of every site, is bitwise surfaces_kernel's window.  No atomics: a pair's
+// numbers depend on that pair alone.
+struct CondParams {
+    SiteView sites; WindowView win;
+    const double *Rt; int NP, npairs, nslices;      // nslices: slices of SURFS_THREADS pairs
+    const double *A; int nA;
+    const int32_t *tests, *ctest, *clin;             // the listed pairs of this launch
+    double *T;        // [n][nA][npairs]
+    int32_t *ns;      // [n][nA]
+    int32_t *nsh;     // [n][nA]: the shared sites among ns
+};
+
+__global__ __launch_bounds__(SURFS_THREADS) void cond_surfaces_kernel(CondParams S) {
+    __shared__ double s_u[SURFS_THREADS];
+    __shared__ double s_d[SURFS_THREADS];
+    __shared__ int s_row[SURFS_THREADS];
+    __shared__ int64_t s_range[2];
+    const int tid = threadIdx.x;
+    const int slice = blockIdx.x % S.nslices;
+    const int iA = (blockIdx.x / S.nslices) % S.nA;
+    const int64_t q = blockIdx.x / S.nslices / S.nA;
+    const int p = slice * SURFS_THREADS + tid;
+    const bool live = p < S.npairs;
+    const int64_t t = S.tests[q];
+    const double A = S.A[iA], tg = S.win.test_gen[t];
+    const int32_t ct = S.ctest[q], cl = S.clin[q];
+    const bool cond = ct >= 0 && cl >= 0;
+    double tc = 0.0, Ac = 0.0;
+    int pc = 0;
+    int64_t clo = 0, chi = -1;                       // (no conditioning locus: no site is inside this window)
+    if (cond) {
+        tc = S.win.test_gen[ct]; Ac = S.A[cl / S.npairs]; pc = cl % S.npairs;
+        clo = max(S.win.win_lo[ct], (int64_t)0); chi = min(S.win.win_hi[ct], S.sites.N - 1);
+    }
+    if (tid < WAVE) {
+        const SiteRange R = window_range(S.sites, S.win, t, tg, A);
+        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
+    }
+    __syncthreads();
+    const int64_t rlo = s_range[0], rhi = s_range[1];
+    double sum = 0.0, z;
+    int ns = 0, nsh = 0;
+    for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
+        const int64_t i = base + tid;
+        const bool in = tile_site(S.sites.genpos, i, rhi, tg, A, S.win.zcut, z);
+        tile_store(S.sites.row, i, in, z, s_u, s_row);               // alpha for now
+        bool shared = false;
+        double d = 0.0;
+        if (in && i >= clo && i <= chi) {
+            const double g = S.sites.genpos[i], zc = Ac * fabs(g - tc);
+            shared = zc <= S.win.zcut && g != tc;
+            if (shared) d = exp(-zc) * S.Rt[(size_t)s_row[tid] * S.NP + pc];
+        }
+        s_d[tid] = d;
+        s_u[tid] = s_u[tid] / (1.0 + d);
+        ns += __syncthreads_count(in);
+        nsh += __syncthreads_count(shared);
+        if (live) {
+            const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
+            for (int s = 0; s < cnt; ++s) {
+                const int r_s = s_row[s];
+                if (r_s >= 0) sum += log1p(s_u[s] * (S.Rt[(size_t)r_s * S.NP + p] - s_d[s]));
+            }
+        }
+        __syncthreads();
+    }
+    if (live) S.T[((size_t)q * S.nA + iA) * S.npairs + p] = ns ? 2.0 * sum : NAN;
+    if (slice == 0 && tid == 0) { S.ns[(size_t)q * S.nA + iA] = ns; S.nsh[(size_t)q * S.nA + iA] = nsh; }
+}
+
 // ----------------------------------------------------------- delete-block jackknife of a list of test sites' grid maxima
 // bmx_ctx_influence (the definition is ballermixplus_amd/influence.py).  Per chunk of listed windows four launches on the
 // context's stream: surfaces_kernel gives T and ns, influence_range_kernel every (window, A)'s site range,
@@ -5375,6 +5455,11 @@ struct bmx_ctx {
     DevBuf<double> ft_gw, ft_edges, ft_ws, ft_Es, ft_En;
     DevBuf<int32_t> ft_lin, ft_cls, ft_O, ft_skip;
     DevTimer ft;
+    // conditional surfaces (bmx_ctx_cond_surfaces): the pairs' conditioning sites and grid points, one chunk's shared counts,
+    // maxima and argmaxes (T and nsites in the surfaces' buffers), the events around a chunk's kernels
+    DevBuf<int32_t> cs_ctest, cs_clin, cs_nsh, cs_lin;
+    DevBuf<double> cs_tmax;
+    DevTimer cs;
     DevBuf<int64_t> gap_sample;
     // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
     int pl_which = 0;
@@ -5723,6 +5808,8 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->ft_gw.release(); c->ft_edges.release(); c->ft_ws.release(); c->ft_Es.release(); c->ft_En.release();
     c->ft_lin.release(); c->ft_cls.release(); c->ft_O.release(); c->ft_skip.release();
     c->ft.release();
+    c->cs_ctest.release(); c->cs_clin.release(); c->cs_nsh.release(); c->cs_lin.release(); c->cs_tmax.release();
+    c->cs.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
@@ -6983,6 +7070,67 @@ int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin,
 int bmx_ctx_fit_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
     return c->ft.get(ms, "no fit call yet");
+}
+
+int bmx_ctx_cond_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *cond_test, const int32_t *cond_lin, double *T_out,
+                          int32_t *nsites_out, int32_t *nshared_out, double *tmax_out, int32_t *lin_out) {
+    int rc;
+    if ((rc = list_ready(c, "cond_surfaces", n, nullptr, !tests || !cond_test || !cond_lin))) return rc;
+    if (n == 0) { c->cs.ms = 0.0; return BMX_OK; }
+    ChromSlot *s = c->cur;
+    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one pair's surface
+    for (int64_t q = 0; q < n; q++) {
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "cond_surfaces: test site index out of range at entry " + std::to_string(q));
+        if (cond_test[q] < -1 || cond_test[q] >= s->M)
+            return fail(BMX_E_INVALID, "cond_surfaces: conditioning test site index out of range at entry " + std::to_string(q));
+        if (cond_lin[q] >= 0 && (size_t)cond_lin[q] >= per)
+            return fail(BMX_E_INVALID, "cond_surfaces: conditioning grid index out of range at entry " + std::to_string(q));
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
+    const int64_t step = surfaces_step(c, nsl);
+    const size_t first = (size_t)std::min<int64_t>(step, n);
+    HIP_TRY(c->sfs_T.ensure(first * per));
+    HIP_TRY(c->sfs_ns.ensure(first * c->nA));
+    HIP_TRY(c->cs_nsh.ensure(first * c->nA));
+    HIP_TRY(c->cs_tmax.ensure(first));
+    HIP_TRY(c->cs_lin.ensure(first));
+    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
+    if ((rc = upload(c->cs_ctest, cond_test, (size_t)n, c->stream))) return rc;
+    if ((rc = upload(c->cs_clin, cond_lin, (size_t)n, c->stream))) return rc;
+    CondParams S;
+    S.sites = site_view(s); S.win = window_view(c, s);
+    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p; S.nsh = c->cs_nsh.p;
+    double total = 0.0;
+    for (int64_t q0 = 0; q0 < n; q0 += step) {
+        const int64_t m = std::min(step, n - q0);
+        S.tests = c->sfs_list.p + q0; S.ctest = c->cs_ctest.p + q0; S.clin = c->cs_clin.p + q0;
+        HIP_TRY(c->cs.begin(c->stream));
+        hipLaunchKernelGGL(cond_surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
+        if (tmax_out || lin_out)
+            hipLaunchKernelGGL(influence_argmax_kernel, dim3((unsigned)m), dim3(INFL_THREADS), 0, c->stream, (const double *)c->sfs_T.p,
+                               (int64_t)per, c->cs_tmax.p, c->cs_lin.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(c->cs.end(c->stream));
+        // each chunk goes back before the next is launched, as in bmx_ctx_surfaces; without T_out the surfaces stay on the device
+        const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+        if (T_out) HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), D2H, c->stream));
+        if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
+        if (nshared_out) HIP_TRY(hipMemcpyAsync(nshared_out + (size_t)q0 * c->nA, c->cs_nsh.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
+        if (tmax_out) HIP_TRY(hipMemcpyAsync(tmax_out + q0, c->cs_tmax.p, (size_t)m * sizeof(double), D2H, c->stream));
+        if (lin_out) HIP_TRY(hipMemcpyAsync(lin_out + q0, c->cs_lin.p, (size_t)m * sizeof(int32_t), D2H, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->cs.read());
+        total += c->cs.ms;
+    }
+    c->cs.ms = total;        // the call's figure: its chunks' kernels
+    return BMX_OK;
+}
+
+int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    return c->cs.get(ms, "no cond_surfaces call yet");
 }
 
 }  // extern "C"

@@ -537,6 +537,29 @@ class Context:
         """Device milliseconds of the kernel of the context's last fit() call."""
         return self._ms(self._L.bmx_ctx_fit_ms)
 
+    def cond_surfaces(self, tests, cond_test, cond_lin, want_T=True):
+        """Conditional surfaces (ballermixplus_amd/conditional.py) of the listed pairs on the selected slot: pair q is the window
+        of test site tests[q] given the conditioning locus cond_test[q] (a test site, -1: none) held at the grid point
+        cond_lin[q] = (iA * nx + ix) * nab + ia (< 0: none).  Returns a dict: T f64[n, nA, nx, nab] (None without want_T: the
+        surfaces are then not copied back), nsites i32[n, nA], nshared i32[n, nA], tmax f64[n] and lin i32[n] (the scan's rule on
+        each pair's T; 0 and -1 when nothing is > 0)."""
+        m = self.model
+        t, ct, cl = _lib.i32(tests), _lib.i32(cond_test), _lib.i32(cond_lin)
+        if t.ndim != 1 or ct.shape != t.shape or cl.shape != t.shape:
+            raise ValueError('a flat list of test site indices and one conditioning site and grid point per entry are needed')
+        n = len(t)
+        out = {'T': np.empty((n, self.nA, len(m.x), len(m.abeta)), dtype=np.float64) if want_T else None,
+               'nsites': np.empty((n, self.nA), dtype=np.int32), 'nshared': np.empty((n, self.nA), dtype=np.int32),
+               'tmax': np.empty(n, dtype=np.float64), 'lin': np.empty(n, dtype=np.int32)}
+        _lib.check(self._L.bmx_ctx_cond_surfaces(self._h, n, _lib.as_ip(t), _lib.as_ip(ct), _lib.as_ip(cl),
+                                                 _lib.as_dp(out['T']) if want_T else None, _lib.as_ip(out['nsites']),
+                                                 _lib.as_ip(out['nshared']), _lib.as_dp(out['tmax']), _lib.as_ip(out['lin'])))
+        return out
+
+    def cond_surfaces_ms(self):
+        """Device milliseconds of the kernels of the context's last cond_surfaces() call."""
+        return self._ms(self._L.bmx_ctx_cond_surfaces_ms)
+
     def fetch_lut(self):
         m = self.model
         shape = (len(m.x), len(m.abeta), m.rows)

@@ -258,6 +258,34 @@ int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin,
                 const double *edges, int32_t D, int32_t *O_out, double *Esel_out, double *Eneu_out,
                 int32_t *skipped_out /* [n], may be NULL */);
 int bmx_ctx_fit_ms(bmx_ctx *c, double *ms);
+/* Conditional surfaces of n PAIRS on the selected slot: the surface of a candidate window given one fitted neighbouring locus;
+ * the definition is ballermixplus_amd/conditional.py.  Pair q: the window of test site tests[q] (tg, win_lo, win_hi) and the
+ * conditioning locus cond_test[q] (a test site of the same slot: position tc and its own window bounds) held at the grid point
+ * cond_lin[q] = (iA_c * nx + ix_c) * nab + ia_c.  The candidate's sites at A are the surfaces' sites.  One of them is SHARED
+ * iff max(win_lo[c], 0) <= i <= min(win_hi[c], N - 1), zc_i = A_c * |g_i - tc| <= bmx_alpha_cut() (that single product) and
+ * g_i != tc; then d_i = exp(-zc_i) * R[ix_c][ia_c][row_i], for every other site d_i = 0.0 exactly (also with cond_test < 0 or
+ * cond_lin < 0: no conditioning locus).  With alpha_i = exp(-A |g_i - tg|) and u_i = alpha_i / (1.0 + d_i),
+ *     T_cond(A, x, abeta) = 2 * sum_i log1p(u_i * (R_i - d_i))      over the candidate's sites in increasing site index,
+ * NaN where no site qualifies at that A.
+ *   T_out[n][nA][nx][nab]  (may be NULL: the surfaces are then not copied back)
+ *   nsites_out[n][nA]      the surfaces' count (may be NULL);   nshared_out[n][nA]  the shared sites among them (may be NULL)
+ *   tmax_out[n], lin_out[n]  the scan's rule on each pair's T_cond (may be NULL): a value must be > 0, the larger wins, a tie
+ *                          goes to the smaller linear index, NaN never wins; 0 and -1 when nothing is > 0
+ * With every d_i == 0.0, u_i == alpha_i and R_i - 0.0 == R_i: T_cond, nsites, tmax and lin are then bitwise bmx_ctx_surfaces'
+ * (and its argmax), nshared 0.  cond_surfaces_kernel: one workgroup of 256 per (pair, A, slice of 256 grid pairs), no atomics;
+ * a pair's numbers depend on that pair alone (bitwise the same alone, in a list, or twice).  Chunked as bmx_ctx_surfaces:
+ * device output at or below BMX_SURFACES_CHUNK_BYTES, each chunk copied back before the next launch.
+ * BMX_E_INVALID and nothing is written: a NULL context, n < 0, a NULL tests / cond_test / cond_lin with n > 0, a tests index
+ * outside [0, M), a cond_test outside [-1, M), a cond_lin >= nA * nx * nab.  BMX_E_STATE without model, sites and test sites;
+ * bmx_ctx_cond_surfaces_ms (milliseconds the last call spent in its kernels) before a successful call is BMX_E_STATE.
+ * n == 0 succeeds.  Blocks.  Uses the surfaces' device buffers and its own; leaves sites, test sites, scan results, records,
+ * profiles, refinement, support, bootstrap, peak, null, influence, fit and locate state of every slot untouched.
+ * Added without a bump of BMX_ABI_VERSION_MINOR, as the groups above: look the symbols up to find out. */
+int bmx_ctx_cond_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *cond_test, const int32_t *cond_lin,
+                          double *T_out /* [n][nA][nx][nab], may be NULL */, int32_t *nsites_out /* [n][nA], may be NULL */,
+                          int32_t *nshared_out /* [n][nA], may be NULL */, double *tmax_out /* [n], may be NULL */,
+                          int32_t *lin_out /* [n], may be NULL */);
+int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms);
 /* Choose the scan kernel variant (0 = default). For A/B measurements only. */
 int bmx_ctx_set_variant(bmx_ctx *c, int variant);
 /* Select (creating it on first use) chromosome slot `slot`, 0 <= slot < 4096. */
