@@ -120,6 +120,9 @@ constexpr int MOM_SLOTS_LDS = 64;             // ... of which this many are used
 #ifndef BMX_FOLD_EARLY
 #define BMX_FOLD_EARLY (!USE_LDS)         // prepared kernel's fold: heads and R of the next two slots requested before this step's powers
 #endif
+#ifndef BMX_LIST_TAILS
+#define BMX_LIST_TAILS 1                  // prepared kernel's near lists: no pair step of two neutral entries, short forms for quad tails of 1 or 2
+#endif
 #ifndef BMX_MIDTRI
 #define BMX_MIDTRI 1
 #endif
@@ -1483,7 +1486,8 @@ __global__ __launch_bounds__(SCAN_THREADS_MAX) void clr_scan_grouped_kernel(Scan
 //                  (Quad entries from 64 * 12 on have no budget byte: the consumer works those out itself, as before.)
 //                  near list: n_pair entries with alpha > 1/2 (padded to whole blocks), then n_quad entries (multiple of 4),
 //                             each (E_i f64, row offset i32), in walk order; 8 neutral guard entries (what the block loops
-//                             request one block ahead)
+//                             request one block ahead).  The header's n_pair and n_quad are the padded counts; their low
+//                             bits (3 / 2 at blocks of 8 / 4) hold the number of neutral entries in the list's last block
 //                  ragged end (rag only): n_rag entries (E, row offset, flag) + 1 guard   (round 4: here, not behind the far field)
 //   far(zone)    = moments:   n_occ entries of PREP_MOM units: (M_1, row offset) (M_2, M_3) (M_4, M_5) ...
 //                  series entries: n_ser (a multiple of 4, <= 64) entries (E, row offset, order class) of far sites whose row has no
@@ -1831,11 +1835,13 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(PrepParams P) {
                 }
                 wpos += nrmax + PREP_RAG_GUARD;
             }
-            zbase_o = zbase; npp_o = n_pair_pad; nqp_o = n_quad_pad; nfar_o = nfar_tot; base_o = base; m1p_o = m1p; m2p_o = m2p;
+            // (the padded counts are multiples of BS and of 4: their low bits carry the number of neutral entries in the last block)
+            npp_o = n_pair_pad | (n_pair_pad - n_pair); nqp_o = n_quad_pad | (n_quad_pad - n_quad);
+            zbase_o = zbase; nfar_o = nfar_tot; base_o = base; m1p_o = m1p; m2p_o = m2p;
             nragv_o = nrag_v; nrmax_o = nrmax; rag_o = rag; zr_o = zr; rr_o = rr; nser_o = n_ser;
         };
         // ... second half: the moments of the occupied slots (slot order), the ragged end's entries, and the header
-        auto zone_far = [&](double *mom, const ScratchEnt *ser, int n_ser, int zbase, int n_pair_pad, int n_quad_pad, int nfar_tot, int base,
+        auto zone_far = [&](double *mom, const ScratchEnt *ser, int n_ser, int zbase, int pair_w, int quad_w, int nfar_tot, int base,
                             double m1p, double m2p, int nrag_v, int nrmax, int rag, double zr, int rr) {
             int n_occ = 0;
             if (nfar_tot) {
@@ -1925,7 +1931,7 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(PrepParams P) {
                           w2 = __builtin_amdgcn_readlane(w, 8 % J), w3 = __builtin_amdgcn_readlane(w, 12 % J);
                 if (lane == 0) {
                     int4 *o = reinterpret_cast<int4 *>(out + zbase);
-                    o[0] = int4{PREP_MAGIC | rag, n_pair_pad, n_quad_pad, n_occ};
+                    o[0] = int4{PREP_MAGIC | rag, pair_w, quad_w, n_occ};
                     o[1] = int4{nfar_tot + n_ser, rag ? nrmax : 0, rag ? PREP_ZONE_DONE : base, ser_w};      // n_far: every site of the far field
                     o[2] = int4{w0, w1, w2, w3};
                 }
@@ -2261,9 +2267,11 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
             h0 = int4{hp[0], hp[1], hp[2], hp[3]}; h1 = int4{hp[4], hp[5], hp[6], hp[7]}; h3 = int4{hp[12], hp[13], hp[14], hp[15]};
         };
         auto hdr_ok = [&](const int4 h0, const int4 h1, const int4 h3) -> bool {
-            const int magic = h0.x, n_pair = h0.y, n_quad = h0.z, n_occ = h0.w, nrmax = h1.y, ser_w = h1.w;
+            const int magic = h0.x, n_pair = h0.y & ~(BS - 1), n_quad = h0.z & ~3, n_occ = h0.w, nrmax = h1.y, ser_w = h1.w;
             const int n_ser = ser_w & 0xff, c8 = (ser_w >> 8) & 0xff, c5 = (ser_w >> 16) & 0xff, c3 = (ser_w >> 24) & 0xff;
-            return !((magic & ~3) != PREP_MAGIC || (magic & 3) == 2 || n_pair < 0 || n_quad < 0 || n_pair > N + 8 || n_quad > N + 8 || n_occ < 0 ||
+            // (low bits of the list lengths: neutral entries in the last block -- fewer than a block, none in an empty list)
+            return !((magic & ~3) != PREP_MAGIC || (magic & 3) == 2 || h0.y < 0 || h0.z < 0 || n_pair > N + 8 || n_quad > N + 8 || n_occ < 0 ||
+                     (n_pair == 0 && h0.y != 0) || (n_quad == 0 && h0.z != 0) ||
                      n_occ > MOM_SLOTS || nrmax < 0 || nrmax >= WAVE || n_ser > SER_CAP || (n_ser & 3) || c8 > c5 || c5 > c3 || c3 > n_ser ||
                      (h3.x & 0xffff) > 1000 || (h3.x >> 17) != 0);
         };
@@ -2388,7 +2396,9 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                 load_f(pos + PREP_HDR_INT, F);
                 need();
                 const int magic = h0.x;
-                const int n_pair = h0.y, n_quad = h0.z, n_occ = h0.w;
+                const int n_pair = h0.y & ~(BS - 1), n_quad = h0.z & ~3, n_occ = h0.w;
+                // neutral entries in each list's last block (E = 0: a factor of exactly 1)
+                const int pair_pad = BMX_LIST_TAILS ? h0.y & (BS - 1) : 0, quad_pad = BMX_LIST_TAILS ? h0.z & 3 : 0;
                 const int nfar_tot = h1.x, nrmax = h1.y, base_end = h1.z, ser_w = h1.w;
                 const int rag = magic & 3;
                 const int span8 = h3.x & 0xffff;                  // exponent budget of a pair entry, from the list's largest alpha
@@ -2414,7 +2424,13 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                             Rp[u] = loadR(en.ro);
                         }
                     }
-                    for (int l0 = 0; l0 < n_pair; l0 += BS) {
+                    // one block; tail: the list's last block with nreal <= BS - 2 real entries.  A pair step of two neutral entries
+                    // has v = +-0, so sv and qv are zeros and every factor is fma(F, +-0, 1.0) = 1.0 exactly: acc * 1.0 is skipped
+                    // (a step with one real entry stays).  The tail is code of its own behind the loop, so that the loop over the
+                    // whole blocks stays one basic block (a branch inside it: +1.5 % on the whole step); it asks for nothing ahead --
+                    // what follows the list is the quad list's own first request, or the guard.
+                    auto pair_block = [&](auto tailc, int nreal) {
+                        constexpr bool tail = decltype(tailc)::value;
                         need();
                         const ScratchEnt *rp = ring + (pos & (RING_UNITS - 1));
                         spend(span8 * BS / 8);
@@ -2422,11 +2438,13 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                         if (BMX_PPAIR_PREFETCH) {
 #pragma unroll
                             for (int u = 0; u < BS; ++u) v[u] = ep[u] * Rp[u];
+                            if (!tail) {
 #pragma unroll
-                            for (int u = 0; u < BS; ++u) {
-                                const ScratchEnt en = rp[BS + u];
-                                ep[u] = en.e;
-                                Rp[u] = loadR(en.ro);
+                                for (int u = 0; u < BS; ++u) {
+                                    const ScratchEnt en = rp[BS + u];
+                                    ep[u] = en.e;
+                                    Rp[u] = loadR(en.ro);
+                                }
                             }
                         } else {
 #pragma unroll
@@ -2437,12 +2455,16 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                         }
 #pragma unroll
                         for (int u = 0; u < BS; u += 2) {
+                            if (tail && (u >= BS - 2 || (u > 0 && u >= nreal))) break;
                             const double sv = v[u] + v[u + 1], qv = v[u] * v[u + 1];
 #pragma unroll
                             for (int j = 0; j < J; ++j) acc[j] *= fma(F[j], fma(F[j], qv, sv), 1.0);
                         }
                         pos += BS;
-                    }
+                    };
+                    const int n_pair_main = pair_pad >= 2 ? n_pair - BS : n_pair;
+                    for (int l0 = 0; l0 < n_pair_main; l0 += BS) pair_block(std::false_type{}, BS);
+                    if (pair_pad >= 2) pair_block(std::true_type{}, BS - pair_pad);
                 }
                 PROF_MARK(2);
                 if (n_quad > 0) {
@@ -2458,7 +2480,15 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                             Rn[u] = loadR(en.ro);
                         }
                     }
-                    for (int l0 = 0; l0 < n_quad; l0 += 4) {
+                    // one block; tail: the list's last block with nreal = 1 or 2 real entries -- the neutral ones have v = +-0.  With
+                    // v2 = v3 = +-0: s23 and q23 are zeros, so e1 = s01 + 0 = s01, e2 = fma(s01, 0, q01 + 0) = q01, e3 = fma(q01, 0, 0 s01)
+                    // and e4 = q01 0 are zeros, and the chain is t = 0, t = fma(F, 0, q01) = q01, t = fma(F, q01, s01): the pair step.
+                    // With v1 = +-0 as well: s01 = v0, q01 a zero, and the chain ends in t = fma(F, 0, v0) = v0.  (x + 0 = x and
+                    // fma(a, 0, c) = c hold exactly for x, c != 0 whatever the zero's sign; where x or c is itself a zero only the sign
+                    // of a zero can differ, and every such zero ends in fma(F, +-0, 1.0) = 1.0.)  Three real entries keep the
+                    // four-site form.  Code of its own behind the loop, like the pair list's; its budget is the block's as before.
+                    auto quad_block = [&](auto tailc, int l0, int nreal) {
+                        constexpr bool tail = decltype(tailc)::value;
                         need();
                         const ScratchEnt *rp = ring + (pos & (RING_UNITS - 1));
                         if ((l0 & 63) == 0) {
@@ -2475,31 +2505,47 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
                             }
                         }
                         spend(span8q / 2);
-                        double v[4];
+                        if constexpr (tail) {
+                            const double v0 = en_e[0] * Rn[0];
+                            if (nreal == 2) {
+                                const double v1 = en_e[1] * Rn[1];
+                                const double s01 = v0 + v1, q01 = v0 * v1;
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) v[u] = en_e[u] * Rn[u];
+                                for (int j = 0; j < J; ++j) acc[j] *= fma(F[j], fma(F[j], q01, s01), 1.0);
+                            } else {
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const ScratchEnt en = rp[4 + u];
-                            en_e[u] = en.e;
-                            Rn[u] = loadR(en.ro);
-                        }
-                        const double s01 = v[0] + v[1], q01 = v[0] * v[1];
-                        const double s23 = v[2] + v[3], q23 = v[2] * v[3];
-                        const double e1 = s01 + s23;
-                        const double e2 = fma(s01, s23, q01 + q23);
-                        const double e3 = fma(q01, s23, q23 * s01);
-                        const double e4 = q01 * q23;
+                                for (int j = 0; j < J; ++j) acc[j] *= fma(F[j], v0, 1.0);
+                            }
+                        } else {
+                            double v[4];
 #pragma unroll
-                        for (int j = 0; j < J; ++j) {
-                            double t = fma(F[j], e4, e3);
-                            t = fma(F[j], t, e2);
-                            t = fma(F[j], t, e1);
-                            acc[j] *= fma(F[j], t, 1.0);
-                            if ((j & (BMX_QSB - 1)) == BMX_QSB - 1) __builtin_amdgcn_sched_barrier(0);
+                            for (int u = 0; u < 4; ++u) v[u] = en_e[u] * Rn[u];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const ScratchEnt en = rp[4 + u];
+                                en_e[u] = en.e;
+                                Rn[u] = loadR(en.ro);
+                            }
+                            const double s01 = v[0] + v[1], q01 = v[0] * v[1];
+                            const double s23 = v[2] + v[3], q23 = v[2] * v[3];
+                            const double e1 = s01 + s23;
+                            const double e2 = fma(s01, s23, q01 + q23);
+                            const double e3 = fma(q01, s23, q23 * s01);
+                            const double e4 = q01 * q23;
+#pragma unroll
+                            for (int j = 0; j < J; ++j) {
+                                double t = fma(F[j], e4, e3);
+                                t = fma(F[j], t, e2);
+                                t = fma(F[j], t, e1);
+                                acc[j] *= fma(F[j], t, 1.0);
+                                if ((j & (BMX_QSB - 1)) == BMX_QSB - 1) __builtin_amdgcn_sched_barrier(0);
+                            }
                         }
                         pos += 4;
-                    }
+                    };
+                    const int n_quad_main = quad_pad >= 2 ? n_quad - 4 : n_quad;
+                    for (int l0 = 0; l0 < n_quad_main; l0 += 4) quad_block(std::false_type{}, l0, 4);
+                    if (quad_pad >= 2) quad_block(std::true_type{}, n_quad_main, 4 - quad_pad);
                 }
                 PROF_MARK(3);
                 pos += PREP_GUARD;
@@ -2577,6 +2623,10 @@ __global__ __launch_bounds__((J == 8 && USE_LDS) ? SCAN_THREADS_J8 : SCAN_THREAD
 #pragma unroll
                 for (int k = 0; k < P_ORDER; ++k) pk[k] = 0.0;
                 // p_k += M_k R^k for one moment entry (q: its units 1.. as (M_2, M_3), (M_4, M_5), ...); powers by halving: depth log2 k
+                // (Measured and dropped: stopping an entry's powers and FMAs at its top non-zero order -- a slot of few, far sites ends in
+                // M_k = +0.0, 60 % of the entries at config 4 -- written by prep_kernel into the entry's first unit.  Exact, and fewer
+                // instructions, but the wave-uniform branches inside the fold cost more than the skipped arithmetic: +2.0 % on the
+                // whole step with a cut per unit, +1.4 % with two cuts and every unit still read up front; profiles/fold_tails_ab.txt.)
                 auto fold = [&](const double m1, const double2 *q, const double R) {
                     double pw[P_ORDER + 1];
                     pw[1] = R;
