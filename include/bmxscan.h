@@ -248,7 +248,8 @@ int bmx_ctx_influence_ms(bmx_ctx *c, double *ms);
  * BMX_E_INVALID and nothing is written: a NULL context, n < 0, a NULL tests / lin / gw / cls / edges (D > 1) / O_out / Esel_out /
  * Eneu_out with n > 0, an index outside [0, M), lin >= nA * nx * nab, F < 1, D < 1, D * F > BMX_FIT_MAX_CELLS, an edge that is
  * not finite, not > 0 or not above the one before, a cls outside [0, F), a gw outside [0, 1] (NaN included).  BMX_E_STATE
- * without model, sites and test sites; bmx_ctx_fit_ms (milliseconds the last call spent in its kernels) before a successful call
+ * without model, sites and test sites: n < 0, F < 1, D < 1 and D * F > BMX_FIT_MAX_CELLS are refused before the state is looked
+ * at (as bmx_ctx_influence's block < 1), every other argument after it; bmx_ctx_fit_ms (milliseconds the last call spent in its kernels) before a successful call
  * is BMX_E_STATE.  n == 0 succeeds.  Blocks.  Leaves sites, test sites, scan results, records, profiles, refinement, support,
  * bootstrap, peak, null, influence and locate state of every slot untouched.
  * Added without a bump of BMX_ABI_VERSION_MINOR, as the groups above: look the symbols up to find out. */

@@ -18,6 +18,16 @@ sites: a dense run of 613 (stride 1: prepared J = 16), every 5th site (prepared 
 ragged index windows (the recipe of gridshape.windows_of for any length).  COST_CAP keeps the product test sites x window x pairs x A
 of a scan small: the long chromosomes are scanned with the cheap models or ragged windows.
 
+fit and cond_surfaces (the groups 'fit' and 'conditional') take their lists as surfaces and influence do (index_list); fit's grid
+points and cond_surfaces' conditioning sites and grid points follow fixed spread rules (fit_lins, cond_lists), gw is the world's
+admissible weights (capped at 1: fit_gw), cls fit.classes and edges fit.default_edges of the op's (F, D) out of FIT_SHAPES.  On
+w4 (221 sample sizes) F = 7 and F = 10 keep fit's prologue sums in the workspace in device memory, everything else in LDS.
+
+Scripts: the hand-written one and five seeded walks.  The three walks of OLD_WALK_SEEDS were drawn before fit and cond_surfaces had
+ops and stay op for op what they were (walk() draws them from _WEIGHTS); the two of NEW_WALK_SEEDS draw from _NEW_WEIGHTS, which
+weights the two new ops 3 each.  The hand-written script keeps its earlier ops in order, the new ones are inserted
+(tests/test_lifetime_cpu.py pins both with a sha256).
+
 An op is (name, {argument: plain value}); every array an op needs is derived from its plain arguments and the state by the
 functions at the end of this module, so that a script is a list of small tuples that can be compared and printed.
 """
@@ -53,6 +63,8 @@ GROUPS = {
                 'eval_points_weighted'),
     'peaks': ('peaks', 'peaks_track', 'fetch_peaks'),
     'surfaces': ('surfaces', 'influence'),
+    'fit': ('fit',),
+    'conditional': ('cond_surfaces',),
     'locate': ('resample_sites', 'locate_begin', 'locate_accumulate', 'fetch_locate'),
     'plant': ('plant_sites', 'fetch_at'),
     'pack_records': ('pack_records',),
@@ -65,6 +77,9 @@ NO_PROFILE_VARIANTS = (12,)
 PROFILE_SETS = (0, 7, 1, 4)
 CHUNKS = (0, 64, 1000)
 LISTS = (1, 3, 40)
+FIT_SHAPES = ((1, 1), (7, 6), (10, 25))          # (F, D) of a fit call: on w4 the last two keep their sums in the workspace home
+FIT_LDS_BYTES = 40 << 10                         # BMX_FIT_LDS_BYTES: n_sizes * (F + 1) * 24 bytes of sums fit LDS up to here
+FIT_BAD = ('F', 'lin', 'gw')                     # F = 0, lin = nA * npairs, gw[0] = 1.5: all BMX_E_INVALID
 STRIDES = (1, 5, 20)
 WINDOWS = ('all', 'ragged')
 MAX_SLOTS = 4096
@@ -119,6 +134,8 @@ class World:
             self.chroms['M'] = (_frozen(parts[0][0]), _frozen(parts[0][1]))
             self.chroms['L'] = (_frozen(np.concatenate([p[0] for p in parts])), _frozen(np.concatenate([p[1] for p in parts])))
         self.gw = power.allowed_rows('B2', 1, self.model.sizes, self.model.row_off, self.model.g)
+        # bmx_ctx_fit refuses a gw above 1 (no probability): gridshape's spectrum holds one row at LOW_G = 8
+        self.fit_gw = _frozen(np.minimum(self.gw, 1.0))
         self.nA, self.nx, self.nab = len(self.As), len(self.xs), len(self.abetas)
         self.cost = self.nA * self.nx * self.nab
 
@@ -167,13 +184,37 @@ def scan_cost(w, N, stride, windows):
 
 # ------------------------------------------------------------------------------------------------ arrays of an op's plain arguments
 def index_list(kind, M):
-    """The window lists of surfaces / influence / fetch_at: 1, 3 or 40 indices into M test sites, any order, with repeats."""
+    """The window lists of surfaces / influence / fit / cond_surfaces / fetch_at: 1, 3 or 40 indices into M test sites, any order, with repeats."""
     base = (np.arange(kind, dtype=np.int64) * 7919 + 5) % max(M, 1)
     if kind >= 3:
         base[-1] = base[0]                                            # a repeat
     if kind >= 40:
         base[7], base[8] = M - 1, 0
     return base.astype(np.int32)
+
+
+def fit_lins(kind, points):
+    """One grid point per listed window by a fixed spread rule (tests/fitcases.spread's), the second entry without one."""
+    v = (np.arange(kind, dtype=np.int64) * 7919 + 5) % points
+    if kind >= 3:
+        v[1] = -1
+    return v.astype(np.int32)
+
+
+def cond_lists(tests, M, points):
+    """(cond_test, cond_lin) of a cond_surfaces call: the test site three further on (mod M), every fourth entry without one; a
+    spread grid point, the third entry without one."""
+    ct = (np.asarray(tests, dtype=np.int64) + 3) % max(M, 1)
+    ct[3::4] = -1
+    cl = (np.arange(len(ct), dtype=np.int64) * 7919 + 11) % points
+    if len(cl) >= 3:
+        cl[2] = -1
+    return ct.astype(np.int32), cl.astype(np.int32)
+
+
+def fit_in_lds(w, F):
+    """Whether bmx_ctx_fit keeps the prologue sums of a window of this model in LDS (else in its workspace in device memory)."""
+    return len(w.model.sizes) * (F + 1) * 24 <= FIT_LDS_BYTES
 
 
 def track_of(n, seed):
@@ -489,6 +530,19 @@ class State:
             self.infl = True
         return 0
 
+    # ---- fit, cond_surfaces: list_ready's rule (model, sites and test sites, no scan); they commit nothing
+    def _fit(self, a, commit):
+        if a['F'] < 1:                               # the call's own argument refusal comes before the state's
+            return INVALID
+        if not self.ready():
+            return STATE
+        return INVALID if a.get('bad') else 0
+
+    def _cond_surfaces(self, a, commit):
+        if not self.ready():
+            return STATE
+        return INVALID if a.get('bad') else 0
+
     # ---- derived sites
     def _source(self, a):
         """(code, source slot) of resample_sites / plant_sites' src argument, before their own argument checks."""
@@ -606,12 +660,13 @@ def _prepare(chrom, stride, windows):
 
 
 def hand_script():
-    """The required transitions, in the order of the issue's list where the state allows it (tests/test_lifetime_cpu.py finds
-    each one in the script itself)."""
+    """The required transitions, in the order of their list where the state allows it (tests/test_lifetime_cpu.py finds each one
+    in the script itself); the fit and cond_surfaces ops (transition 13) stand among the surfaces and influence calls of 9. and 2."""
     K1, K2 = 0x1234567890ABCDEF, 0x0FEDCBA987654321
     s = [op('scan'), op('set_sites', chrom='S'), op('scan_write', chunk=0), op('restore_rows'), op('null_begin'), op('eval_points'),
          op('fetch_peaks'),                                                          # all refused: nothing is set
-         op('set_model', model='g3x3')]
+         op('set_model', model='g3x3'),
+         op('fit', kind=1, F=1, D=1), op('cond_surfaces', kind=1, want_T=True)]         # refused: no sites yet
     # 1. one slot long -> short -> medium, M large -> small -> larger
     s += _prepare('L', 5, 'all') + _prepare('S', 20, 'ragged') + _prepare('M', 5, 'ragged')
     # 3. the same test sites under profiles 0 -> 7 -> 1 -> 0 and variants 0 -> 12 -> 0 (and the LIMIT refusal in between)
@@ -665,13 +720,21 @@ def hand_script():
           op('peaks_track', n=300, seed=1, **PEAKS), op('fetch_peaks'), op('refine', min_clr=0.0),
           op('peaks', **PEAKS), op('refine', min_clr=0.0), op('fetch_refined'), op('refine_at_peaks', on=False)]
     # 9. surfaces and influence with 40 windows, then 1, then again after every change of the model's shape
-    s += [op('surfaces', kind=40), op('influence', kind=40, block=50), op('surfaces', kind=1, bad=True), op('surfaces', kind=1),
-          op('influence', kind=3, block=0), op('influence', kind=1, block=50)]
+    #    13. fit and cond_surfaces with 40 windows, then 1, directly after surfaces and influence calls with longer and shorter lists
+    s += [op('surfaces', kind=40), op('fit', kind=1, F=7, D=6), op('influence', kind=40, block=50), op('cond_surfaces', kind=1, want_T=True),
+          op('fit', kind=40, F=10, D=25), op('cond_surfaces', kind=40, want_T=True),
+          op('surfaces', kind=1, bad=True), op('surfaces', kind=1), op('cond_surfaces', kind=40, want_T=False), op('fit', kind=1, F=1, D=1),
+          op('influence', kind=3, block=0), op('influence', kind=1, block=50), op('fit', kind=40, F=1, D=1), op('fit', kind=3, F=0, D=6),
+          op('fit', kind=3, F=7, D=6), op('fit', kind=3, F=7, D=6, bad='lin'), op('fit', kind=1, F=10, D=25), op('fit', kind=40, F=7, D=6, bad='gw'),
+          op('cond_surfaces', kind=3, want_T=True, bad=True), op('cond_surfaces', kind=1, want_T=False), op('cond_surfaces', kind=3, want_T=True)]
     # 2. the models, each with a scan (and the 4-byte rows between two scans on 2-byte rows); every other slot's sites are gone
     for m in HAND_MODELS[1:]:
         s += [op('set_model', model='bad'), op('set_model', model=m), op('select_slot', slot=2), op('set_tests', stride=5, windows='all'),
               op('select_slot', slot=0)]
-        s += _prepare('M', 1, 'ragged') + [op('surfaces', kind=40), op('influence', kind=40, block=64), op('influence', kind=1, block=64),
+        s += _prepare('M', 1, 'ragged') + [op('surfaces', kind=40), op('cond_surfaces', kind=3, want_T=False),
+                                          op('influence', kind=40, block=64), op('fit', kind=3, F=1, D=1),
+                                          op('influence', kind=1, block=64), op('cond_surfaces', kind=40, want_T=True),
+                                          op('fit', kind=40, F=7, D=6), op('fit', kind=1, F=10, D=25), op('cond_surfaces', kind=1, want_T=False),
                                           op('select_slot', slot=1)] + _prepare('S', 5, 'all')
         s += [op('set_profiles', which=4), op('permute_rows', key=K1, block=2), op('scan'), op('fetch_profile', which=1),
               op('fetch_profile', which=4), op('set_profiles', which=0)]
@@ -686,10 +749,16 @@ def hand_script():
     return s
 
 
-WALK_SEEDS = (20261101, 20261102, 20261103)
+OLD_WALK_SEEDS = (20261101, 20261102, 20261103)               # drawn before fit and cond_surfaces had ops: they stay what they were
+NEW_WALK_SEEDS = (20261105, 20261110)                         # drawn from the table that also weights the two (the first two seeds
+#                                                               after the earlier ones whose walk has both ops succeed twice, one of
+#                                                               them on the workspace home of w4; tests/test_lifetime_cpu.py asserts it)
+WALK_SEEDS = OLD_WALK_SEEDS + NEW_WALK_SEEDS
+NEW_OPS = ('fit', 'cond_surfaces')
 WALK_LENGTH = 88
 WALK_SLOTS = (0, 1, 2)
-WALK_MODELS = {20261101: ('g3x3', 'l2', 'g1', 'g17x61'), 20261102: ('w4', 'g3x3', 'g17x61', 'l2'), 20261103: ('g17x61', 'g1', 'w4', 'g3x3')}
+WALK_MODELS = {20261101: ('g3x3', 'l2', 'g1', 'g17x61'), 20261102: ('w4', 'g3x3', 'g17x61', 'l2'), 20261103: ('g17x61', 'g1', 'w4', 'g3x3'),
+               20261105: ('w4', 'g1', 'l2', 'g17x61'), 20261110: ('g1', 'w4', 'g3x3', 'l2')}
 BAD_SHARE = 0.07                 # deliberately bad arguments; refusals by state come on top (kept with probability KEEP_REFUSED)
 KEEP_REFUSED = 0.3
 
@@ -699,6 +768,7 @@ _WEIGHTS = {'set_sites': 4, 'set_tests': 6, 'select_slot': 6, 'set_variant': 3, 
             'eval_points_weighted': 2, 'peaks': 3, 'peaks_track': 2, 'fetch_peaks': 1, 'surfaces': 3, 'influence': 3,
             'resample_sites': 3, 'locate_begin': 2, 'locate_accumulate': 3, 'fetch_locate': 2, 'plant_sites': 3, 'fetch_at': 3,
             'pack_records': 3}
+_NEW_WEIGHTS = dict(_WEIGHTS, fit=3, cond_surfaces=3)
 
 
 def _draw(rng, st, name):
@@ -748,6 +818,12 @@ def _draw(rng, st, name):
     if name == 'influence':
         blk = 0 if bad and rng.random() < 0.5 else pick((16, 200))
         return op(name, kind=pick(LISTS), block=blk, **({'bad': True} if bad and blk else {}))
+    if name == 'fit':
+        F, D = pick(FIT_SHAPES)
+        how = pick(FIT_BAD) if bad else None
+        return op(name, kind=pick(LISTS), F=0 if how == 'F' else F, D=D, **({'bad': how} if how in ('lin', 'gw') else {}))
+    if name == 'cond_surfaces':
+        return op(name, kind=pick(LISTS), want_T=bool(pick((True, False))), **({'bad': True} if bad else {}))
     if name == 'resample_sites':
         return op(name, src=st.cur if bad else pick(others), key=key, block=pick((1, 5, 64)))
     if name == 'plant_sites':
@@ -769,7 +845,8 @@ def walk(seed, length=WALK_LENGTH):
     selected slot lacks (sites, test sites, a scan) preferred, refusals kept at about one op in eight."""
     rng = np.random.default_rng([20261023, seed])
     st = State(R_of=lambda m: None)
-    names, weights = list(_WEIGHTS), np.array(list(_WEIGHTS.values()), dtype=np.float64)
+    table = _WEIGHTS if seed in OLD_WALK_SEEDS else _NEW_WEIGHTS
+    names, weights = list(table), np.array(list(table.values()), dtype=np.float64)
     models = WALK_MODELS[seed]
     ops = []
     while len(ops) < length:
@@ -796,7 +873,7 @@ def walk(seed, length=WALK_LENGTH):
 def _is_bad(o):
     a = o[1]
     return (a.get('block') == 0 or a.get('R') == 0 or a.get('stride') == 0 or a.get('chrom') == 'bad' or a.get('slot') == MAX_SLOTS
-            or a.get('which') == 8 or a.get('frac') == 0.0 or a.get('drop') == 0.0 or a.get('short')
+            or a.get('which') == 8 or a.get('F') == 0 or a.get('frac') == 0.0 or a.get('drop') == 0.0 or a.get('short')
             or NAN in a.values())
 
 

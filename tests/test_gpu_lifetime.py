@@ -12,7 +12,10 @@ Every test runs one script in ONE engine.Context that is closed only at the end.
   * after every op one OTHER slot that holds results is fetched again and must be what it was when it was scanned.
   * at three checkpoints per script (one of them after the last set_model) the long-lived context's scan is compared with
     util.c_scan on the device's own table: integer fields exact outside the oracle's near-ties (gridshape.decide, at most 2 % of
-    the windows), CLR within rtol 1e-9 / atol 1e-12 on every window -- so that the two contexts cannot be wrong together.
+    the windows), CLR within rtol 1e-9 / atol 1e-12 on every window -- so that the two contexts cannot be wrong together.  At the
+    same checkpoints its fit and cond_surfaces of a 3-entry list are compared with fit.host_fit and
+    conditional.host_cond_surface on the device's own table, at those features' tolerances (fitcases.TOL * max(1, n_d) per cell,
+    condcases.REL_TOL of the conditional scale; integer fields exact).
 """
 import collections
 import time
@@ -20,11 +23,28 @@ import time
 import numpy as np
 import pytest
 
+import condcases as cc
+import fitcases as fc
 import gridshape as gs
 import lifetime as lt
 from util import c_oracle, c_scan
 
+from ballermixplus_amd import conditional, fit
+
 pytestmark = pytest.mark.gpu
+
+ANCHOR_FIT = (7, 6)                  # (F, D) of the fit compared with host_fit at the checkpoints
+
+
+def _zcut():
+    from ballermixplus_amd import _lib
+    return float(_lib.lib().bmx_alpha_cut())
+
+
+def _fit_arrays(w, F, D):
+    """(gw, cls, edges) of a fit call on a world's model (D = 1: no edge)."""
+    m = w.model
+    return w.fit_gw, fit.classes('B2', m.sizes, m.row_off, max(F, 1)), fit.default_edges(D, _zcut())
 
 
 def _bytes(v):
@@ -131,6 +151,23 @@ class Runner:
             if a.get('bad'):
                 v[-1] = s.M
             return {'list': v}
+        if name == 'fit':
+            v = lt.index_list(a['kind'], s.M)
+            points = w.nA * w.nx * w.nab
+            lin = lt.fit_lins(a['kind'], points)
+            gw, cls, edges = _fit_arrays(w, a['F'], a['D'])
+            if a.get('bad') == 'lin':
+                lin[-1] = points
+            if a.get('bad') == 'gw':
+                gw = gw.copy()
+                gw[0] = 1.5
+            return {'list': v, 'lin': lin, 'gw': gw, 'cls': cls, 'edges': edges}
+        if name == 'cond_surfaces':
+            v = lt.index_list(a['kind'], s.M)
+            ct, cl = lt.cond_lists(v, s.M, w.nA * w.nx * w.nab)
+            if a.get('bad'):
+                ct[-1] = s.M
+            return {'list': v, 'ct': ct, 'cl': cl}
         if name == 'plant_sites':
             src = st.slots.get(a['src'])
             have = src is not None and src.sites is not None and 0 <= a['iA'] < w.nA if w else False
@@ -226,6 +263,10 @@ class Runner:
             return ctx.surfaces(g['list'])
         if name == 'influence':
             return ctx.influence(g['list'], a['block'])
+        if name == 'fit':
+            return ctx.fit(g['list'], g['lin'], g['gw'], g['cls'], a['F'], g['edges'])
+        if name == 'cond_surfaces':
+            return ctx.cond_surfaces(g['list'], g['ct'], g['cl'], want_T=a['want_T'])
         if name == 'resample_sites':
             n = ctx.resample_sites(a['src'], a['key'], a['block'])
             return n, (ctx.fetch_sites(n) if n else None)
@@ -359,7 +400,7 @@ class Runner:
             elif name == 'set_variant':
                 self._setup(room, dict(d, variant=0))
             else:
-                assert name in ('scan', 'scan_write', 'surfaces', 'influence', 'eval_points', 'eval_points_weighted'), name
+                assert name in ('scan', 'scan_write', 'surfaces', 'influence', 'fit', 'cond_surfaces', 'eval_points', 'eval_points_weighted'), name
                 self._setup(room, d)
             return self.do(room, o, g, **kw)
         finally:
@@ -407,7 +448,44 @@ class Runner:
         for q in (1, 2, 3, 4):
             assert np.array_equal(got[q][keep], ref[q][keep]), (i, q, np.nonzero(got[q] != ref[q])[0][:8])
         assert np.allclose(got[0], ref[0], rtol=1e-9, atol=1e-12), (i, worst)
+        self.anchor_listed(i, w, gen, rows, t['tg'], lo, hi)
         self.anchors.append(i)
+
+    def anchor_listed(self, i, w, gen, rows, tg, lo, hi):
+        """The long-lived context's fit and cond_surfaces of a 3-entry list against the host restatements on the device's table."""
+        R, zcut, M = device_table(self.st.model), _zcut(), len(tg)
+        v = lt.index_list(3, M)
+        points, npairs = w.nA * w.nx * w.nab, w.nx * w.nab
+        F, D = ANCHOR_FIT
+        lin = lt.fit_lins(3, points)
+        gw, cls, edges = _fit_arrays(w, F, D)
+        O, Es, En, sk = self.ctx.fit(v, lin, gw, cls, F, edges)
+        worst_fit = 0.0
+        for q, (j, l) in enumerate(zip(v.tolist(), lin.tolist())):
+            if l < 0:
+                assert not O[q].any() and np.isnan(Es[q]).all() and np.isnan(En[q]).all() and sk[q] == 0
+                continue
+            hO, hEs, hEn, hsk = fit.host_fit(gen, rows, w.model.row_off, R, gw, cls, F, edges, w.As[l // npairs], (l // w.nab) % w.nx, l % w.nab,
+                                             tg[j], lo[j], hi[j], zcut)
+            assert np.array_equal(O[q], hO) and sk[q] == hsk, (i, q)
+            bound = fc.TOL * np.maximum(1, hO.sum(axis=1))[:, None]
+            worst_fit = max(worst_fit, float(np.max(np.abs(Es[q] - hEs) / bound)), float(np.max(np.abs(En[q] - hEn) / bound)))
+        assert worst_fit <= 1.0, (i, worst_fit)
+        ct, cl = lt.cond_lists(v, M, points)
+        res = self.ctx.cond_surfaces(v, ct, cl, want_T=True)
+        worst_cond = 0.0
+        for q, (j, c, l) in enumerate(zip(v.tolist(), ct.tolist(), cl.tolist())):
+            if c < 0 or l < 0:
+                Th, nh, sh, S = conditional.host_cond_surface(gen, rows, R, w.As, tg[j], lo[j], hi[j], None, 0, -1, 0.0, 0, 0, zcut, scale=True)
+            else:
+                Th, nh, sh, S = conditional.host_cond_surface(gen, rows, R, w.As, tg[j], lo[j], hi[j], tg[c], lo[c], hi[c], w.As[l // npairs],
+                                                              (l // w.nab) % w.nx, l % w.nab, zcut, scale=True)
+            assert np.array_equal(res['nsites'][q], nh) and np.array_equal(res['nshared'][q], sh), (i, q)
+            assert np.array_equal(np.isnan(res['T'][q]), np.isnan(Th)), (i, q)
+            if (nh > 0).any():
+                worst_cond = max(worst_cond, float(np.nanmax(np.abs(res['T'][q] - Th))) / (cc.REL_TOL * float(S.max())))
+        assert worst_cond <= 1.0, (i, worst_cond)
+        print('  listed anchor at op %d: fit (F %d, D %d) worst %.2e of its bound, cond_surfaces worst %.2e of its tolerance' % (i, F, D, worst_fit, worst_cond))
 
     def run(self, ops, anchors):
         st, ctx = self.st, self.ctx

@@ -1,8 +1,10 @@
 """tests/lifetime.py on the host: the scripts that tests/test_gpu_lifetime.py runs in one long-lived context are deterministic, hold
 every transition they are meant to hold, run every op group before every other, compare every group at least five times and meet
 every error code; the state model answers a table of rows restated from include/bmxscan.h as the header does; and the site arrays
-it expects after permute, restore, resample and plant are what the package's host restatements give.  No GPU."""
+it expects after permute, restore, resample and plant are what the package's host restatements give.  The scripts from before fit
+and cond_surfaces had ops are pinned by their sha256, and the fit ops reach both homes of the prologue sums.  No GPU."""
 import collections
+import hashlib
 
 import numpy as np
 import pytest
@@ -80,6 +82,29 @@ def test_scripts_are_deterministic(scripts):
         assert len(ops) >= 80 and len(slots) >= 3
         assert len(ops) / 16 <= n_ref <= len(ops) / 4              # about one op in eight
     assert scripts['walk%d' % lt.WALK_SEEDS[0]] != scripts['walk%d' % lt.WALK_SEEDS[1]]
+
+
+# sha256 of repr() of the scripts as they were before fit and cond_surfaces had ops
+PINNED = {'hand': 'f33bfc16a490813785aa3927fc6cc387ee04f80682c52f20e7806a109c0f63c7',
+          'walk20261101': '89d6ccf692b7ebab8e06591903fd5c02c22f2d2a57b0621a99922e8b96676454',
+          'walk20261102': 'a98854200f3b9b65f1d4f24ba3d7086c74e6e0a2e1ac0978372af43635988381',
+          'walk20261103': '09faa44244ca0223ca72b558b998e689d136af8628bb864ad61c123b5d77e497'}
+
+
+def test_the_earlier_scripts_are_what_they_were(scripts):
+    """The three earlier walks op for op; the hand-written script keeps its earlier ops in order, the new ones are inserted."""
+    assert set(PINNED) == {'hand'} | {'walk%d' % s for s in lt.OLD_WALK_SEEDS}
+    for k, want in PINNED.items():
+        ops = scripts[k]
+        if k == 'hand':
+            assert sum(o[0] in lt.NEW_OPS for o in ops) >= 30
+            ops = [o for o in ops if o[0] not in lt.NEW_OPS]
+        else:
+            assert not any(o[0] in lt.NEW_OPS for o in ops)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == want, k
+    for seed in lt.NEW_WALK_SEEDS:                      # the new walks draw both new ops, succeeding
+        done = collections.Counter(o[0] for o, c, _ in _run(scripts['walk%d' % seed]) if c == 0)
+        assert all(done[n] >= 2 for n in lt.NEW_OPS), (seed, done)
 
 
 def test_worlds():
@@ -167,6 +192,19 @@ def test_required_transitions(scripts):
     for a, b in zip(cuts[1:], cuts[2:]):
         part = run[a:b]
         assert _chain(part, [ok('surfaces', kind=40)]) and _chain(part, [ok('influence', kind=40), ok('influence', kind=1)]), a
+    # 13. fit and cond_surfaces: 40 windows, then 1, again after every change of the model's shape, and directly after surfaces
+    #     and influence calls with longer and shorter lists (the shared buffers grow and shrink)
+    for name in lt.NEW_OPS:
+        assert _chain(run, [ok(name, kind=40), ok(name, kind=1)]) and _chain(run, [ok(name, kind=1), ok(name, kind=40)]), name
+        for a, b in zip(cuts[1:], cuts[2:]):
+            assert _chain(run[a:b], [ok(name, kind=40), ok(name, kind=1)]), (name, a)
+        after = {(run[i - 1][0][0], run[i - 1][0][1]['kind'], o[1]['kind']) for i, (o, c, s) in enumerate(run)
+                 if o[0] == name and c == 0 and run[i - 1][1] == 0 and run[i - 1][0][0] in ('surfaces', 'influence')}
+        assert {p for p, _, _ in after} == {'surfaces', 'influence'}, (name, after)
+        assert any(k0 > k1 for _, k0, k1 in after) and any(k0 < k1 for _, k0, k1 in after), (name, after)
+    assert {o[1]['want_T'] for o, c, _ in run if o[0] == 'cond_surfaces' and c == 0} == {True, False}
+    assert {(o[1]['F'], o[1]['D']) for o, c, _ in run if o[0] == 'fit' and c == 0} == set(lt.FIT_SHAPES)
+    assert {o[1].get('bad', 'F') for o, c, _ in run if o[0] == 'fit' and c == INVALID} == set(lt.FIT_BAD)
     # 10. scan_write on a small M, on a larger M in another slot, a plain scan of the first
     i = _find(run, 0, ok('scan_write'))
     j = _find(run, i + 1, ok('scan_write'))
@@ -219,6 +257,30 @@ def test_every_group_before_every_other_and_compared(scripts):
     assert {n for n, good in used if not good} >= set(lt.GROUP_OF) - cannot_refuse
 
 
+def test_both_homes_of_the_fit_sums_are_reached(scripts):
+    """On w4 (221 sample sizes) F = 7 and F = 10 keep the prologue sums in the workspace in device memory; every other model and
+    F = 1 keep them in LDS."""
+    homes = collections.Counter()
+    for k, ops in scripts.items():
+        for o, c, s in _run(ops):
+            if o[0] == 'fit' and c == 0:
+                homes[(k == 'hand', lt.fit_in_lds(lt.world(s['model']), o[1]['F']))] += 1
+    print('successful fit ops by (hand-written script, sums in LDS):', dict(homes))
+    assert all(homes[(h, l)] >= 1 for h in (True, False) for l in (True, False)), homes
+    w4 = lt.world('w4')
+    assert [lt.fit_in_lds(w4, F) for F, _ in lt.FIT_SHAPES] == [True, False, False] and len(w4.model.sizes) == 221
+    assert all(lt.fit_in_lds(lt.world(m), F) for m in lt.MODEL_SPECS if m != 'w4' for F, _ in lt.FIT_SHAPES)
+    assert all(F * D <= 256 for F, D in lt.FIT_SHAPES)
+    # the lists: one entry without a grid point, every fourth without a conditioning site, one without a conditioning grid point
+    for kind in lt.LISTS:
+        t = lt.index_list(kind, 613)
+        lins = lt.fit_lins(kind, 36)
+        ct, cl = lt.cond_lists(t, 613, 36)
+        assert len(lins) == len(ct) == len(cl) == kind and lins.max() < 36 and cl.max() < 36 and ct.max() < 613 and ct.min() >= -1
+        assert (lins < 0).sum() == (kind >= 3) and (cl < 0).sum() == (kind >= 3) and (ct < 0).sum() == kind // 4
+        assert np.array_equal(ct[ct >= 0], ((t.astype(np.int64) + 3) % 613)[ct >= 0])
+
+
 G3 = op('set_model', model='g3x3')
 SITES, TESTS, SCAN = op('set_sites', chrom='S'), op('set_tests', stride=5, windows='all'), op('scan')
 READY = [G3, SITES, TESTS]
@@ -261,6 +323,16 @@ HEADER_ROWS = [
     (READY, op('surfaces', kind=3, bad=True), INVALID),                   # "an index outside [0, M) ... is BMX_E_INVALID"
     ([G3], op('influence', kind=1, block=0), INVALID),                    # "block < 1 ... is BMX_E_INVALID and nothing is read"
     ([G3], op('influence', kind=1, block=5), STATE),
+    ([G3, SITES], op('fit', kind=1, F=7, D=6), STATE),                    # "BMX_E_STATE without model, sites and test sites"
+    (READY, op('fit', kind=3, F=7, D=6), 0),                              # no scan is needed
+    (SCANNED, op('fit', kind=3, F=1, D=1), 0),
+    ([G3], op('fit', kind=1, F=0, D=6), INVALID),                         # "F < 1 ... BMX_E_INVALID": the call's own argument comes first
+    (READY, op('fit', kind=3, F=7, D=6, bad='lin'), INVALID),             # "lin >= nA * nx * nab"
+    (READY, op('fit', kind=3, F=7, D=6, bad='gw'), INVALID),              # "a gw outside [0, 1]"
+    ([G3], op('fit', kind=3, F=7, D=6, bad='gw'), STATE),                 # ... which is looked at after the state
+    ([G3, SITES], op('cond_surfaces', kind=1, want_T=True), STATE),       # "BMX_E_STATE without model, sites and test sites"
+    (READY, op('cond_surfaces', kind=3, want_T=False), 0),
+    (READY, op('cond_surfaces', kind=3, want_T=True, bad=True), INVALID),                   # "a cond_test outside [-1, M)"
     (READY, op('resample_sites', src=0, key=1, block=1), INVALID),        # "src_slot == the selected slot"
     (READY + [op('select_slot', slot=1)], op('resample_sites', src=2, key=1, block=1), STATE),      # "a source without sites"
     (READY + [op('select_slot', slot=1)], op('resample_sites', src=0, key=1, block=0), INVALID),
