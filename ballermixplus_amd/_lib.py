@@ -86,6 +86,9 @@ PROTOTYPES = {
     'bmx_ctx_fit_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_cond_surfaces': (C.c_int, [_vp, C.c_int64, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _ip]),
     'bmx_ctx_cond_surfaces_ms': (C.c_int, [_vp, _dp]),
+    'bmx_ctx_sandwich': (C.c_int, [_vp, C.c_int64, _ip, _dp, _dp, _dp, C.c_int64, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _ip, _ip, _ip]),
+    'bmx_ctx_sandwich_ms': (C.c_int, [_vp, _dp]),
+    'bmx_ctx_refine_R': (C.c_int, [_vp, C.c_double, C.c_double, _dp]),
     'bmx_ctx_permute_rows': (C.c_int, [_vp, C.c_uint64, C.c_int64]),
     'bmx_ctx_restore_rows': (C.c_int, [_vp]),
     'bmx_ctx_null_begin': (C.c_int, [_vp]),

@@ -61,6 +61,13 @@ Additions (do not change any reference command line):
                     of the unconditional maximum it retains, and the same for the parent given the apex; with --condSurfaces
                     <out>.conditional.surfaces.txt (the conditional surfaces, in --surfaces' format).  One locus, not refitted;
                     sites are linked: `retained` describes, it is no test.
+  --sandwich [--sandwichBlock B] [--sandwichMin C] [--sandwichMax N] [--sandwichStep hx,hv]     how well are x, alpha_beta and A
+                    determined (ballermixplus_amd/sandwich.py)?  The sandwich (Godambe) variance H^-1 J H^-1 of selected windows of
+                    the observed scan (selected as --surfaces selects) at each window's fitted point -- the refined point with
+                    --refine, else the grid argmax: H from the per-site scores, J from their sums over blocks of B consecutive
+                    sites (default 1).  Writes <out>.sandwich.txt next to each output file: standard errors of x, ln alpha_beta
+                    and ln A with and without the linkage correction, the scale lambda by which linkage inflates the CLR, and
+                    CLR / lambda.  The point is not re-optimised and the null is on the boundary: CLR_adj describes, it is no test.
   --locate R [--locateSeed S] [--locateBlock B] [--locateSpan H] [--locateLevel L] [--locateMin C] [--locateReps]     with
                     --peaks: a block-bootstrap interval for the POSITION of every apex (ballermixplus_amd/locate.py): R replicates
                     resample the sites in blocks of B consecutive sites on the device, repeat the grid scan at the test positions
@@ -272,6 +279,23 @@ def build_parser():
     parser.add_argument('--condSurfaces', dest='condSurfaces', action='store_true', default=False,
                         help='MI355X build only, with --conditional: also write the conditional surface of every apex that has a '
                              'parent to <out>.conditional.surfaces.txt, in the format of --surfaces')
+    parser.add_argument('--sandwich', dest='sandwich', action='store_true', default=False,
+                        help='MI355X build only: sandwich (Godambe) standard errors of selected windows of the observed scan.  At each '
+                             'window\'s fitted point (the refined point with --refine, else the grid argmax) H is the sum of the outer '
+                             'products of the per-site scores and J that of their sums over blocks of --sandwichBlock consecutive '
+                             'sites; <out>.sandwich.txt next to each output file gives the standard errors of x, ln alpha_beta and '
+                             'ln A from H^-1 J H^-1 and from H^-1 alone, lambda = tr(H^-1 J) / p and CLR / lambda.  Needs --peaks G '
+                             '(the apexes) or --sandwichMin C.  The point is not re-optimised: the numbers describe, they are no test')
+    parser.add_argument('--sandwichBlock', dest='sandwichBlock', type=int, default=None,
+                        help='MI355X build only, with --sandwich: sites per block of the score sums, consecutive in the input '
+                             '(default 1: J equals H)')
+    parser.add_argument('--sandwichMin', dest='sandwichMin', type=float, default=None,
+                        help='MI355X build only, with --sandwich: only windows with CLR >= this value (default 0)')
+    parser.add_argument('--sandwichMax', dest='sandwichMax', type=int, default=None,
+                        help='MI355X build only, with --sandwich: at most N windows per file, the N with the highest CLR (default 1000)')
+    parser.add_argument('--sandwichStep', dest='sandwichStep', type=str, default=None,
+                        help='MI355X build only, with --sandwich: hx,hv, the steps of the central differences of the selection table '
+                             'in x and in ln alpha_beta (default 0.001,0.01); a second pass at twice the steps gives fd_rel')
     parser.add_argument('--locate', dest='locate', type=int, default=0,
                         help='MI355X build only, with --peaks: R >= 2 bootstrap replicates of the grid scan around every apex.  Each '
                              'replicate gives every block of --locateBlock consecutive sites a Poisson(1) weight, scans the '
@@ -550,6 +574,37 @@ def write_conditional(opt, ctx, sel, outfile, ts, called, say):
     say(f'\n{datetime.now()}. Conditional: {n} apex/es, {with_parent} with a parent -> {conditional.output_name(outfile)}')
 
 
+def sandwich_refusal(opt):
+    """--sandwich / --sandwichBlock / --sandwichMin / --sandwichMax / --sandwichStep."""
+    if not opt.sandwich:
+        return orphan(opt, '--sandwich', ('sandwichBlock', 'sandwichMin', 'sandwichMax', 'sandwichStep'))
+    from . import sandwich
+    return (sandwich.value_refusal(opt.sandwichBlock, opt.sandwichMin, opt.sandwichMax, opt.sandwichStep)
+            or when(opt.peaks is None and opt.sandwichMin is None,
+                    '--sandwich needs --peaks G (the standard errors of the apexes) or --sandwichMin C (of the windows with CLR >= C): '
+                    'the variance of every window of a chromosome is never what is meant.')
+            or helper_mode(opt, '--sandwich')
+            or no_output(opt, '--sandwich', 'sandwich file is')
+            or multi_rank('--sandwich'))
+
+
+def write_sandwich(opt, ctx, sel, outfile, ts, called, say):
+    """<outfile>.sandwich.txt of one file whose observed scan (its peak call: `called`, or None without --peaks; with --refine its
+    refinement) has just run on ctx's selected slot."""
+    from . import sandwich
+    B = given(opt.sandwichBlock, 1)
+    hx, hv = sandwich.parse_step(opt.sandwichStep) if opt.sandwichStep is not None else (sandwich.HX, sandwich.HV)
+    try:
+        n, dropped = sandwich.sandwich_and_write(ctx, outfile, ts, sel, B, given(opt.sandwichMin, 0.0), given(opt.sandwichMax, sandwich.MAX_WINDOWS),
+                                                 hx, hv, called[0]['row'] if called is not None else None, bool(opt.refine))
+    except ValueError as e:
+        print(e)
+        sys.exit(1)
+    say(f'\n{datetime.now()}. Sandwich: {n} window/s, blocks of {B} site/s -> {sandwich.output_name(outfile)}')
+    if dropped:
+        say(f'--sandwichMax: {dropped} more window/s qualified and were dropped (the {n} with the highest CLR are kept).')
+
+
 def peaks_refusal(opt):
     """--peaks / --peakMin / --peakExtent / --atPeaks.  Asked before the refusals of the features that do not need the peaks,
     so that a command line with --peaks is refused in this feature's name."""
@@ -714,6 +769,9 @@ def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
     if opt.refine:
         write_refined(opt, ctx, outfile, ts, f)
         stamp('file %d: refine' % (f + 1))
+    if opt.sandwich:
+        write_sandwich(opt, ctx, sel, outfile, ts, called, say)
+        stamp('file %d: sandwich' % (f + 1))
     if opt.locate:
         write_locate(opt, ctx, outfile, ts, called, say, f)
         stamp('file %d: locate' % (f + 1))
@@ -783,7 +841,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = power_refusal(opt) or locate_refusal(opt) or conditional_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt)
+    refused = power_refusal(opt) or locate_refusal(opt) or conditional_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt) or sandwich_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)

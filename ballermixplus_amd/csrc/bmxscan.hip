@@ -15,6 +15,8 @@
 //       fit_kernel                 <- observed against expected spectrum by distance of listed windows (bmx_ctx_fit)
 //       cond_surfaces_kernel       <- the surfaces of listed windows given one fitted neighbouring locus each
 //                                     (bmx_ctx_cond_surfaces), with influence_argmax_kernel for their maxima
+//       sandwich_kernel            <- score sums, outer-product H and block-sum J of listed windows at given points
+//                                     (bmx_ctx_sandwich); refine_R_kernel <- one off-grid table column (bmx_ctx_refine_R)
 //
 // The shipped library reads ONE environment variable, BMX_TRACE (stage messages on stderr, no effect on results).
 // Tuning knobs for A/B runs (BMX_LDS_PAD, BMX_DENSE_GAP, BMX_SOLO_GAP, BMX_FORCE_J, BMX_FAR_EPS, BMX_MOM_SLOTS, BMX_SPB,
@@ -4268,6 +4270,200 @@ __global__ void boot_init_kernel(const double *clr, const int32_t *rounds, int64
     if (t < M) flag[t] = (rounds[t] >= 0 && clr[t] >= min_clr) ? 1 : 0;
 }
 
+// ----------------------------------------------------------------------------- sandwich (Godambe) pieces of listed windows
+// bmx_ctx_sandwich (the definition is ballermixplus_amd/sandwich.py).  Window q of the list is test site tests[q] at the
+// caller's point (A, x, alpha_beta)[q]; the host has laid out the five (x, alpha_beta) of the table columns -- the point,
+// x - hx, x + hx, alpha_beta / rv, alpha_beta * rv -- so the kernel forms no shifted point itself.  One workgroup of
+// REFINE_THREADS per window, grid-striding over the list; the workspace is the compass kernels' (REFINE_TABS columns x rows, row
+// list, row map; LDS or slab).  Per window:
+//   1. wave 0: window_range at the point's A;
+//   2. the rows the range references are marked and compacted in order (own text: compass_round's stays as it is);
+//   3. the five columns of those rows by refine_R, ONE inlined call site in the strided loop;
+//   4. the block pass over the blocks i / B that meet [a, b).  B < SANDWICH_WAVE_BLOCK: thread tid takes the blocks
+//      b0 + tid + REFINE_THREADS k and walks each one's sites in order, adding s s^T to its H partials and, at the block's end,
+//      S_b S_b^T to its J partials.  Otherwise wave w takes the blocks b0 + w + REFINE_WAVES k, its lanes stride over the block's
+//      sites, and a fixed-order xor butterfly forms S_b in every lane; lane 0 adds S_b S_b^T.  Both add the products through
+//      sandwich_outer, so with B = 1 (S_b = s) J is H bit for bit;
+//   5. the per-thread partials (T, g[3], H[6], J[6], three counts) are reduced by an xor butterfly in each wave and the four
+//      waves as (0 + 1) + (2 + 3).
+// No atomics; every order is fixed by the window's range, B and the thread layout: a window's numbers depend on that window,
+// its point, B and the steps alone.
+constexpr int64_t SANDWICH_WAVE_BLOCK = 64;       // blocks of at least this many sites go to a wave each
+constexpr int SANDWICH_VALS = 16;                 // T, g[3], H[6], J[6]
+
+struct SandwichParams {
+    RefineParams P;                       // the model, sites, windows and workspace as refine_kernel has them
+    const int32_t *tests;                 // [n] the listed windows of this launch
+    const double *pA, *px, *pab;          // [n] the points
+    const double *pxm, *pxp, *pabm, *pabp;// [n] x - hx, x + hx, alpha_beta / rv, alpha_beta * rv
+    int64_t n, B;
+    double den_x, den_v;                  // 2 hx and 2 hv: the central differences' denominators
+    double *T, *g, *H, *J;                // [n], [n][3], [n][6], [n][6]
+    int32_t *ns, *nsk, *nb;               // [n] each
+};
+
+// M += v v^T for v = (a, b, c), in the order (uu, ux, uv, xx, xv, vv): the one expression of H's and J's products
+__device__ __forceinline__ void sandwich_outer(double *M, double a, double b, double c) {
+    M[0] = fma(a, a, M[0]); M[1] = fma(a, b, M[1]); M[2] = fma(a, c, M[2]);
+    M[3] = fma(b, b, M[3]); M[4] = fma(b, c, M[4]); M[5] = fma(c, c, M[5]);
+}
+
+// Site i of the window: its score s into (su, sx, sv) and log1p(alpha R) into lt.  0: not one of the window's sites; 1: used;
+// 2: skipped (D not > 0 or a score not finite)
+__device__ __forceinline__ int sandwich_site(const RefineParams &P, const double *tab, int64_t i, double tg, double A, double den_x,
+                                             double den_v, double &su, double &sx, double &sv, double &lt) {
+    const double gi = P.sites.genpos[i];
+    const double z = A * fabs(gi - tg);
+    if (!(z <= P.win.zcut) || gi == tg) return 0;
+    const int r = P.sites.row[i];
+    const size_t rows = (size_t)P.rows;
+    const double alpha = exp(-z);
+    const double R0 = tab[r];
+    const double Rx = (tab[2 * rows + r] - tab[rows + r]) / den_x;
+    const double Rv = (tab[4 * rows + r] - tab[3 * rows + r]) / den_v;
+    const double aR = alpha * R0;
+    const double D = 1.0 + aR;
+    su = -z * aR / D; sx = alpha * Rx / D; sv = alpha * Rv / D;
+    lt = log1p(aR);
+    return (D > 0.0 && isfinite(su) && isfinite(sx) && isfinite(sv)) ? 1 : 2;
+}
+
+__global__ __launch_bounds__(REFINE_THREADS) void sandwich_kernel(SandwichParams Q) {
+    extern __shared__ __attribute__((aligned(16))) double lds_ws[];
+    __shared__ int64_t s_range[2];
+    __shared__ double s_px[REFINE_TABS], s_pab[REFINE_TABS];
+    __shared__ int s_wtot[REFINE_WAVES];
+    __shared__ int s_nused;
+    __shared__ double s_red[REFINE_WAVES][SANDWICH_VALS];
+    __shared__ int s_redn[REFINE_WAVES][3];
+    const RefineParams &P = Q.P;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    const CompassWs ws = compass_ws(P, lds_ws);
+    const int64_t B = Q.B;
+    const double den_x = Q.den_x, den_v = Q.den_v;
+    for (int64_t q = blockIdx.x; q < Q.n; q += gridDim.x) {
+        const int64_t t = Q.tests[q];
+        const double A = Q.pA[q], tg = P.win.test_gen[t];
+        // ---- 1. the site range [a, b) of the point's A; the five (x, alpha_beta) of the columns
+        if (wave == 0) {
+            const SiteRange R = window_range(P.sites, P.win, t, tg, A);
+            if (lane == 0) { s_range[0] = R.a; s_range[1] = R.b; }
+        }
+        if (tid == 0) {
+            s_px[0] = Q.px[q]; s_px[1] = Q.pxm[q]; s_px[2] = Q.pxp[q]; s_px[3] = Q.px[q]; s_px[4] = Q.px[q];
+            s_pab[0] = Q.pab[q]; s_pab[1] = Q.pab[q]; s_pab[2] = Q.pab[q]; s_pab[3] = Q.pabm[q]; s_pab[4] = Q.pabp[q];
+        }
+        for (int r = tid; r < P.rows; r += REFINE_THREADS) ws.map[r] = 0;
+        __syncthreads();
+        const int64_t a = s_range[0], b = s_range[1];
+        // ---- 2. the rows of the range, marked (plain stores of 1) and compacted in ascending order
+        for (int64_t i = a + tid; i < b; i += REFINE_THREADS) ws.map[P.sites.row[i]] = 1;
+        __syncthreads();
+        int base = 0;
+        for (int r0 = 0; r0 < P.rows; r0 += REFINE_THREADS) {
+            const int r = r0 + tid;
+            const bool on = r < P.rows && ws.map[r];
+            const unsigned long long m = __ballot(on);
+            if (lane == 0) s_wtot[wave] = __popcll(m);
+            __syncthreads();
+            int off = base;
+            for (int w = 0; w < wave; ++w) off += s_wtot[w];
+            if (on) ws.list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+            for (int w = 0; w < REFINE_WAVES; ++w) base += s_wtot[w];
+            __syncthreads();
+        }
+        if (tid == 0) s_nused = base;
+        __syncthreads();
+        // ---- 3. the five columns of those rows
+        {
+            const int nu = s_nused;
+            for (int it = tid; it < REFINE_TABS * nu; it += REFINE_THREADS) {
+                const int k = it / nu, r = ws.list[it % nu];
+                ws.tab[(size_t)k * P.rows + r] = refine_R(P, r, s_px[k], s_pab[k]);
+            }
+        }
+        __syncthreads();
+        // ---- 4. the block pass: acc = T / 2, g[3], H[6], J[6]; cnt = the window's sites, the skipped ones, the blocks with a used site
+        double acc[SANDWICH_VALS];
+        int cnt[3] = {0, 0, 0};
+        for (int e = 0; e < SANDWICH_VALS; ++e) acc[e] = 0.0;
+        if (a < b) {
+            const int64_t b0 = a / B, b1 = (b - 1) / B;
+            if (B < SANDWICH_WAVE_BLOCK) {
+                for (int64_t blk = b0 + tid; blk <= b1; blk += REFINE_THREADS) {
+                    const int64_t lo = max(a, blk * B), hi = min(b, (blk + 1) * B);
+                    double Su = 0.0, Sx = 0.0, Sv = 0.0;
+                    int used = 0;
+                    for (int64_t i = lo; i < hi; ++i) {
+                        double su, sx, sv, lt;
+                        const int kind = sandwich_site(P, ws.tab, i, tg, A, den_x, den_v, su, sx, sv, lt);
+                        if (kind == 0) continue;
+                        cnt[0]++;
+                        if (kind == 2) { cnt[1]++; continue; }
+                        acc[0] += lt; acc[1] += su; acc[2] += sx; acc[3] += sv;
+                        sandwich_outer(acc + 4, su, sx, sv);
+                        Su += su; Sx += sx; Sv += sv;
+                        used++;
+                    }
+                    if (used) { sandwich_outer(acc + 10, Su, Sx, Sv); cnt[2]++; }
+                }
+            } else {
+                for (int64_t blk = b0 + wave; blk <= b1; blk += REFINE_WAVES) {
+                    const int64_t lo = max(a, blk * B), hi = min(b, (blk + 1) * B);
+                    double Su = 0.0, Sx = 0.0, Sv = 0.0;
+                    int used = 0;
+                    for (int64_t i = lo + lane; i < hi; i += WAVE) {
+                        double su, sx, sv, lt;
+                        const int kind = sandwich_site(P, ws.tab, i, tg, A, den_x, den_v, su, sx, sv, lt);
+                        if (kind == 0) continue;
+                        cnt[0]++;
+                        if (kind == 2) { cnt[1]++; continue; }
+                        acc[0] += lt; acc[1] += su; acc[2] += sx; acc[3] += sv;
+                        sandwich_outer(acc + 4, su, sx, sv);
+                        Su += su; Sx += sx; Sv += sv;
+                        used++;
+                    }
+                    for (int off = 1; off < WAVE; off <<= 1) {
+                        Su += __shfl_xor(Su, off); Sx += __shfl_xor(Sx, off); Sv += __shfl_xor(Sv, off);
+                        used += __shfl_xor(used, off);
+                    }
+                    if (lane == 0 && used) { sandwich_outer(acc + 10, Su, Sx, Sv); cnt[2]++; }
+                }
+            }
+        }
+        // ---- 5. fixed-order reduction across the workgroup
+        for (int off = 1; off < WAVE; off <<= 1) {
+            for (int e = 0; e < SANDWICH_VALS; ++e) acc[e] += __shfl_xor(acc[e], off);
+            for (int k = 0; k < 3; ++k) cnt[k] += __shfl_xor(cnt[k], off);
+        }
+        if (lane == 0) {
+            for (int e = 0; e < SANDWICH_VALS; ++e) s_red[wave][e] = acc[e];
+            for (int k = 0; k < 3; ++k) s_redn[wave][k] = cnt[k];
+        }
+        __syncthreads();
+        if (tid < SANDWICH_VALS) {
+            const double v = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
+            const int nsites = (s_redn[0][0] + s_redn[1][0]) + (s_redn[2][0] + s_redn[3][0]);
+            const int nskip = (s_redn[0][1] + s_redn[1][1]) + (s_redn[2][1] + s_redn[3][1]);
+            if (tid == 0) Q.T[q] = nsites > nskip ? 2.0 * v : -INFINITY;
+            else if (tid < 4) Q.g[q * 3 + (tid - 1)] = v;
+            else if (tid < 10) Q.H[q * 6 + (tid - 4)] = v;
+            else Q.J[q * 6 + (tid - 10)] = v;
+        } else if (tid == SANDWICH_VALS) {
+            Q.ns[q] = (s_redn[0][0] + s_redn[1][0]) + (s_redn[2][0] + s_redn[3][0]);
+            Q.nsk[q] = (s_redn[0][1] + s_redn[1][1]) + (s_redn[2][1] + s_redn[3][1]);
+            Q.nb[q] = (s_redn[0][2] + s_redn[1][2]) + (s_redn[2][2] + s_redn[3][2]);
+        }
+        __syncthreads();
+    }
+}
+
+// bmx_ctx_refine_R: the off-grid column of every table row at one (x, alpha_beta), one thread per row
+__global__ __launch_bounds__(REFINE_THREADS) void refine_R_kernel(RefineParams P, double x, double ab, double *out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < P.rows) out[r] = refine_R(P, r, x, ab);
+}
+
 // ----------------------------------------------------------------------------- resampled sites, position bootstrap
 // bmx_ctx_resample_sites / bmx_ctx_locate_* (the definition is ballermixplus_amd/locate.py).  An integer-weighted composite
 // likelihood is the plain one of the site array in which site i stands w_i times: the scan kernels run unchanged on the array
@@ -5510,6 +5706,11 @@ struct bmx_ctx {
     DevBuf<int32_t> cs_ctest, cs_clin, cs_nsh, cs_lin;
     DevBuf<double> cs_tmax;
     DevTimer cs;
+    // sandwich pieces (bmx_ctx_sandwich): the list, the points with the four shifted arguments of their columns, one chunk's
+    // sums and counts, the events around a chunk's kernel; the column of bmx_ctx_refine_R
+    DevBuf<int32_t> sw_list, sw_cnt;
+    DevBuf<double> sw_pts, sw_out, sw_R;
+    DevTimer sw;
     DevBuf<int64_t> gap_sample;
     // profile likelihoods (bmx_ctx_set_profiles): the BMX_PL_* set of later scans, and the keys of one launch range
     int pl_which = 0;
@@ -5860,6 +6061,8 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->ft.release();
     c->cs_ctest.release(); c->cs_clin.release(); c->cs_nsh.release(); c->cs_lin.release(); c->cs_tmax.release();
     c->cs.release();
+    c->sw_list.release(); c->sw_cnt.release(); c->sw_pts.release(); c->sw_out.release(); c->sw_R.release();
+    c->sw.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
     c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
     c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
@@ -7536,6 +7739,120 @@ int bmx_ctx_fetch_boot(bmx_ctx *c, int32_t *window, double *A, double *x, double
     HIP_TRY(download(window, s->bt_win.p, n));
     HIP_TRY(download(A, s->bt_A.p, nt)); HIP_TRY(download(x, s->bt_x.p, nt)); HIP_TRY(download(abeta, s->bt_ab.p, nt));
     HIP_TRY(download(T, s->bt_T.p, nt)); HIP_TRY(download(T_centre, s->bt_Tc.p, nt)); HIP_TRY(download(rounds, s->bt_rounds.p, nt));
+    return BMX_OK;
+}
+
+/* ---- sandwich (Godambe) pieces of listed windows (ballermixplus_amd/sandwich.py holds the definition) ---- */
+
+int bmx_ctx_sandwich(bmx_ctx *c, int64_t n, const int32_t *tests, const double *A, const double *x, const double *abeta, int64_t block,
+                     double hx, double hv, double *T_out, double *g_out, double *H_out, double *J_out, int32_t *nsites_out,
+                     int32_t *nskipped_out, int32_t *nblocks_out) {
+    int rc;
+    const bool steps_ok = std::isfinite(hx) && hx > 0.0 && std::isfinite(hv) && hv > 0.0;
+    const char *own = block < 1 ? "block < 1" : steps_ok ? nullptr : "the steps hx and hv must be finite and > 0";
+    if ((rc = list_ready(c, "sandwich", n, own, !tests || !A || !x || !abeta))) return rc;
+    if (n > BMX_SANDWICH_MAX_WINDOWS) return fail(BMX_E_LIMIT, "sandwich: more than BMX_SANDWICH_MAX_WINDOWS windows in one call");
+    if (n == 0) { c->sw.ms = 0.0; return BMX_OK; }
+    ChromSlot *s = c->cur;
+    const double rv = std::exp(hv);                 // the C library's exp, once: the four shifted points are the host's
+    // the five (x, alpha_beta) of entry q's columns, as every pass below forms them
+    auto shifted = [&](int64_t q, double &xm, double &xp, double &am, double &ap) {
+        xm = x[q] - hx; xp = x[q] + hx; am = abeta[q] / rv; ap = abeta[q] * rv;
+    };
+    for (int64_t q = 0; q < n; q++) {               // the whole list is judged before anything is launched or written
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "sandwich: test site index out of range at entry " + std::to_string(q));
+        if (!(A[q] > 0.0) || !std::isfinite(A[q]) || !(abeta[q] > 0.0) || !std::isfinite(abeta[q]))
+            return fail(BMX_E_INVALID, "sandwich: A and alpha_beta must be finite and > 0 at entry " + std::to_string(q));
+        double xm, xp, am, ap;
+        shifted(q, xm, xp, am, ap);
+        if (!(xm > 0.0) || !(xp < 1.0))
+            return fail(BMX_E_INVALID, "sandwich: 0 < x - hx and x + hx < 1 are needed at entry " + std::to_string(q));
+        if (!(am > 0.0) || !std::isfinite(ap))
+            return fail(BMX_E_INVALID, "sandwich: alpha_beta / exp(hv) and alpha_beta * exp(hv) must be finite and > 0 at entry " + std::to_string(q));
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    SandwichParams Q;
+    if ((rc = refine_setup(c, s, Q.P, 0))) return rc;
+    // chunks of at most BMX_SANDWICH_CHUNK_WINDOWS windows: list, points and outputs of one chunk on the host and on the device
+    const int64_t step = std::min<int64_t>(BMX_SANDWICH_CHUNK_WINDOWS, n);
+    std::vector<double> pts;                        // [7][step]: A, x, abeta, x - hx, x + hx, abeta / rv, abeta * rv
+    try {
+        pts.resize((size_t)7 * step);
+    } catch (const std::bad_alloc &) {
+        return fail(BMX_E_LIMIT, "sandwich: no host memory for one chunk's points");
+    }
+    HIP_TRY(c->sw_out.ensure((size_t)step * SANDWICH_VALS));
+    HIP_TRY(c->sw_cnt.ensure((size_t)step * 3));
+    HIP_TRY(c->sw_list.ensure((size_t)step));
+    HIP_TRY(c->sw_pts.ensure((size_t)step * 7));
+    Q.B = std::min(block, std::max<int64_t>(s->N, 1));           // i / B is 0 for every site either way
+    Q.den_x = 2.0 * hx; Q.den_v = 2.0 * hv;
+    Q.T = c->sw_out.p; Q.g = Q.T + step; Q.H = Q.g + 3 * step; Q.J = Q.H + 6 * step;
+    Q.ns = c->sw_cnt.p; Q.nsk = Q.ns + step; Q.nb = Q.nsk + step;
+    Q.tests = c->sw_list.p;
+    const double *d = c->sw_pts.p;
+    Q.pA = d; Q.px = d + step; Q.pab = d + 2 * step; Q.pxm = d + 3 * step; Q.pxp = d + 4 * step; Q.pabm = d + 5 * step; Q.pabp = d + 6 * step;
+    const double ms_before = c->sw.ms;
+    double total = 0.0;
+    auto run = [&]() -> int {
+        const hipMemcpyKind D2H = hipMemcpyDeviceToHost, H2D = hipMemcpyHostToDevice;
+        for (int64_t q0 = 0; q0 < n; q0 += step) {
+            const int64_t m = std::min(step, n - q0);
+            for (int64_t q = 0; q < m; q++) {
+                double xm, xp, am, ap;
+                shifted(q0 + q, xm, xp, am, ap);
+                const double row[7] = {A[q0 + q], x[q0 + q], abeta[q0 + q], xm, xp, am, ap};
+                for (int k = 0; k < 7; k++) pts[(size_t)k * step + q] = row[k];
+            }
+            HIP_TRY(hipMemcpyAsync(c->sw_list.p, tests + q0, (size_t)m * sizeof(int32_t), H2D, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->sw_pts.p, pts.data(), pts.size() * sizeof(double), H2D, c->stream));
+            Q.n = m;
+            HIP_TRY(c->sw.begin(c->stream));
+            int lrc = launch_ws(c, sandwich_kernel, Q, Q.P, m);
+            if (lrc) return lrc;
+            HIP_TRY(c->sw.end(c->stream));
+            // each chunk goes back before the next is launched (and before its points are overwritten on the host)
+            if (T_out) HIP_TRY(hipMemcpyAsync(T_out + q0, Q.T, (size_t)m * sizeof(double), D2H, c->stream));
+            if (g_out) HIP_TRY(hipMemcpyAsync(g_out + q0 * 3, Q.g, (size_t)m * 3 * sizeof(double), D2H, c->stream));
+            if (H_out) HIP_TRY(hipMemcpyAsync(H_out + q0 * 6, Q.H, (size_t)m * 6 * sizeof(double), D2H, c->stream));
+            if (J_out) HIP_TRY(hipMemcpyAsync(J_out + q0 * 6, Q.J, (size_t)m * 6 * sizeof(double), D2H, c->stream));
+            if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out + q0, Q.ns, (size_t)m * sizeof(int32_t), D2H, c->stream));
+            if (nskipped_out) HIP_TRY(hipMemcpyAsync(nskipped_out + q0, Q.nsk, (size_t)m * sizeof(int32_t), D2H, c->stream));
+            if (nblocks_out) HIP_TRY(hipMemcpyAsync(nblocks_out + q0, Q.nb, (size_t)m * sizeof(int32_t), D2H, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(c->sw.read());
+            total += c->sw.ms;
+        }
+        return BMX_OK;
+    };
+    rc = run();
+    c->sw.ms = rc ? ms_before : total;      // the call's figure: its chunks' kernels; a failed call leaves the last good one
+    return rc;
+}
+
+int bmx_ctx_sandwich_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    return c->sw.get(ms, "no sandwich call yet");
+}
+
+int bmx_ctx_refine_R(bmx_ctx *c, double x, double abeta, double *R_out) {
+    if (!c || !R_out) return fail(BMX_E_INVALID, "NULL argument");
+    ChromSlot *s = c->cur;
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before refine_R");
+    if (!(x > 0.0 && x < 1.0) || !(abeta > 0.0) || !std::isfinite(abeta))
+        return fail(BMX_E_INVALID, "refine_R: 0 < x < 1 and alpha_beta > 0 (finite) are needed");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    RefineParams P;
+    int rc = refine_setup(c, s, P, 0);
+    if (rc) return rc;
+    HIP_TRY(c->sw_R.ensure((size_t)c->rows));
+    hipLaunchKernelGGL(refine_R_kernel, dim3((unsigned)((c->rows + REFINE_THREADS - 1) / REFINE_THREADS)), dim3(REFINE_THREADS), 0, c->stream, P, x, abeta,
+                       c->sw_R.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(R_out, c->sw_R.p, (size_t)c->rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BMX_OK;
 }
 

@@ -560,6 +560,36 @@ class Context:
         """Device milliseconds of the kernels of the context's last cond_surfaces() call."""
         return self._ms(self._L.bmx_ctx_cond_surfaces_ms)
 
+    def sandwich(self, tests, A, x, abeta, block=1, hx=None, hv=None):
+        """The pieces of the sandwich variance (ballermixplus_amd/sandwich.py) of the listed windows of the selected slot, window
+        q at the point (A[q], x[q], abeta[q]) (scalars broadcast over the list), blocks of `block` consecutive sites, steps
+        hx, hv of the table's central differences (default: sandwich.HX, sandwich.HV).  Returns a dict: T f64[n], g f64[n, 3],
+        H f64[n, 6] and J f64[n, 6] (uu, ux, uv, xx, xv, vv of (ln A, x, ln alpha_beta)), nsites, nskipped, nblocks i32[n]."""
+        from . import sandwich
+        t = _lib.i32(tests)
+        if t.ndim != 1:
+            raise ValueError('a flat list of test site indices is needed')
+        n = len(t)
+        pA, px, pab = (_lib.f64(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))) for v in (A, x, abeta))
+        out = {'T': np.empty(n, dtype=np.float64), 'g': np.empty((n, 3), dtype=np.float64), 'H': np.empty((n, 6), dtype=np.float64),
+               'J': np.empty((n, 6), dtype=np.float64)}
+        out.update({k: np.empty(n, dtype=np.int32) for k in ('nsites', 'nskipped', 'nblocks')})
+        _lib.check(self._L.bmx_ctx_sandwich(self._h, n, _lib.as_ip(t), _lib.as_dp(pA), _lib.as_dp(px), _lib.as_dp(pab), int(block),
+                                            float(sandwich.HX if hx is None else hx), float(sandwich.HV if hv is None else hv),
+                                            _lib.as_dp(out['T']), _lib.as_dp(out['g']), _lib.as_dp(out['H']), _lib.as_dp(out['J']),
+                                            _lib.as_ip(out['nsites']), _lib.as_ip(out['nskipped']), _lib.as_ip(out['nblocks'])))
+        return out
+
+    def sandwich_ms(self):
+        """Device milliseconds of the kernels of the context's last sandwich() call."""
+        return self._ms(self._L.bmx_ctx_sandwich_ms)
+
+    def refine_R(self, x, abeta):
+        """R f64[table rows] at the off-grid point (x, abeta): the refinement's own arithmetic for every row of the model."""
+        R = np.empty(self.model.rows, dtype=np.float64)
+        _lib.check(self._L.bmx_ctx_refine_R(self._h, float(x), float(abeta), _lib.as_dp(R)))
+        return R
+
     def fetch_lut(self):
         m = self.model
         shape = (len(m.x), len(m.abeta), m.rows)

@@ -287,6 +287,49 @@ int bmx_ctx_cond_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, const int
                           int32_t *nshared_out /* [n][nA], may be NULL */, double *tmax_out /* [n], may be NULL */,
                           int32_t *lin_out /* [n], may be NULL */);
 int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms);
+/* The pieces of the sandwich (Godambe) variance H^-1 J H^-1 of n listed windows on the selected slot, each at a point the caller
+ * gives; the definition is ballermixplus_amd/sandwich.py.  Window q: test site tests[q] (tg, win_lo, win_hi) at (A[q], x[q],
+ * abeta[q]).  Its sites are the surfaces' sites at that A: z_i = A * |g_i - tg| <= bmx_alpha_cut(), g_i != tg.  Coordinates
+ * (u, x, v) = (ln A, x, ln alpha_beta).  With alpha_i = exp(-z_i), R(row | x, abeta) the off-grid table entry bmx_ctx_refine_R
+ * returns, rv = exp(hv) (the host's exp, once per call),
+ *     R_i = R(row_i | x, abeta),  Rx_i = (R(row_i | x + hx, abeta) - R(row_i | x - hx, abeta)) / (2 hx),
+ *     Rv_i = (R(row_i | x, abeta * rv) - R(row_i | x, abeta / rv)) / (2 hv),  D_i = 1 + alpha_i R_i,
+ *     s_i = (-z_i alpha_i R_i / D_i, alpha_i Rx_i / D_i, alpha_i Rv_i / D_i).
+ * A site whose D_i is not > 0 or whose s_i is not finite is SKIPPED: counted in nsites and nskipped, it enters no sum.
+ *   T_out[n]        2 * sum log1p(alpha_i R_i) over the used sites; -inf without one
+ *   g_out[n][3]     sum s_i
+ *   H_out[n][6]     sum s_i s_i^T, as (uu, ux, uv, xx, xv, vv)
+ *   J_out[n][6]     sum over the blocks b = i / block (the site index in the slot's array) of S_b S_b^T, S_b = the sum of s_i over
+ *                   the block's used sites in this window; the same six entries
+ *   nsites_out[n]   the window's sites at A (the surfaces' count), nskipped_out[n] the skipped among them,
+ *   nblocks_out[n]  the blocks with a used site
+ * Every output may be NULL.  An empty window: T = -inf, the counts 0, g, H and J all 0.0.
+ * sandwich_kernel: one workgroup of 256 per window, the workspace of the refinement's kernels (five table columns of the rows the
+ * window references, in LDS or in a slab), blocks of fewer than 64 sites one thread each, larger ones one wave each; no atomics,
+ * every sum in a fixed order: a window's 16 doubles depend on that window, its point, block, hx and hv alone (bitwise the same
+ * alone, in a list, twice, in any order), and with block = 1 J is H bit for bit.  At most BMX_SANDWICH_CHUNK_WINDOWS windows per
+ * launch: the list is judged as a whole first, then each chunk's points are formed and uploaded, its kernel runs and its outputs
+ * are copied back before the next chunk, so host and device hold one chunk's arrays whatever n is.
+ * BMX_E_INVALID and nothing is written: a NULL context, n < 0, block < 1, hx or hv not finite and > 0, a NULL tests / A / x /
+ * abeta with n > 0, an index outside [0, M), an A or abeta not finite and > 0, x - hx <= 0 or x + hx >= 1, abeta / rv or
+ * abeta * rv not finite and > 0.  BMX_E_STATE without model, sites and test sites (n < 0, block and the steps are refused before
+ * the state is looked at); BMX_E_LIMIT for n > BMX_SANDWICH_MAX_WINDOWS.  n == 0 succeeds.  Blocks.  Needs no scan; leaves
+ * sites, test sites, scan results, records, profiles, refinement, support, bootstrap, peak, null, influence, fit and locate
+ * state of every slot untouched.  bmx_ctx_sandwich_ms (milliseconds the last call spent in its kernels) before a successful
+ * call is BMX_E_STATE.
+ * bmx_ctx_refine_R: R_out[rows] = R(row | x, abeta) of every table row of the model, the refinement's off-grid arithmetic
+ * (refine_R; NaN for a row without a neutral probability), one thread per row.  bmx_ctx_eval_points' argument rules: a NULL
+ * argument, x outside (0, 1) or abeta not finite and > 0 is BMX_E_INVALID, without model, sites and test sites BMX_E_STATE.
+ * Blocks.
+ * Added without a bump of BMX_ABI_VERSION_MINOR, as the groups above: look the symbols up to find out. */
+#define BMX_SANDWICH_MAX_WINDOWS (1LL << 24)
+#define BMX_SANDWICH_CHUNK_WINDOWS (1LL << 18)
+int bmx_ctx_sandwich(bmx_ctx *c, int64_t n, const int32_t *tests, const double *A, const double *x, const double *abeta,
+                     int64_t block, double hx, double hv, double *T_out /* [n] */, double *g_out /* [n][3] */,
+                     double *H_out /* [n][6] */, double *J_out /* [n][6] */, int32_t *nsites_out /* [n] */,
+                     int32_t *nskipped_out /* [n] */, int32_t *nblocks_out /* [n] */);
+int bmx_ctx_sandwich_ms(bmx_ctx *c, double *ms);
+int bmx_ctx_refine_R(bmx_ctx *c, double x, double abeta, double *R_out /* [rows] */);
 /* Choose the scan kernel variant (0 = default). For A/B measurements only. */
 int bmx_ctx_set_variant(bmx_ctx *c, int variant);
 /* Select (creating it on first use) chromosome slot `slot`, 0 <= slot < 4096. */
