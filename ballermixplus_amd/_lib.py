@@ -86,6 +86,11 @@ PROTOTYPES = {
     'bmx_ctx_fit_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_cond_surfaces': (C.c_int, [_vp, C.c_int64, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _ip]),
     'bmx_ctx_cond_surfaces_ms': (C.c_int, [_vp, _dp]),
+    'bmx_ctx_baseline_reset': (C.c_int, [_vp]),
+    'bmx_ctx_baseline_add': (C.c_int, [_vp, C.c_int32, C.c_int32, _lp, _lp, _ip]),
+    'bmx_ctx_baseline_fetch': (C.c_int, [_vp, _dp, _ip]),
+    'bmx_ctx_base_surfaces': (C.c_int, [_vp, C.c_int64, _ip, _dp, _ip, _ip, _dp, _ip]),
+    'bmx_ctx_base_surfaces_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_sandwich': (C.c_int, [_vp, C.c_int64, _ip, _dp, _dp, _dp, C.c_int64, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _ip, _ip, _ip]),
     'bmx_ctx_sandwich_ms': (C.c_int, [_vp, _dp]),
     'bmx_ctx_refine_R': (C.c_int, [_vp, C.c_double, C.c_double, _dp]),

@@ -61,6 +61,15 @@ Additions (do not change any reference command line):
                     of the unconditional maximum it retains, and the same for the parent given the apex; with --condSurfaces
                     <out>.conditional.surfaces.txt (the conditional surfaces, in --surfaces' format).  One locus, not refitted;
                     sites are linked: `retained` describes, it is no test.
+  --stepwise [--stepMin C] [--stepMax K] [--stepSurfaces]     with --peaks: which of the apexes are separate loci
+                    (ballermixplus_amd/stepwise.py)?  Forward stepwise selection: the highest apex is accepted at its grid argmax,
+                    every other apex is computed again given ALL accepted loci, the best of what is left is accepted, until
+                    nothing reaches C (default: --peakMin's value, else 0) or K loci (default 1000) are in.  Writes
+                    <out>.stepwise.txt next to each output file: per apex its order of entry, the conditional maximum (at entry
+                    for an accepted apex, given all accepted loci for the others) and where it sits, the share of the
+                    unconditional maximum it retains and the running log ratio T_total of the accepted loci against neutrality;
+                    with --stepSurfaces <out>.stepwise.surfaces.txt (each accepted apex's surface at entry, in --surfaces'
+                    format).  Greedy, loci held at grid points and never refitted; sites are linked: C is a threshold, not a test.
   --sandwich [--sandwichBlock B] [--sandwichMin C] [--sandwichMax N] [--sandwichStep hx,hv]     how well are x, alpha_beta and A
                     determined (ballermixplus_amd/sandwich.py)?  The sandwich (Godambe) variance H^-1 J H^-1 of selected windows of
                     the observed scan (selected as --surfaces selects) at each window's fitted point -- the refined point with
@@ -279,6 +288,21 @@ def build_parser():
     parser.add_argument('--condSurfaces', dest='condSurfaces', action='store_true', default=False,
                         help='MI355X build only, with --conditional: also write the conditional surface of every apex that has a '
                              'parent to <out>.conditional.surfaces.txt, in the format of --surfaces')
+    parser.add_argument('--stepwise', dest='stepwise', action='store_true', default=False,
+                        help='MI355X build only, with --peaks: forward stepwise conditional selection of the apexes of the observed '
+                             'scan.  The highest apex is accepted at its grid argmax, every other apex is computed again given all '
+                             'accepted loci, the best of what is left is accepted, until nothing reaches --stepMin or --stepMax loci '
+                             'are in.  <out>.stepwise.txt next to each output file gives per apex its order of entry, the '
+                             'conditional maximum, the share of the unconditional maximum it retains and the running log ratio of '
+                             'the accepted loci against neutrality.  Greedy; loci are never refitted; the threshold is no test')
+    parser.add_argument('--stepMin', dest='stepMin', type=float, default=None,
+                        help='MI355X build only, with --stepwise: an apex enters only with a conditional maximum >= this value '
+                             '(default: the value of --peakMin, else 0; --nullPerm\'s genome-wide threshold is the natural choice)')
+    parser.add_argument('--stepMax', dest='stepMax', type=int, default=None,
+                        help='MI355X build only, with --stepwise: at most this many loci are accepted per file (default 1000)')
+    parser.add_argument('--stepSurfaces', dest='stepSurfaces', action='store_true', default=False,
+                        help='MI355X build only, with --stepwise: also write every accepted apex\'s surface at entry to '
+                             '<out>.stepwise.surfaces.txt, in the format of --surfaces')
     parser.add_argument('--sandwich', dest='sandwich', action='store_true', default=False,
                         help='MI355X build only: sandwich (Godambe) standard errors of selected windows of the observed scan.  At each '
                              'window\'s fitted point (the refined point with --refine, else the grid argmax) H is the sum of the outer '
@@ -574,6 +598,30 @@ def write_conditional(opt, ctx, sel, outfile, ts, called, say):
     say(f'\n{datetime.now()}. Conditional: {n} apex/es, {with_parent} with a parent -> {conditional.output_name(outfile)}')
 
 
+def stepwise_refusal(opt):
+    """--stepwise / --stepMin / --stepMax / --stepSurfaces."""
+    if not opt.stepwise:
+        return orphan(opt, '--stepwise', ('stepMin', 'stepMax', 'stepSurfaces'))
+    from . import stepwise
+    return (stepwise.value_refusal(opt.stepMin, opt.stepMax)
+            or when(opt.peaks is None, '--stepwise needs --peaks G: it selects among the apexes of the peak call.')
+            or helper_mode(opt, '--stepwise')
+            or no_output(opt, '--stepwise', 'stepwise file is')
+            or multi_rank('--stepwise'))
+
+
+def write_stepwise(opt, ctx, sel, outfile, ts, data, called, say):
+    """<outfile>.stepwise.txt (with --stepSurfaces <outfile>.stepwise.surfaces.txt) of one file whose observed scan and peak call
+    (`called`) have just run on ctx's selected slot.  Returns the rows written (for the genome-wide table)."""
+    from . import stepwise
+    C = given(opt.stepMin, given(opt.peakMin, 0.0))
+    rows, accepted, total = stepwise.stepwise_and_write(ctx, outfile, ts, sel, data.genPos, called[0]['row'], C,
+                                                        given(opt.stepMax, stepwise.MAX_LOCI), opt.stepSurfaces)
+    say(f'\n{datetime.now()}. Stepwise: {len(rows)} apex/es, {accepted} accepted (threshold {float(C)!r}), T_total {total!r} -> '
+        f'{stepwise.output_name(outfile)}')
+    return rows
+
+
 def sandwich_refusal(opt):
     """--sandwich / --sandwichBlock / --sandwichMin / --sandwichMax / --sandwichStep."""
     if not opt.sandwich:
@@ -738,8 +786,9 @@ def null_of_file(opt, ctx, ts, f):
 
 # One file's results that wait for all files: called = call_peaks()'s pair (None without --peaks), null = null_of_file()'s
 # tuple (None without --nullPerm), waiting = (data, neut, sel) when the file's power step waits for the genome-wide null;
+# stepwise: the rows of the file's stepwise table (None without --stepwise);
 # ts: the test sites, kept only with --nullPerm (for the p-value file and the waiting power step) -- a whole genome's are large.
-FileRecord = namedtuple('FileRecord', 'outfile ts called null waiting')
+FileRecord = namedtuple('FileRecord', 'outfile ts called null waiting stepwise')
 
 
 def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
@@ -766,6 +815,10 @@ def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
     if opt.conditional:
         write_conditional(opt, ctx, sel, outfile, ts, called, say)
         stamp('file %d: conditional' % (f + 1))
+    step_rows = None
+    if opt.stepwise:
+        step_rows = write_stepwise(opt, ctx, sel, outfile, ts, data, called, say)
+        stamp('file %d: stepwise' % (f + 1))
     if opt.refine:
         write_refined(opt, ctx, outfile, ts, f)
         stamp('file %d: refine' % (f + 1))
@@ -787,7 +840,7 @@ def file_stages(opt, ctx, sel, outfile, ts, data, neut, f, planted, say, stamp):
     elif opt.power:
         write_power(opt, ctx, sel, outfile, ts, data.genPos, planted, None, say, f)
         stamp('file %d: power' % (f + 1))
-    return FileRecord(outfile, ts if opt.nullPerm else None, called, null, waiting)
+    return FileRecord(outfile, ts if opt.nullPerm else None, called, null, waiting, step_rows)
 
 
 def wrap_up(opt, ctx, records, planted, say, stamp, inputs=None):
@@ -826,6 +879,9 @@ def wrap_up(opt, ctx, records, planted, say, stamp, inputs=None):
             where = null_name(opt.outfile, 'peaks')
             peaks.write_genome(where, [(os.path.basename(i), t) for i, t in zip(inputs, tables)])
         say(f'\n{datetime.now()}. Peaks: {sum(len(t) for t in tables)} (separation {opt.peaks!r}) -> {where}')
+    if opt.stepwise and inputs is not None:
+        from . import stepwise
+        stepwise.write_genome(null_name(opt.outfile, 'stepwise'), [(os.path.basename(i), rec.stepwise) for i, rec in zip(inputs, records)])
 
 
 def main(argv=None):
@@ -841,7 +897,7 @@ def main(argv=None):
     opt = parser.parse_args(argv)
     if opt.infile is None and opt.inputs is None:
         parser.error('the following arguments are required: -i/--input')
-    refused = power_refusal(opt) or locate_refusal(opt) or conditional_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt) or sandwich_refusal(opt)
+    refused = power_refusal(opt) or locate_refusal(opt) or conditional_refusal(opt) or stepwise_refusal(opt) or peaks_refusal(opt) or surfaces_refusal(opt) or null_refusal(opt) or profiles_refusal(opt) or boot_refusal(opt) or refine_refusal(opt) or support_refusal(opt) or influence_refusal(opt) or fit_refusal(opt) or sandwich_refusal(opt)
     if refused:
         print(refused)
         sys.exit(1)

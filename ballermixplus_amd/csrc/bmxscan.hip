@@ -15,7 +15,9 @@
 //       fit_kernel                 <- observed against expected spectrum by distance of listed windows (bmx_ctx_fit)
 //       cond_surfaces_kernel       <- the surfaces of listed windows given one fitted neighbouring locus each
 //                                     (bmx_ctx_cond_surfaces), with influence_argmax_kernel for their maxima
-//       sandwich_kernel            <- score sums, outer-product H and block-sum J of listed windows at given points
+//       baseline_add_kernel, base_surfaces_kernel    <- a per-site baseline of any number of accepted loci, and the
+//                                     surfaces of listed windows against it (bmx_ctx_baseline_*, bmx_ctx_base_surfaces)
+//       sandwich_kernel           <- score sums, outer-product H and block-sum J of listed windows at given points
 //                                     (bmx_ctx_sandwich); refine_R_kernel <- one off-grid table column (bmx_ctx_refine_R)
 //
 // The shipped library reads ONE environment variable, BMX_TRACE (stage messages on stderr, no effect on results).
@@ -5069,6 +5071,114 @@ __global__ __launch_bounds__(SURFS_THREADS) void cond_surfaces_kernel(CondParams
     if (slice == 0 && tid == 0) { S.ns[(size_t)q * S.nA + iA] = ns; S.nsh[(size_t)q * S.nA + iA] = nsh; }
 }
 
+// ------------------------------------------------- a per-site baseline of accepted loci, and surfaces of listed windows against it
+// bmx_ctx_baseline_* and bmx_ctx_base_surfaces (the definition is ballermixplus_amd/stepwise.py).  The slot keeps d[N] and cnt[N]:
+// under the accepted loci site i follows g (1 + d_i), and cnt_i of them reach it.
+//   baseline_add_kernel: the locus is test site t held at (A, column p of the table).  Wave 0 of every workgroup finds the locus'
+//   site range with window_range (a few dozen probes), then the workgroups stride over the range in tiles of SURFS_THREADS sites,
+//   one thread per site: tile_site's predicate, d_i <- d_i + exp(-z) (R[row_i][p] - d_i) -- from d_i = 0.0 that is exp(-z) R bit
+//   for bit, cond_surfaces_kernel's d -- and cnt_i + 1.  A site is written by one thread of one workgroup: plain loads and stores.
+//   Workgroup 0 also writes out[0..2] = the first and last written site and how many were written, from the range as
+//   influence_range_kernel derives its o[2], o[3]: inside [a, b) every site passes the cut, and the sites [ctr, e) at the locus' own
+//   position are the only ones left out (first > last: none).
+//   base_surfaces_kernel: cond_surfaces_kernel with d_i and `shared` (cnt_i > 0) read from the slot's arrays: no exp, no gather on
+//   the conditioning side.  The same u = alpha / (1.0 + d), the same log1p(u (R - d)) in the same order, so after ONE
+//   baseline_add a window is bitwise cond_surfaces_kernel's pair (window | that locus), and against the empty baseline
+//   surfaces_kernel's window.  No atomics: a window's numbers depend on that window and the baseline alone.
+constexpr int BASE_ADD_GRID_MAX = 1024;       // workgroups of a baseline_add launch (they stride over the range)
+
+struct BaseAddParams {
+    SiteView sites; WindowView win;
+    const double *Rt; int NP;
+    int64_t t; double A; int p;                      // the locus: its test site, and the grid point it is held at
+    double *d; int32_t *cnt;                         // [N]
+    int64_t *out;                                    // [3]: first, last, number written
+};
+
+__global__ __launch_bounds__(SURFS_THREADS) void baseline_add_kernel(BaseAddParams S) {
+    __shared__ int64_t s_range[2];
+    const int tid = threadIdx.x;
+    const double A = S.A, tc = S.win.test_gen[S.t];
+    if (tid < WAVE) {
+        const SiteRange R = window_range(S.sites, S.win, S.t, tc, A);
+        if (blockIdx.x == 0) {                       // (workgroup-uniform)
+            const int64_t e = wave_first_true(R.ctr, R.b, [&](int64_t i) { return S.sites.genpos[i] > tc; });
+            if (tid == 0) {
+                S.out[0] = R.a < R.ctr ? R.a : e;
+                S.out[1] = e < R.b ? R.b - 1 : R.ctr - 1;
+                S.out[2] = (R.b - R.a) - (e - R.ctr);
+            }
+        }
+        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
+    }
+    __syncthreads();
+    const int64_t rlo = s_range[0], rhi = s_range[1];
+    for (int64_t base = rlo + (int64_t)blockIdx.x * SURFS_THREADS; base <= rhi; base += (int64_t)gridDim.x * SURFS_THREADS) {
+        const int64_t i = base + tid;
+        double z;
+        if (tile_site(S.sites.genpos, i, rhi, tc, A, S.win.zcut, z)) {
+            const double d = S.d[i];
+            S.d[i] = d + exp(-z) * (S.Rt[(size_t)S.sites.row[i] * S.NP + S.p] - d);
+            S.cnt[i] = S.cnt[i] + 1;
+        }
+    }
+}
+
+struct BaseParams {
+    SiteView sites; WindowView win;
+    const double *Rt; int NP, npairs, nslices;      // nslices: slices of SURFS_THREADS pairs
+    const double *A; int nA;
+    const int32_t *tests;                            // the listed test sites of this launch
+    const double *d; const int32_t *cnt;             // the slot's baseline: [N]
+    double *T;        // [n][nA][npairs]
+    int32_t *ns;      // [n][nA]
+    int32_t *nsh;     // [n][nA]: the sites among ns that an accepted locus reaches
+};
+
+__global__ __launch_bounds__(SURFS_THREADS) void base_surfaces_kernel(BaseParams S) {
+    __shared__ double s_u[SURFS_THREADS];
+    __shared__ double s_d[SURFS_THREADS];
+    __shared__ int s_row[SURFS_THREADS];
+    __shared__ int64_t s_range[2];
+    const int tid = threadIdx.x;
+    const int slice = blockIdx.x % S.nslices;
+    const int iA = (blockIdx.x / S.nslices) % S.nA;
+    const int64_t q = blockIdx.x / S.nslices / S.nA;
+    const int p = slice * SURFS_THREADS + tid;
+    const bool live = p < S.npairs;
+    const int64_t t = S.tests[q];
+    const double A = S.A[iA], tg = S.win.test_gen[t];
+    if (tid < WAVE) {
+        const SiteRange R = window_range(S.sites, S.win, t, tg, A);
+        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
+    }
+    __syncthreads();
+    const int64_t rlo = s_range[0], rhi = s_range[1];
+    double sum = 0.0, z;
+    int ns = 0, nsh = 0;
+    for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
+        const int64_t i = base + tid;
+        const bool in = tile_site(S.sites.genpos, i, rhi, tg, A, S.win.zcut, z);
+        tile_store(S.sites.row, i, in, z, s_u, s_row);               // alpha for now
+        const double d = in ? S.d[i] : 0.0;
+        const bool shared = in && S.cnt[i] > 0;
+        s_d[tid] = d;
+        s_u[tid] = s_u[tid] / (1.0 + d);
+        ns += __syncthreads_count(in);
+        nsh += __syncthreads_count(shared);
+        if (live) {
+            const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
+            for (int s = 0; s < cnt; ++s) {
+                const int r_s = s_row[s];
+                if (r_s >= 0) sum += log1p(s_u[s] * (S.Rt[(size_t)r_s * S.NP + p] - s_d[s]));
+            }
+        }
+        __syncthreads();
+    }
+    if (live) S.T[((size_t)q * S.nA + iA) * S.npairs + p] = ns ? 2.0 * sum : NAN;
+    if (slice == 0 && tid == 0) { S.ns[(size_t)q * S.nA + iA] = ns; S.nsh[(size_t)q * S.nA + iA] = nsh; }
+}
+
 // ----------------------------------------------------------- delete-block jackknife of a list of test sites' grid maxima
 // bmx_ctx_influence (the definition is ballermixplus_amd/influence.py).  Per chunk of listed windows four launches on the
 // context's stream: surfaces_kernel gives T and ns, influence_range_kernel every (window, A)'s site range,
@@ -5602,6 +5712,12 @@ struct ChromSlot {
     DevBuf<int32_t> lc_lo, lc_hi, lc_row;
     DevBuf<double> lc_clr;
 
+    // the baseline of accepted loci (bmx_ctx_baseline_*): per site d and the number of loci that reach it.  It belongs to the
+    // sites: set_sites, resample_sites and plant_sites drop it.
+    bool bl_have = false;
+    DevBuf<double> bl_d;
+    DevBuf<int32_t> bl_cnt;
+
     // the row indices: 16-bit unless the table has more than 65535 rows (wide_rows); orig: the given rows while they are permuted
     RowArray row_array() const { return RowArray{wide_rows ? nullptr : row16.p, wide_rows ? row32.p : nullptr}; }
     void *row_ptr() const { return wide_rows ? (void *)row32.p : (void *)row16.p; }
@@ -5645,6 +5761,8 @@ struct ChromSlot {
         release_peaks();
         lc_ok = false;
         lc_lo.release(); lc_hi.release(); lc_row.release(); lc_clr.release();
+        bl_have = false;
+        bl_d.release(); bl_cnt.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         ev0 = ev1 = nullptr;
@@ -5706,6 +5824,12 @@ struct bmx_ctx {
     DevBuf<int32_t> cs_ctest, cs_clin, cs_nsh, cs_lin;
     DevBuf<double> cs_tmax;
     DevTimer cs;
+    // surfaces against a slot's baseline (bmx_ctx_base_surfaces): one chunk's shared counts, maxima and argmaxes (the list, T and
+    // nsites in the surfaces' buffers), the events around a chunk's kernels; baseline_add's three numbers
+    DevBuf<int32_t> bs_nsh, bs_lin;
+    DevBuf<double> bs_tmax;
+    DevBuf<int64_t> bs_out;
+    DevTimer bs;
     // sandwich pieces (bmx_ctx_sandwich): the list, the points with the four shifted arguments of their columns, one chunk's
     // sums and counts, the events around a chunk's kernel; the column of bmx_ctx_refine_R
     DevBuf<int32_t> sw_list, sw_cnt;
@@ -5773,7 +5897,8 @@ void drop_tests(ChromSlot *s) {
 void drop_sites(ChromSlot *s) {
     s->has_sites = false;
     s->has_orig = false;    // new rows: nothing is permuted
-    drop_tests(s);          // test sites were located in the old site array
+    s->bl_have = false;     // ... and the baseline of accepted loci was formed from the old ones
+    drop_tests(s);        // test sites were located in the old site array
 }
 
 template <class T>
@@ -6061,6 +6186,8 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->ft.release();
     c->cs_ctest.release(); c->cs_clin.release(); c->cs_nsh.release(); c->cs_lin.release(); c->cs_tmax.release();
     c->cs.release();
+    c->bs_nsh.release(); c->bs_lin.release(); c->bs_tmax.release(); c->bs_out.release();
+    c->bs.release();
     c->sw_list.release(); c->sw_cnt.release(); c->sw_pts.release(); c->sw_out.release(); c->sw_R.release();
     c->sw.release();
     c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
@@ -7384,6 +7511,114 @@ int bmx_ctx_cond_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, const int
 int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
     return c->cs.get(ms, "no cond_surfaces call yet");
+}
+
+int bmx_ctx_baseline_reset(bmx_ctx *c) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_sites) return fail(BMX_E_STATE, "sites must be set before baseline_reset");
+    HIP_TRY(hipSetDevice(c->device));
+    s->bl_have = false;
+    HIP_TRY(s->bl_d.ensure((size_t)s->N));
+    HIP_TRY(s->bl_cnt.ensure((size_t)s->N));
+    HIP_TRY(hipMemsetAsync(s->bl_d.p, 0, (size_t)s->N * sizeof(double), c->stream));          // (all bits 0: 0.0)
+    HIP_TRY(hipMemsetAsync(s->bl_cnt.p, 0, (size_t)s->N * sizeof(int32_t), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    s->bl_have = true;
+    return BMX_OK;
+}
+
+int bmx_ctx_baseline_add(bmx_ctx *c, int32_t test, int32_t lin, int64_t *first, int64_t *last, int32_t *n_written) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->ready_to_scan(c)) return fail(BMX_E_STATE, "model, sites and tests must be set before baseline_add");
+    if (!s->bl_have) return fail(BMX_E_STATE, "baseline_add: no baseline (bmx_ctx_baseline_reset) on this slot's sites");
+    if (test < 0 || test >= s->M) return fail(BMX_E_INVALID, "baseline_add: test site index out of range");
+    if (lin < 0 || (int64_t)lin >= (int64_t)c->nA * c->npairs) return fail(BMX_E_INVALID, "baseline_add: grid index out of range");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->bs_out.ensure(3));
+    BaseAddParams P;
+    P.sites = site_view(s); P.win = window_view(c, s);
+    P.Rt = c->d_Rt; P.NP = c->NP;
+    P.t = test; P.A = c->h_A[(size_t)(lin / c->npairs)]; P.p = lin % c->npairs;
+    P.d = s->bl_d.p; P.cnt = s->bl_cnt.p; P.out = c->bs_out.p;
+    const int64_t grid = std::min<int64_t>(std::max<int64_t>((s->N + SURFS_THREADS - 1) / SURFS_THREADS, 1), BASE_ADD_GRID_MAX);
+    hipLaunchKernelGGL(baseline_add_kernel, dim3((unsigned)grid), dim3(SURFS_THREADS), 0, c->stream, P);
+    HIP_TRY(hipGetLastError());
+    int64_t out[3] = {0, -1, 0};
+    HIP_TRY(hipMemcpyAsync(out, c->bs_out.p, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first) *first = out[0];
+    if (last) *last = out[1];
+    if (n_written) *n_written = (int32_t)out[2];
+    return BMX_OK;
+}
+
+int bmx_ctx_baseline_fetch(bmx_ctx *c, double *d_out, int32_t *cnt_out) {
+    if (!c) return fail(BMX_E_INVALID, "ctx is NULL");
+    ChromSlot *s = c->cur;
+    if (!s->has_sites || !s->bl_have) return fail(BMX_E_STATE, "baseline_fetch: no baseline (bmx_ctx_baseline_reset) on this slot's sites");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(download(d_out, (const double *)s->bl_d.p, (size_t)s->N));
+    HIP_TRY(download(cnt_out, (const int32_t *)s->bl_cnt.p, (size_t)s->N));
+    return BMX_OK;
+}
+
+int bmx_ctx_base_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out, int32_t *nsites_out, int32_t *nshared_out,
+                          double *tmax_out, int32_t *lin_out) {
+    int rc;
+    if ((rc = list_ready(c, "base_surfaces", n, nullptr, !tests))) return rc;
+    ChromSlot *s = c->cur;
+    if (!s->bl_have) return fail(BMX_E_STATE, "base_surfaces: no baseline (bmx_ctx_baseline_reset) on this slot's sites");
+    if (n == 0) { c->bs.ms = 0.0; return BMX_OK; }
+    for (int64_t q = 0; q < n; q++)
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "base_surfaces: test site index out of range at entry " + std::to_string(q));
+    HIP_TRY(hipSetDevice(c->device));
+    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
+    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one window's surface
+    const int64_t step = surfaces_step(c, nsl);                // the windows per chunk, as bmx_ctx_cond_surfaces takes them
+    const size_t first = (size_t)std::min<int64_t>(step, n);
+    HIP_TRY(c->sfs_T.ensure(first * per));
+    HIP_TRY(c->sfs_ns.ensure(first * c->nA));
+    HIP_TRY(c->bs_nsh.ensure(first * c->nA));
+    HIP_TRY(c->bs_tmax.ensure(first));
+    HIP_TRY(c->bs_lin.ensure(first));
+    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
+    BaseParams S;
+    S.sites = site_view(s); S.win = window_view(c, s);
+    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    S.d = s->bl_d.p; S.cnt = s->bl_cnt.p;
+    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p; S.nsh = c->bs_nsh.p;
+    double total = 0.0;
+    for (int64_t q0 = 0; q0 < n; q0 += step) {
+        const int64_t m = std::min(step, n - q0);
+        S.tests = c->sfs_list.p + q0;
+        HIP_TRY(c->bs.begin(c->stream));
+        hipLaunchKernelGGL(base_surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
+        if (tmax_out || lin_out)
+            hipLaunchKernelGGL(influence_argmax_kernel, dim3((unsigned)m), dim3(INFL_THREADS), 0, c->stream, (const double *)c->sfs_T.p,
+                               (int64_t)per, c->bs_tmax.p, c->bs_lin.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(c->bs.end(c->stream));
+        // each chunk goes back before the next is launched, as in bmx_ctx_cond_surfaces; without T_out the surfaces stay on the device
+        const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+        if (T_out) HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), D2H, c->stream));
+        if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
+        if (nshared_out) HIP_TRY(hipMemcpyAsync(nshared_out + (size_t)q0 * c->nA, c->bs_nsh.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
+        if (tmax_out) HIP_TRY(hipMemcpyAsync(tmax_out + q0, c->bs_tmax.p, (size_t)m * sizeof(double), D2H, c->stream));
+        if (lin_out) HIP_TRY(hipMemcpyAsync(lin_out + q0, c->bs_lin.p, (size_t)m * sizeof(int32_t), D2H, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(c->bs.read());
+        total += c->bs.ms;
+    }
+    c->bs.ms = total;        // the call's figure: its chunks' kernels
+    return BMX_OK;
+}
+
+int bmx_ctx_base_surfaces_ms(bmx_ctx *c, double *ms) {
+    if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
+    return c->bs.get(ms, "no base_surfaces call yet");
 }
 
 }  // extern "C"

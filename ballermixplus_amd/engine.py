@@ -560,6 +560,48 @@ class Context:
         """Device milliseconds of the kernels of the context's last cond_surfaces() call."""
         return self._ms(self._L.bmx_ctx_cond_surfaces_ms)
 
+    def baseline_reset(self):
+        """Allocate or zero the selected slot's baseline of accepted loci (ballermixplus_amd/stepwise.py): d = 0.0 and cnt = 0 for
+        every site.  set_sites, resample_sites and plant_sites drop it."""
+        _lib.check(self._L.bmx_ctx_baseline_reset(self._h))
+
+    def baseline_add(self, test, lin):
+        """Add the locus `test site test held at the grid point lin = (iA * nx + ix) * nab + ia` to the selected slot's
+        baseline.  Returns (first, last, n_written): the first and last site index written and how many were (first > last and
+        0 for a locus without a site)."""
+        first, last, n = C.c_int64(), C.c_int64(), C.c_int32()
+        _lib.check(self._L.bmx_ctx_baseline_add(self._h, int(test), int(lin), C.byref(first), C.byref(last), C.byref(n)))
+        return first.value, last.value, n.value
+
+    def baseline_fetch(self, N=None):
+        """(d f64[N], cnt i32[N]) of the selected slot's baseline; N: the slot's number of sites (default: as fetch_sites)."""
+        N = int(self.N if N is None else N)
+        d, cnt = np.empty(N, dtype=np.float64), np.empty(N, dtype=np.int32)
+        _lib.check(self._L.bmx_ctx_baseline_fetch(self._h, _lib.as_dp(d), _lib.as_ip(cnt)))
+        return d, cnt
+
+    def base_surfaces(self, tests, want_T=True):
+        """The surfaces of the listed test sites of the selected slot (any order, repeats allowed) against its baseline of
+        accepted loci (ballermixplus_amd/stepwise.py).  Returns cond_surfaces' dict: T f64[n, nA, nx, nab] (None without want_T:
+        the surfaces are then not copied back), nsites i32[n, nA], nshared i32[n, nA] (the sites an accepted locus reaches),
+        tmax f64[n] and lin i32[n] (the scan's rule on each window's T; 0 and -1 when nothing is > 0)."""
+        m = self.model
+        t = _lib.i32(tests)
+        if t.ndim != 1:
+            raise ValueError('a flat list of test site indices is needed')
+        n = len(t)
+        out = {'T': np.empty((n, self.nA, len(m.x), len(m.abeta)), dtype=np.float64) if want_T else None,
+               'nsites': np.empty((n, self.nA), dtype=np.int32), 'nshared': np.empty((n, self.nA), dtype=np.int32),
+               'tmax': np.empty(n, dtype=np.float64), 'lin': np.empty(n, dtype=np.int32)}
+        _lib.check(self._L.bmx_ctx_base_surfaces(self._h, n, _lib.as_ip(t), _lib.as_dp(out['T']) if want_T else None,
+                                                 _lib.as_ip(out['nsites']), _lib.as_ip(out['nshared']), _lib.as_dp(out['tmax']),
+                                                 _lib.as_ip(out['lin'])))
+        return out
+
+    def base_surfaces_ms(self):
+        """Device milliseconds of the kernels of the context's last base_surfaces() call."""
+        return self._ms(self._L.bmx_ctx_base_surfaces_ms)
+
     def sandwich(self, tests, A, x, abeta, block=1, hx=None, hv=None):
         """The pieces of the sandwich variance (ballermixplus_amd/sandwich.py) of the listed windows of the selected slot, window
         q at the point (A[q], x[q], abeta[q]) (scalars broadcast over the list), blocks of `block` consecutive sites, steps

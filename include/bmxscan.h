@@ -287,6 +287,50 @@ int bmx_ctx_cond_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, const int
                           int32_t *nshared_out /* [n][nA], may be NULL */, double *tmax_out /* [n], may be NULL */,
                           int32_t *lin_out /* [n], may be NULL */);
 int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms);
+/* A per-site BASELINE of any number of accepted loci on the selected slot, and the surfaces of n listed windows against it: the
+ * device side of forward stepwise selection; the definition is ballermixplus_amd/stepwise.py.  The slot keeps d[N] (double) and
+ * cnt[N] (int32): under the accepted loci site i follows g (1 + d_i), and cnt_i of them reach it.
+ * bmx_ctx_baseline_reset: allocates the two arrays for the slot's N sites, or zeroes them (d = 0.0, cnt = 0).  BMX_E_INVALID: a
+ *   NULL context; BMX_E_STATE without sites.  bmx_ctx_set_sites, _resample_sites and _plant_sites on a slot (and a new model)
+ *   drop its baseline: the calls below are then BMX_E_STATE until the next reset.
+ * bmx_ctx_baseline_add: adds the locus "test site `test` held at the grid point lin = (iA_c * nx + ix_c) * nab + ia_c".  Its sites
+ *   are the surfaces' sites at A_c: max(win_lo, 0) <= i <= min(win_hi, N - 1), z_i = A_c * |g_i - tc| <= bmx_alpha_cut() (that
+ *   single product), g_i != tc.  Each of them gets
+ *       d_i <- d_i + exp(-z_i) * (R[ix_c][ia_c][row_i] - d_i)        (no FMA contraction),   cnt_i <- cnt_i + 1;
+ *   from d_i = 0.0 that is exp(-z_i) * R bit for bit: bmx_ctx_cond_surfaces' d.  *first, *last: the first and last site written,
+ *   *n_written: how many (each may be NULL); a locus without a site writes nothing and returns first > last, n_written 0.
+ *   baseline_add_kernel: one thread per site of the locus' range, plain loads and stores, no atomics.  Refusals, in this order:
+ *   BMX_E_INVALID a NULL context; BMX_E_STATE without model, sites and test sites; BMX_E_STATE without a baseline; BMX_E_INVALID
+ *   test outside [0, M); BMX_E_INVALID lin outside [0, nA * nx * nab).  A refused call writes nothing.
+ * bmx_ctx_baseline_fetch: d_out[N], cnt_out[N] (either may be NULL).  BMX_E_INVALID: a NULL context; BMX_E_STATE without a
+ *   baseline.
+ * bmx_ctx_base_surfaces: window q is test site tests[q] (tg, win_lo, win_hi); its sites at A are the surfaces' sites.  With
+ *   alpha_i = exp(-A |g_i - tg|) and u_i = alpha_i / (1.0 + d_i),
+ *       T_base(A, x, abeta) = 2 * sum_i log1p(u_i * (R_i - d_i))      over the window's sites in increasing site index,
+ *   NaN where no site qualifies at that A: bmx_ctx_cond_surfaces' expression with d read from the baseline.
+ *     T_out[n][nA][nx][nab]  (may be NULL: the surfaces are then not copied back)
+ *     nsites_out[n][nA]      the surfaces' count (may be NULL);   nshared_out[n][nA]  the sites among them with cnt_i > 0 (may be NULL)
+ *     tmax_out[n], lin_out[n]  the scan's rule on each window's T_base (may be NULL), as bmx_ctx_cond_surfaces gives them
+ *   Against the empty baseline T_base, nsites, tmax and lin are bitwise bmx_ctx_surfaces' (and its argmax) and nshared is 0; after
+ *   ONE bmx_ctx_baseline_add they are bitwise bmx_ctx_cond_surfaces' of the pairs (window | that locus), nshared included.
+ *   base_surfaces_kernel: one workgroup of 256 per (window, A, slice of 256 grid pairs), no atomics; a window's numbers depend on
+ *   that window and the baseline alone (bitwise the same alone, in a list, or twice).  Chunked as bmx_ctx_surfaces: device output
+ *   at or below BMX_SURFACES_CHUNK_BYTES, each chunk copied back before the next launch.  Refusals, in this order: BMX_E_INVALID
+ *   a NULL context; BMX_E_INVALID n < 0; BMX_E_STATE without model, sites and test sites; BMX_E_INVALID a NULL tests with n > 0;
+ *   BMX_E_STATE without a baseline; BMX_E_INVALID an index outside [0, M).  Nothing is written on refusal.  n == 0 succeeds.
+ *   bmx_ctx_base_surfaces_ms (milliseconds the last call spent in its kernels) before a successful call is BMX_E_STATE.
+ * All block.  They use the surfaces' device buffers and their own; apart from the selected slot's baseline they leave sites, test
+ * sites, scan results, records, profiles, refinement, support, bootstrap, peak, null, influence, fit, conditional, sandwich and
+ * locate state of every slot untouched.
+ * Added without a bump of BMX_ABI_VERSION_MINOR, as the groups above: look the symbols up to find out. */
+int bmx_ctx_baseline_reset(bmx_ctx *c);
+int bmx_ctx_baseline_add(bmx_ctx *c, int32_t test, int32_t lin, int64_t *first /* may be NULL */, int64_t *last /* may be NULL */,
+                         int32_t *n_written /* may be NULL */);
+int bmx_ctx_baseline_fetch(bmx_ctx *c, double *d_out /* [N], may be NULL */, int32_t *cnt_out /* [N], may be NULL */);
+int bmx_ctx_base_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out /* [n][nA][nx][nab], may be NULL */,
+                          int32_t *nsites_out /* [n][nA], may be NULL */, int32_t *nshared_out /* [n][nA], may be NULL */,
+                          double *tmax_out /* [n], may be NULL */, int32_t *lin_out /* [n], may be NULL */);
+int bmx_ctx_base_surfaces_ms(bmx_ctx *c, double *ms);
 /* The pieces of the sandwich (Godambe) variance H^-1 J H^-1 of n listed windows on the selected slot, each at a point the caller
  * gives; the definition is ballermixplus_amd/sandwich.py.  Window q: test site tests[q] (tg, win_lo, win_hi) at (A[q], x[q],
  * abeta[q]).  Its sites are the surfaces' sites at that A: z_i = A * |g_i - tg| <= bmx_alpha_cut(), g_i != tg.  Coordinates
