@@ -75,40 +75,23 @@ def value_refusal(span, min_clr):
 # ----------------------------------------------------------------------------------------------- the host restatement
 
 def host_cond_surface(genpos, rows, R, A, tg, lo, hi, tc, clo, chi, A_c, ix_c, ia_c, zcut, scale=False):
-    """The conditional surface of one pair in numpy, in the style of surfaces.host_surface.  genpos[N], rows[N], R[nx][nab][table
+    """The conditional surface of one pair in numpy: d and `shared` of the window's sites by the definition above, then
+    surfaces.host_sided_surface, the body shared with stepwise.host_base_surface.  genpos[N], rows[N], R[nx][nab][table
     rows], A: the grid in the order wanted; (tg, lo, hi): the candidate window; (tc, clo, chi): the conditioning locus' position
     and inclusive site index window, held at (A_c, ix_c, ia_c) -- tc None: no conditioning locus; zcut: bmx_alpha_cut().
     Returns (T[nA][nx][nab], NaN where no site qualifies; nsites[nA]; nshared[nA]) and with scale=True also S[nA][nx][nab] =
     2 sum_i |term_i| (0 where no site qualifies): the size of what cancels in T."""
-    g = np.asarray(genpos, dtype=np.float64)
-    rows = np.asarray(rows, dtype=np.int64)
-    R = np.asarray(R, dtype=np.float64)
-    A = np.atleast_1d(np.asarray(A, dtype=np.float64))
-    a, b = max(int(lo), 0), min(int(hi), len(g) - 1)
-    T = np.full((len(A),) + R.shape[:2], np.nan)
-    S = np.zeros(T.shape)
-    ns, nsh = np.zeros(len(A), dtype=np.int32), np.zeros(len(A), dtype=np.int32)
-    if b >= a:
-        idx = np.arange(a, b + 1, dtype=np.int64)
-        gw, rw = g[a:b + 1], rows[a:b + 1]
-        dist = np.abs(gw - tg)
+    def side(a, b, gw, rw, R):
         d, shared = np.zeros(len(gw)), np.zeros(len(gw), dtype=bool)
         if tc is not None:
+            idx = np.arange(a, b + 1, dtype=np.int64)
             zc = A_c * np.abs(gw - tc)
-            shared = (idx >= max(int(clo), 0)) & (idx <= min(int(chi), len(g) - 1)) & (zc <= zcut) & (gw != tc)
+            shared = (idx >= max(int(clo), 0)) & (idx <= min(int(chi), len(genpos) - 1)) & (zc <= zcut) & (gw != tc)
             with np.errstate(over='ignore', invalid='ignore'):
                 d[shared] = np.exp(-zc[shared]) * R[int(ix_c), int(ia_c), rw[shared]]
-        for i, Av in enumerate(A.tolist()):
-            z = Av * dist
-            keep = (z <= zcut) & (gw != tg)
-            ns[i], nsh[i] = int(keep.sum()), int((keep & shared).sum())
-            if ns[i]:
-                with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
-                    u = np.exp(-z[keep]) / (1.0 + d[keep])
-                    term = np.log1p(u * (R[:, :, rw[keep]] - d[keep]))
-                    T[i] = 2.0 * np.sum(term, axis=2)
-                    S[i] = 2.0 * np.sum(np.abs(term), axis=2)
-    return (T, ns, nsh, S) if scale else (T, ns, nsh)
+        return d, shared
+
+    return surfaces.host_sided_surface(genpos, rows, R, A, tg, lo, hi, side, zcut, scale)
 
 
 def parents(gen, clr, iA_hat, grid_A, apex_rows, zcut, span=None):

@@ -9,14 +9,14 @@
 //                                     tests), and the path for tables of 4 GiB and more
 //       locate_kernel / finalize_kernel: test-site positions, per-slice argmax merge + nSites
 //       surface_kernel             <- the full T[A,x,alpha] surface of one site (v1:449-450 wish)
-//       surfaces_kernel            <- the same surfaces for a list of test sites in one launch (bmx_ctx_surfaces)
-//       influence_kernel           <- every leave-one-block-out maximum of those surfaces (bmx_ctx_influence), with
+//       surfaces_kernel, cond_surfaces_kernel, base_surfaces_kernel    <- the same surfaces for a list of test sites in
+//                                     one launch: plain (bmx_ctx_surfaces), given one fitted neighbouring locus each
+//                                     (bmx_ctx_cond_surfaces) and against a per-site baseline of any number of accepted loci
+//                                     (bmx_ctx_base_surfaces); one body, listed_surface, with influence_argmax_kernel for the maxima
+//       baseline_add_kernel        <- adds a locus to that baseline (bmx_ctx_baseline_*)
+//       influence_kernel          <- every leave-one-block-out maximum of those surfaces (bmx_ctx_influence), with
 //                                     influence_range_kernel and influence_argmax_kernel
 //       fit_kernel                 <- observed against expected spectrum by distance of listed windows (bmx_ctx_fit)
-//       cond_surfaces_kernel       <- the surfaces of listed windows given one fitted neighbouring locus each
-//                                     (bmx_ctx_cond_surfaces), with influence_argmax_kernel for their maxima
-//       baseline_add_kernel, base_surfaces_kernel    <- a per-site baseline of any number of accepted loci, and the
-//                                     surfaces of listed windows against it (bmx_ctx_baseline_*, bmx_ctx_base_surfaces)
 //       sandwich_kernel           <- score sums, outer-product H and block-sum J of listed windows at given points
 //                                     (bmx_ctx_sandwich); refine_R_kernel <- one off-grid table column (bmx_ctx_refine_R)
 //
@@ -4935,16 +4935,33 @@ __global__ __launch_bounds__(PEAK_THREADS) void peak_extent_kernel(const double 
 }
 
 // ----------------------------------------------------------------------------- surfaces of a list of test sites
-// surface_kernel's T[iA][pair] for a LIST of test sites of the slot in one launch (bmx_ctx_surfaces; the definition and the
-// CLI's selection rule are ballermixplus_amd/surfaces.py).  One workgroup of SURFS_THREADS per (listed window q, iA, slice of
-// SURFS_THREADS pairs); thread tid owns pair p = slice * SURFS_THREADS + tid.
+// surface_kernel's T[iA][pair] for a LIST of test sites of the slot in one launch, plain (bmx_ctx_surfaces; the definition and the
+// CLI's selection rule are ballermixplus_amd/surfaces.py), given one fitted neighbouring locus per entry (bmx_ctx_cond_surfaces,
+// ballermixplus_amd/conditional.py) or against the slot's baseline of accepted loci (bmx_ctx_base_surfaces,
+// ballermixplus_amd/stepwise.py).  One body, listed_surface; the three kernels differ in their SIDE alone: where the (d, shared) of
+// a staged site comes from.  One workgroup of SURFS_THREADS per (listed entry q, iA, slice of SURFS_THREADS pairs); thread tid owns
+// pair p = slice * SURFS_THREADS + tid.
 //   1. wave 0 finds the inclusive site range of this A inside the window (window_range: a window at A = 1e8 reads a few dozen
 //      positions, not the chromosome); it goes to the workgroup through LDS.
-//   2. the range is walked in tiles of SURFS_THREADS sites: tile_site and tile_store put (alpha, row) of site base + tid into LDS, the
-//      barrier counts the `in` sites, every thread adds tile_term over them IN INCREASING SITE INDEX (same-address LDS reads, R coalesced).
-// Each pair's sum therefore runs over surface_kernel's sites in surface_kernel's order with surface_kernel's expression (the
-// sites outside the range are exactly those it skips), so T and nSites are bitwise what bmx_ctx_surface returns for the
-// window.  No atomics: a window's result is a function of that window alone.
+//   2. the range is walked in tiles of SURFS_THREADS sites: tile_site and tile_store put (alpha, row) of site base + tid into LDS.
+//      Under a side the same thread takes the site's d and whether it is SHARED from the side and stores u = alpha / (1.0 + d) over
+//      alpha and d beside it: the conditioning costs one division per site per tile.  The barriers count the `in` sites (and the
+//      shared ones); every thread then adds its term over them IN INCREASING SITE INDEX (same-address LDS reads, R coalesced):
+//      tile_term = log1p(alpha R) without a side, log1p(u (R - d)) under one -- a subtract more.
+//   The sides:
+//      NoSide (surfaces_kernel): nothing of d is compiled -- no second LDS array, no division, no shared count.
+//      PairSide (cond_surfaces_kernel): entry q's conditioning locus is test site ctest[q] held at the grid point clin[q] = iA_c *
+//        npairs + p_c (either < 0: none).  A site is shared iff it lies inside the conditioning site's clipped window, A_c |g_i - tc|
+//        <= zcut and g_i != tc; then d = exp(-zc) R[row_i][p_c] (one exp, one gather), else d = 0.0 exactly.
+//      BaselineSide (base_surfaces_kernel): d = the slot's d[i] and shared = cnt[i] > 0, two coalesced loads.
+// Bit for bit, by construction and held by the tests:
+//   - surfaces_kernel's sum runs over surface_kernel's sites in surface_kernel's order with surface_kernel's expression (the sites
+//     outside the range are exactly those it skips): T and nSites are what bmx_ctx_surface returns for the window;
+//   - with d = 0.0, u is alpha and R - 0.0 is R: a pair without a conditioning locus, or with one out of reach of every site, and a
+//     window against the empty baseline are surfaces_kernel's window;
+//   - baseline_add_kernel's first update of a site is exp(-z) R, PairSide's d: a window after ONE baseline_add is
+//     cond_surfaces_kernel's pair (window | that locus).
+// No atomics: an entry's numbers depend on that entry (and the baseline) alone.
 constexpr int SURFS_THREADS = 256;
 
 struct SurfsParams {
@@ -4954,10 +4971,54 @@ struct SurfsParams {
     const int32_t *tests;                            // the listed test sites of this launch
     double *T;        // [n][nA][npairs]
     int32_t *ns;      // [n][nA]
+    int32_t *nsh;     // [n][nA]: the shared sites among ns (written under a side only)
 };
 
-__global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) {
-    __shared__ double s_alpha[SURFS_THREADS];
+// A side: begin() is the workgroup's setup for entry q, site() gives `shared` and d of site i, staged by this thread (row in s_row)
+struct NoSide {
+    static constexpr bool sided = false;
+    struct Locus {};
+    __device__ __forceinline__ Locus begin(const SurfsParams &, int64_t) const { return {}; }
+};
+struct PairSide {
+    static constexpr bool sided = true;
+    const int32_t *ctest, *clin;                     // the conditioning loci of this launch's entries
+    struct Locus { double tc, Ac; int pc; int64_t clo, chi; };
+    __device__ __forceinline__ Locus begin(const SurfsParams &S, int64_t q) const {
+        const int32_t ct = ctest[q], cl = clin[q];
+        Locus L{0.0, 0.0, 0, 0, -1};                 // (no conditioning locus: no site is inside this window)
+        if (ct >= 0 && cl >= 0) {
+            L.tc = S.win.test_gen[ct]; L.Ac = S.A[cl / S.npairs]; L.pc = cl % S.npairs;
+            L.clo = max(S.win.win_lo[ct], (int64_t)0); L.chi = min(S.win.win_hi[ct], S.sites.N - 1);
+        }
+        return L;
+    }
+    __device__ __forceinline__ bool site(const SurfsParams &S, const Locus &L, int64_t i, bool in, const int *s_row, double &d) const {
+        bool shared = false;
+        d = 0.0;
+        if (in && i >= L.clo && i <= L.chi) {
+            const double g = S.sites.genpos[i], zc = L.Ac * fabs(g - L.tc);
+            shared = zc <= S.win.zcut && g != L.tc;
+            if (shared) d = exp(-zc) * S.Rt[(size_t)s_row[threadIdx.x] * S.NP + L.pc];
+        }
+        return shared;
+    }
+};
+struct BaselineSide {
+    static constexpr bool sided = true;
+    const double *d; const int32_t *cnt;             // the slot's baseline: [N]
+    struct Locus {};
+    __device__ __forceinline__ Locus begin(const SurfsParams &, int64_t) const { return {}; }
+    __device__ __forceinline__ bool site(const SurfsParams &, const Locus &, int64_t i, bool in, const int *, double &d_i) const {
+        d_i = in ? d[i] : 0.0;
+        return in && cnt[i] > 0;
+    }
+};
+
+template <class Side>
+__device__ __forceinline__ void listed_surface(const SurfsParams &S, const Side &side) {
+    __shared__ double s_u[SURFS_THREADS];           // alpha; under a side u = alpha / (1.0 + d)
+    __shared__ double s_d[SURFS_THREADS];           // (under a side only: never referenced without one, and then not allocated)
     __shared__ int s_row[SURFS_THREADS];
     __shared__ int64_t s_range[2];
     const int tid = threadIdx.x;
@@ -4968,6 +5029,7 @@ __global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) 
     const bool live = p < S.npairs;                 // (p may lie beyond the padded row of R: an idle thread reads nothing)
     const int64_t t = S.tests[q];
     const double A = S.A[iA], tg = S.win.test_gen[t];
+    [[maybe_unused]] const typename Side::Locus locus = side.begin(S, q);
     if (tid < WAVE) {
         const SiteRange R = window_range(S.sites, S.win, t, tg, A);
         if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
@@ -4976,104 +5038,47 @@ __global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) 
     const int64_t rlo = s_range[0], rhi = s_range[1];
     double sum = 0.0, z;
     int ns = 0;
-    for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
-        const bool in = tile_site(S.sites.genpos, base + tid, rhi, tg, A, S.win.zcut, z);
-        tile_store(S.sites.row, base + tid, in, z, s_alpha, s_row);
-        ns += __syncthreads_count(in);
-        if (live) {
-            const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
-            for (int s = 0; s < cnt; ++s) {
-                const int r_s = s_row[s];
-                if (r_s >= 0) sum += tile_term(s_alpha[s], r_s, S.Rt, S.NP, p);
-            }
-        }
-        __syncthreads();
-    }
-    if (live) S.T[((size_t)q * S.nA + iA) * S.npairs + p] = ns ? 2.0 * sum : NAN;
-    if (slice == 0 && tid == 0) S.ns[(size_t)q * S.nA + iA] = ns;
-}
-
-// ------------------------------------------------------ surfaces of listed test sites given one fitted neighbouring locus
-// bmx_ctx_cond_surfaces (the definition is ballermixplus_amd/conditional.py).  Pair q is the window of test site tests[q] and a
-// conditioning locus: test site ctest[q] held at the grid point clin[q] = iA_c * npairs + p_c (either < 0: none).
-// surfaces_kernel's decomposition, range and tiles; the thread that stages site base + tid also decides whether the site is
-// SHARED -- inside the conditioning site's clipped window, A_c |g_i - tc| <= zcut, g_i != tc -- and then gathers the one entry
-// of the conditioning column: d = exp(-zc) R[row_i][p_c], else d = 0.0 exactly.  It stores u = alpha / (1.0 + d) and d beside
-// the row, so the conditioning side costs one exp, one gather and one division per site per tile, and a pair adds
-// log1p(u (R - d)) per site: a subtract more than tile_term.  With d = 0.0, u is alpha and R - 0.0 is R: a pair without a
-// conditioning locus, or with one out of reach of every site, is bitwise surfaces_kernel's window.  No atomics: a pair's
-// numbers depend on that pair alone.
-struct CondParams {
-    SiteView sites; WindowView win;
-    const double *Rt; int NP, npairs, nslices;      // nslices: slices of SURFS_THREADS pairs
-    const double *A; int nA;
-    const int32_t *tests, *ctest, *clin;             // the listed pairs of this launch
-    double *T;        // [n][nA][npairs]
-    int32_t *ns;      // [n][nA]
-    int32_t *nsh;     // [n][nA]: the shared sites among ns
-};
-
-__global__ __launch_bounds__(SURFS_THREADS) void cond_surfaces_kernel(CondParams S) {
-    __shared__ double s_u[SURFS_THREADS];
-    __shared__ double s_d[SURFS_THREADS];
-    __shared__ int s_row[SURFS_THREADS];
-    __shared__ int64_t s_range[2];
-    const int tid = threadIdx.x;
-    const int slice = blockIdx.x % S.nslices;
-    const int iA = (blockIdx.x / S.nslices) % S.nA;
-    const int64_t q = blockIdx.x / S.nslices / S.nA;
-    const int p = slice * SURFS_THREADS + tid;
-    const bool live = p < S.npairs;
-    const int64_t t = S.tests[q];
-    const double A = S.A[iA], tg = S.win.test_gen[t];
-    const int32_t ct = S.ctest[q], cl = S.clin[q];
-    const bool cond = ct >= 0 && cl >= 0;
-    double tc = 0.0, Ac = 0.0;
-    int pc = 0;
-    int64_t clo = 0, chi = -1;                       // (no conditioning locus: no site is inside this window)
-    if (cond) {
-        tc = S.win.test_gen[ct]; Ac = S.A[cl / S.npairs]; pc = cl % S.npairs;
-        clo = max(S.win.win_lo[ct], (int64_t)0); chi = min(S.win.win_hi[ct], S.sites.N - 1);
-    }
-    if (tid < WAVE) {
-        const SiteRange R = window_range(S.sites, S.win, t, tg, A);
-        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
-    }
-    __syncthreads();
-    const int64_t rlo = s_range[0], rhi = s_range[1];
-    double sum = 0.0, z;
-    int ns = 0, nsh = 0;
+    [[maybe_unused]] int nsh = 0;
     for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
         const int64_t i = base + tid;
         const bool in = tile_site(S.sites.genpos, i, rhi, tg, A, S.win.zcut, z);
-        tile_store(S.sites.row, i, in, z, s_u, s_row);               // alpha for now
-        bool shared = false;
-        double d = 0.0;
-        if (in && i >= clo && i <= chi) {
-            const double g = S.sites.genpos[i], zc = Ac * fabs(g - tc);
-            shared = zc <= S.win.zcut && g != tc;
-            if (shared) d = exp(-zc) * S.Rt[(size_t)s_row[tid] * S.NP + pc];
+        tile_store(S.sites.row, i, in, z, s_u, s_row);
+        [[maybe_unused]] bool shared = false;
+        if constexpr (Side::sided) {
+            double d;
+            shared = side.site(S, locus, i, in, s_row, d);
+            s_d[tid] = d;
+            s_u[tid] = s_u[tid] / (1.0 + d);
         }
-        s_d[tid] = d;
-        s_u[tid] = s_u[tid] / (1.0 + d);
         ns += __syncthreads_count(in);
-        nsh += __syncthreads_count(shared);
+        if constexpr (Side::sided) nsh += __syncthreads_count(shared);
         if (live) {
             const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
             for (int s = 0; s < cnt; ++s) {
                 const int r_s = s_row[s];
-                if (r_s >= 0) sum += log1p(s_u[s] * (S.Rt[(size_t)r_s * S.NP + p] - s_d[s]));
+                if constexpr (Side::sided) {
+                    if (r_s >= 0) sum += log1p(s_u[s] * (S.Rt[(size_t)r_s * S.NP + p] - s_d[s]));
+                } else {
+                    if (r_s >= 0) sum += tile_term(s_u[s], r_s, S.Rt, S.NP, p);
+                }
             }
         }
         __syncthreads();
     }
     if (live) S.T[((size_t)q * S.nA + iA) * S.npairs + p] = ns ? 2.0 * sum : NAN;
-    if (slice == 0 && tid == 0) { S.ns[(size_t)q * S.nA + iA] = ns; S.nsh[(size_t)q * S.nA + iA] = nsh; }
+    if (slice == 0 && tid == 0) {
+        S.ns[(size_t)q * S.nA + iA] = ns;
+        if constexpr (Side::sided) S.nsh[(size_t)q * S.nA + iA] = nsh;
+    }
 }
 
-// ------------------------------------------------- a per-site baseline of accepted loci, and surfaces of listed windows against it
-// bmx_ctx_baseline_* and bmx_ctx_base_surfaces (the definition is ballermixplus_amd/stepwise.py).  The slot keeps d[N] and cnt[N]:
-// under the accepted loci site i follows g (1 + d_i), and cnt_i of them reach it.
+__global__ __launch_bounds__(SURFS_THREADS) void surfaces_kernel(SurfsParams S) { listed_surface(S, NoSide{}); }
+__global__ __launch_bounds__(SURFS_THREADS) void cond_surfaces_kernel(SurfsParams S, PairSide side) { listed_surface(S, side); }
+__global__ __launch_bounds__(SURFS_THREADS) void base_surfaces_kernel(SurfsParams S, BaselineSide side) { listed_surface(S, side); }
+
+// ------------------------------------------------------------------------------------ a per-site baseline of accepted loci
+// bmx_ctx_baseline_* (the definition is ballermixplus_amd/stepwise.py; base_surfaces_kernel above reads it).  The slot keeps d[N]
+// and cnt[N]: under the accepted loci site i follows g (1 + d_i), and cnt_i of them reach it.
 //   baseline_add_kernel: the locus is test site t held at (A, column p of the table).  Wave 0 of every workgroup finds the locus'
 //   site range with window_range (a few dozen probes), then the workgroups stride over the range in tiles of SURFS_THREADS sites,
 //   one thread per site: tile_site's predicate, d_i <- d_i + exp(-z) (R[row_i][p] - d_i) -- from d_i = 0.0 that is exp(-z) R bit
@@ -5081,10 +5086,6 @@ __global__ __launch_bounds__(SURFS_THREADS) void cond_surfaces_kernel(CondParams
 //   Workgroup 0 also writes out[0..2] = the first and last written site and how many were written, from the range as
 //   influence_range_kernel derives its o[2], o[3]: inside [a, b) every site passes the cut, and the sites [ctr, e) at the locus' own
 //   position are the only ones left out (first > last: none).
-//   base_surfaces_kernel: cond_surfaces_kernel with d_i and `shared` (cnt_i > 0) read from the slot's arrays: no exp, no gather on
-//   the conditioning side.  The same u = alpha / (1.0 + d), the same log1p(u (R - d)) in the same order, so after ONE
-//   baseline_add a window is bitwise cond_surfaces_kernel's pair (window | that locus), and against the empty baseline
-//   surfaces_kernel's window.  No atomics: a window's numbers depend on that window and the baseline alone.
 constexpr int BASE_ADD_GRID_MAX = 1024;       // workgroups of a baseline_add launch (they stride over the range)
 
 struct BaseAddParams {
@@ -5122,61 +5123,6 @@ __global__ __launch_bounds__(SURFS_THREADS) void baseline_add_kernel(BaseAddPara
             S.cnt[i] = S.cnt[i] + 1;
         }
     }
-}
-
-struct BaseParams {
-    SiteView sites; WindowView win;
-    const double *Rt; int NP, npairs, nslices;      // nslices: slices of SURFS_THREADS pairs
-    const double *A; int nA;
-    const int32_t *tests;                            // the listed test sites of this launch
-    const double *d; const int32_t *cnt;             // the slot's baseline: [N]
-    double *T;        // [n][nA][npairs]
-    int32_t *ns;      // [n][nA]
-    int32_t *nsh;     // [n][nA]: the sites among ns that an accepted locus reaches
-};
-
-__global__ __launch_bounds__(SURFS_THREADS) void base_surfaces_kernel(BaseParams S) {
-    __shared__ double s_u[SURFS_THREADS];
-    __shared__ double s_d[SURFS_THREADS];
-    __shared__ int s_row[SURFS_THREADS];
-    __shared__ int64_t s_range[2];
-    const int tid = threadIdx.x;
-    const int slice = blockIdx.x % S.nslices;
-    const int iA = (blockIdx.x / S.nslices) % S.nA;
-    const int64_t q = blockIdx.x / S.nslices / S.nA;
-    const int p = slice * SURFS_THREADS + tid;
-    const bool live = p < S.npairs;
-    const int64_t t = S.tests[q];
-    const double A = S.A[iA], tg = S.win.test_gen[t];
-    if (tid < WAVE) {
-        const SiteRange R = window_range(S.sites, S.win, t, tg, A);
-        if (tid == 0) { s_range[0] = R.a; s_range[1] = R.b - 1; }
-    }
-    __syncthreads();
-    const int64_t rlo = s_range[0], rhi = s_range[1];
-    double sum = 0.0, z;
-    int ns = 0, nsh = 0;
-    for (int64_t base = rlo; base <= rhi; base += SURFS_THREADS) {
-        const int64_t i = base + tid;
-        const bool in = tile_site(S.sites.genpos, i, rhi, tg, A, S.win.zcut, z);
-        tile_store(S.sites.row, i, in, z, s_u, s_row);               // alpha for now
-        const double d = in ? S.d[i] : 0.0;
-        const bool shared = in && S.cnt[i] > 0;
-        s_d[tid] = d;
-        s_u[tid] = s_u[tid] / (1.0 + d);
-        ns += __syncthreads_count(in);
-        nsh += __syncthreads_count(shared);
-        if (live) {
-            const int cnt = (int)min((int64_t)SURFS_THREADS, rhi - base + 1);
-            for (int s = 0; s < cnt; ++s) {
-                const int r_s = s_row[s];
-                if (r_s >= 0) sum += log1p(s_u[s] * (S.Rt[(size_t)r_s * S.NP + p] - s_d[s]));
-            }
-        }
-        __syncthreads();
-    }
-    if (live) S.T[((size_t)q * S.nA + iA) * S.npairs + p] = ns ? 2.0 * sum : NAN;
-    if (slice == 0 && tid == 0) { S.ns[(size_t)q * S.nA + iA] = ns; S.nsh[(size_t)q * S.nA + iA] = nsh; }
 }
 
 // ----------------------------------------------------------- delete-block jackknife of a list of test sites' grid maxima
@@ -5799,9 +5745,10 @@ struct bmx_ctx {
     int *d_status = nullptr;     // ... and its error bits
     DevBuf<double> surf_T;
     DevBuf<int32_t> surf_ns;
-    // surfaces of a list of test sites (bmx_ctx_surfaces): the list, one chunk's output, the events around a chunk's kernel
-    DevBuf<double> sfs_T;
-    DevBuf<int32_t> sfs_ns, sfs_list;
+    // surfaces of a list of test sites (bmx_ctx_surfaces, _cond_surfaces, _base_surfaces): the list, one chunk's outputs (T and
+    // nsites; under a side the shared counts; the maxima and argmaxes when asked for), the events around bmx_ctx_surfaces' chunks
+    DevBuf<double> sfs_T, sfs_tmax;
+    DevBuf<int32_t> sfs_ns, sfs_list, sfs_nsh, sfs_lin;
     DevTimer sfs;
     // delete-block jackknife (bmx_ctx_influence): the site ranges of the list at A_min and of one chunk at every A, the chunk's
     // runs of blocks, T_max / lin* and per-block outputs, the events around a chunk's kernels; the last call's results on the host
@@ -5819,15 +5766,11 @@ struct bmx_ctx {
     DevBuf<double> ft_gw, ft_edges, ft_ws, ft_Es, ft_En;
     DevBuf<int32_t> ft_lin, ft_cls, ft_O, ft_skip;
     DevTimer ft;
-    // conditional surfaces (bmx_ctx_cond_surfaces): the pairs' conditioning sites and grid points, one chunk's shared counts,
-    // maxima and argmaxes (T and nsites in the surfaces' buffers), the events around a chunk's kernels
-    DevBuf<int32_t> cs_ctest, cs_clin, cs_nsh, cs_lin;
-    DevBuf<double> cs_tmax;
+    // conditional surfaces (bmx_ctx_cond_surfaces): the pairs' conditioning sites and grid points, the events around a chunk's
+    // kernels (everything else in the surfaces' buffers)
+    DevBuf<int32_t> cs_ctest, cs_clin;
     DevTimer cs;
-    // surfaces against a slot's baseline (bmx_ctx_base_surfaces): one chunk's shared counts, maxima and argmaxes (the list, T and
-    // nsites in the surfaces' buffers), the events around a chunk's kernels; baseline_add's three numbers
-    DevBuf<int32_t> bs_nsh, bs_lin;
-    DevBuf<double> bs_tmax;
+    // surfaces against a slot's baseline (bmx_ctx_base_surfaces): the events around a chunk's kernels; baseline_add's three numbers
     DevBuf<int64_t> bs_out;
     DevTimer bs;
     // sandwich pieces (bmx_ctx_sandwich): the list, the points with the four shifted arguments of their columns, one chunk's
@@ -5949,6 +5892,64 @@ int list_ready(bmx_ctx *c, const std::string &who, int64_t n, const char *own, b
 int64_t surfaces_step(const bmx_ctx *c, int nsl) {
     const int64_t chunk = (int64_t)std::max<size_t>(BMX_SURFACES_CHUNK_BYTES / ((size_t)c->nA * c->npairs * sizeof(double)), 1);
     return std::min(chunk, std::max<int64_t>((0xffffffffLL / SURFS_THREADS) / ((int64_t)c->nA * nsl), 1));
+}
+// ... what the listed-surface kernels and bmx_ctx_influence's first stage take of the model and the slot (the list, the outputs and
+// a side are the caller's) ...
+SurfsParams surfs_params(const bmx_ctx *c, const ChromSlot *s, int nsl) {
+    SurfsParams S{};
+    S.sites = site_view(s); S.win = window_view(c, s);
+    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    return S;
+}
+// ... and everything bmx_ctx_surfaces, _cond_surfaces and _base_surfaces do with a list of n > 0 entries once their own refusals
+// are past: the entries' range, surfaces_step entries per launch on one set of device buffers, per chunk `launch(S, q0, grid)` --
+// the call's kernel with its side, on the chunk from entry q0 -- then influence_argmax_kernel when tmax or lin is wanted, the copies
+// that were asked for (a NULL output is not copied; without T_out the surfaces never leave the device), and the chunks' kernel
+// milliseconds summed into the call's timer.
+template <class Launch>
+int listed_surfaces(bmx_ctx *c, const std::string &who, int64_t n, const int32_t *tests, DevTimer &timer, Launch launch, double *T_out,
+                    int32_t *nsites_out, int32_t *nshared_out, double *tmax_out, int32_t *lin_out) {
+    ChromSlot *s = c->cur;
+    for (int64_t q = 0; q < n; q++)
+        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, who + ": test site index out of range at entry " + std::to_string(q));
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one entry's surface
+    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
+    const int64_t step = surfaces_step(c, nsl);
+    const size_t first = (size_t)std::min<int64_t>(step, n);
+    HIP_TRY(c->sfs_T.ensure(first * per));
+    HIP_TRY(c->sfs_ns.ensure(first * c->nA));
+    HIP_TRY(c->sfs_nsh.ensure(first * c->nA));
+    HIP_TRY(c->sfs_tmax.ensure(first));
+    HIP_TRY(c->sfs_lin.ensure(first));
+    int rc;
+    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
+    SurfsParams S = surfs_params(c, s, nsl);
+    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p; S.nsh = c->sfs_nsh.p;
+    double total = 0.0;
+    for (int64_t q0 = 0; q0 < n; q0 += step) {
+        const int64_t m = std::min(step, n - q0);
+        S.tests = c->sfs_list.p + q0;
+        HIP_TRY(timer.begin(c->stream));
+        launch(S, q0, dim3((unsigned)(m * c->nA * nsl)));
+        if (tmax_out || lin_out)
+            hipLaunchKernelGGL(influence_argmax_kernel, dim3((unsigned)m), dim3(INFL_THREADS), 0, c->stream, (const double *)c->sfs_T.p,
+                               (int64_t)per, c->sfs_tmax.p, c->sfs_lin.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(timer.end(c->stream));
+        // each chunk goes back before the next is launched: one set of device buffers serves the whole list
+        const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+        if (T_out) HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), D2H, c->stream));
+        if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
+        if (nshared_out) HIP_TRY(hipMemcpyAsync(nshared_out + (size_t)q0 * c->nA, c->sfs_nsh.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
+        if (tmax_out) HIP_TRY(hipMemcpyAsync(tmax_out + q0, c->sfs_tmax.p, (size_t)m * sizeof(double), D2H, c->stream));
+        if (lin_out) HIP_TRY(hipMemcpyAsync(lin_out + q0, c->sfs_lin.p, (size_t)m * sizeof(int32_t), D2H, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(timer.read());
+        total += timer.ms;
+    }
+    timer.ms = total;        // the call's figure: its chunks' kernels
+    return BMX_OK;
 }
 
 int validate_model(const bmx_model *m) {
@@ -6176,7 +6177,7 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->slots.clear();
     c->part_T.release(); c->part_lin.release(); c->part_ns.release(); c->arena.release(); c->gap_sample.release();
     c->surf_T.release(); c->surf_ns.release();
-    c->sfs_T.release(); c->sfs_ns.release(); c->sfs_list.release();
+    c->sfs_T.release(); c->sfs_ns.release(); c->sfs_list.release(); c->sfs_nsh.release(); c->sfs_tmax.release(); c->sfs_lin.release();
     c->sfs.release();
     c->if_rng1.release(); c->if_rng.release(); c->if_items.release(); c->if_tmax.release(); c->if_contrib.release();
     c->if_L.release(); c->if_lin.release(); c->if_m.release(); c->if_blin.release();
@@ -6184,9 +6185,9 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     c->ft_gw.release(); c->ft_edges.release(); c->ft_ws.release(); c->ft_Es.release(); c->ft_En.release();
     c->ft_lin.release(); c->ft_cls.release(); c->ft_O.release(); c->ft_skip.release();
     c->ft.release();
-    c->cs_ctest.release(); c->cs_clin.release(); c->cs_nsh.release(); c->cs_lin.release(); c->cs_tmax.release();
+    c->cs_ctest.release(); c->cs_clin.release();
     c->cs.release();
-    c->bs_nsh.release(); c->bs_lin.release(); c->bs_tmax.release(); c->bs_out.release();
+    c->bs_out.release();
     c->bs.release();
     c->sw_list.release(); c->sw_cnt.release(); c->sw_pts.release(); c->sw_out.release(); c->sw_R.release();
     c->sw.release();
@@ -7192,42 +7193,17 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
     return BMX_OK;
 }
 
+// The three listed-surface calls: their own refusals, then listed_surfaces.  They differ on purpose in three places, held by the
+// refusal and lifetime tests: bmx_ctx_surfaces refuses a NULL T_out where the other two take it as "do not copy the surfaces
+// back"; with n == 0 it leaves its milliseconds alone where the other two set theirs to 0.0; and bmx_ctx_base_surfaces refuses a
+// missing baseline after list_ready and before its n == 0 return.
 int bmx_ctx_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T_out, int32_t *nsites_out) {
     int rc;
     if ((rc = list_ready(c, "surfaces", n, nullptr, !tests || !T_out))) return rc;
     if (n == 0) return BMX_OK;
-    ChromSlot *s = c->cur;
-    for (int64_t q = 0; q < n; q++)
-        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "surfaces: test site index out of range at entry " + std::to_string(q));
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one window's surface
-    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
-    const int64_t step = surfaces_step(c, nsl);
-    HIP_TRY(c->sfs_T.ensure((size_t)std::min<int64_t>(step, n) * per));
-    HIP_TRY(c->sfs_ns.ensure((size_t)std::min<int64_t>(step, n) * c->nA));
-    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
-    SurfsParams S;
-    S.sites = site_view(s); S.win = window_view(c, s);
-    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
-    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p;
-    double total = 0.0;
-    for (int64_t q0 = 0; q0 < n; q0 += step) {
-        const int64_t m = std::min(step, n - q0);
-        S.tests = c->sfs_list.p + q0;
-        HIP_TRY(c->sfs.begin(c->stream));
-        hipLaunchKernelGGL(surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(c->sfs.end(c->stream));
-        // each chunk goes back before the next is launched: one device buffer serves the whole list
-        HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (nsites_out)
-            HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->sfs.read());
-        total += c->sfs.ms;
-    }
-    c->sfs.ms = total;       // the call's figure: its chunks' kernels
-    return BMX_OK;
+    return listed_surfaces(c, "surfaces", n, tests, c->sfs, [&](const SurfsParams &S, int64_t, dim3 grid) {
+        hipLaunchKernelGGL(surfaces_kernel, grid, dim3(SURFS_THREADS), 0, c->stream, S);
+    }, T_out, nsites_out, nullptr, nullptr, nullptr);
 }
 
 int bmx_ctx_surfaces_ms(bmx_ctx *c, double *ms) {
@@ -7282,9 +7258,7 @@ int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block
     const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
     const int64_t step = surfaces_step(c, nsl);
     const int64_t INFL_CHUNK_BLOCKS = 1 << 22;
-    SurfsParams S;
-    S.sites = Q.sites; S.win = Q.win;
-    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    SurfsParams S = surfs_params(c, s, nsl);
     InflParams P;
     P.sites = Q.sites; P.win = Q.win; P.Rt = c->d_Rt; P.NP = c->NP; P.npairs = c->npairs; P.nslices = nsl;
     P.A = c->d_A; P.nA = c->nA; P.iAmin = iAmin; P.B = B;
@@ -7458,54 +7432,24 @@ int bmx_ctx_cond_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, const int
     if ((rc = list_ready(c, "cond_surfaces", n, nullptr, !tests || !cond_test || !cond_lin))) return rc;
     if (n == 0) { c->cs.ms = 0.0; return BMX_OK; }
     ChromSlot *s = c->cur;
-    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one pair's surface
-    for (int64_t q = 0; q < n; q++) {
-        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "cond_surfaces: test site index out of range at entry " + std::to_string(q));
+    const size_t per = (size_t)c->nA * c->npairs;
+    // the conditioning entries up to the first test site index out of range: listed_surfaces refuses that entry, in its place in
+    // the order of one pass over the entries, and nothing has touched the device by then
+    int64_t q = 0;
+    for (; q < n && tests[q] >= 0 && tests[q] < s->M; q++) {
         if (cond_test[q] < -1 || cond_test[q] >= s->M)
             return fail(BMX_E_INVALID, "cond_surfaces: conditioning test site index out of range at entry " + std::to_string(q));
         if (cond_lin[q] >= 0 && (size_t)cond_lin[q] >= per)
             return fail(BMX_E_INVALID, "cond_surfaces: conditioning grid index out of range at entry " + std::to_string(q));
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
-    const int64_t step = surfaces_step(c, nsl);
-    const size_t first = (size_t)std::min<int64_t>(step, n);
-    HIP_TRY(c->sfs_T.ensure(first * per));
-    HIP_TRY(c->sfs_ns.ensure(first * c->nA));
-    HIP_TRY(c->cs_nsh.ensure(first * c->nA));
-    HIP_TRY(c->cs_tmax.ensure(first));
-    HIP_TRY(c->cs_lin.ensure(first));
-    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
-    if ((rc = upload(c->cs_ctest, cond_test, (size_t)n, c->stream))) return rc;
-    if ((rc = upload(c->cs_clin, cond_lin, (size_t)n, c->stream))) return rc;
-    CondParams S;
-    S.sites = site_view(s); S.win = window_view(c, s);
-    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
-    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p; S.nsh = c->cs_nsh.p;
-    double total = 0.0;
-    for (int64_t q0 = 0; q0 < n; q0 += step) {
-        const int64_t m = std::min(step, n - q0);
-        S.tests = c->sfs_list.p + q0; S.ctest = c->cs_ctest.p + q0; S.clin = c->cs_clin.p + q0;
-        HIP_TRY(c->cs.begin(c->stream));
-        hipLaunchKernelGGL(cond_surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
-        if (tmax_out || lin_out)
-            hipLaunchKernelGGL(influence_argmax_kernel, dim3((unsigned)m), dim3(INFL_THREADS), 0, c->stream, (const double *)c->sfs_T.p,
-                               (int64_t)per, c->cs_tmax.p, c->cs_lin.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(c->cs.end(c->stream));
-        // each chunk goes back before the next is launched, as in bmx_ctx_surfaces; without T_out the surfaces stay on the device
-        const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
-        if (T_out) HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), D2H, c->stream));
-        if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
-        if (nshared_out) HIP_TRY(hipMemcpyAsync(nshared_out + (size_t)q0 * c->nA, c->cs_nsh.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
-        if (tmax_out) HIP_TRY(hipMemcpyAsync(tmax_out + q0, c->cs_tmax.p, (size_t)m * sizeof(double), D2H, c->stream));
-        if (lin_out) HIP_TRY(hipMemcpyAsync(lin_out + q0, c->cs_lin.p, (size_t)m * sizeof(int32_t), D2H, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->cs.read());
-        total += c->cs.ms;
+    if (q == n) {
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = upload(c->cs_ctest, cond_test, (size_t)n, c->stream))) return rc;
+        if ((rc = upload(c->cs_clin, cond_lin, (size_t)n, c->stream))) return rc;
     }
-    c->cs.ms = total;        // the call's figure: its chunks' kernels
-    return BMX_OK;
+    return listed_surfaces(c, "cond_surfaces", n, tests, c->cs, [&](const SurfsParams &S, int64_t q0, dim3 grid) {
+        hipLaunchKernelGGL(cond_surfaces_kernel, grid, dim3(SURFS_THREADS), 0, c->stream, S, PairSide{c->cs_ctest.p + q0, c->cs_clin.p + q0});
+    }, T_out, nsites_out, nshared_out, tmax_out, lin_out);
 }
 
 int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms) {
@@ -7572,48 +7516,9 @@ int bmx_ctx_base_surfaces(bmx_ctx *c, int64_t n, const int32_t *tests, double *T
     ChromSlot *s = c->cur;
     if (!s->bl_have) return fail(BMX_E_STATE, "base_surfaces: no baseline (bmx_ctx_baseline_reset) on this slot's sites");
     if (n == 0) { c->bs.ms = 0.0; return BMX_OK; }
-    for (int64_t q = 0; q < n; q++)
-        if (tests[q] < 0 || tests[q] >= s->M) return fail(BMX_E_INVALID, "base_surfaces: test site index out of range at entry " + std::to_string(q));
-    HIP_TRY(hipSetDevice(c->device));
-    const int nsl = (c->npairs + SURFS_THREADS - 1) / SURFS_THREADS;
-    const size_t per = (size_t)c->nA * c->npairs;              // doubles of one window's surface
-    const int64_t step = surfaces_step(c, nsl);                // the windows per chunk, as bmx_ctx_cond_surfaces takes them
-    const size_t first = (size_t)std::min<int64_t>(step, n);
-    HIP_TRY(c->sfs_T.ensure(first * per));
-    HIP_TRY(c->sfs_ns.ensure(first * c->nA));
-    HIP_TRY(c->bs_nsh.ensure(first * c->nA));
-    HIP_TRY(c->bs_tmax.ensure(first));
-    HIP_TRY(c->bs_lin.ensure(first));
-    if ((rc = upload(c->sfs_list, tests, (size_t)n, c->stream))) return rc;
-    BaseParams S;
-    S.sites = site_view(s); S.win = window_view(c, s);
-    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
-    S.d = s->bl_d.p; S.cnt = s->bl_cnt.p;
-    S.T = c->sfs_T.p; S.ns = c->sfs_ns.p; S.nsh = c->bs_nsh.p;
-    double total = 0.0;
-    for (int64_t q0 = 0; q0 < n; q0 += step) {
-        const int64_t m = std::min(step, n - q0);
-        S.tests = c->sfs_list.p + q0;
-        HIP_TRY(c->bs.begin(c->stream));
-        hipLaunchKernelGGL(base_surfaces_kernel, dim3((unsigned)(m * c->nA * nsl)), dim3(SURFS_THREADS), 0, c->stream, S);
-        if (tmax_out || lin_out)
-            hipLaunchKernelGGL(influence_argmax_kernel, dim3((unsigned)m), dim3(INFL_THREADS), 0, c->stream, (const double *)c->sfs_T.p,
-                               (int64_t)per, c->bs_tmax.p, c->bs_lin.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(c->bs.end(c->stream));
-        // each chunk goes back before the next is launched, as in bmx_ctx_cond_surfaces; without T_out the surfaces stay on the device
-        const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
-        if (T_out) HIP_TRY(hipMemcpyAsync(T_out + (size_t)q0 * per, c->sfs_T.p, (size_t)m * per * sizeof(double), D2H, c->stream));
-        if (nsites_out) HIP_TRY(hipMemcpyAsync(nsites_out + (size_t)q0 * c->nA, c->sfs_ns.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
-        if (nshared_out) HIP_TRY(hipMemcpyAsync(nshared_out + (size_t)q0 * c->nA, c->bs_nsh.p, (size_t)m * c->nA * sizeof(int32_t), D2H, c->stream));
-        if (tmax_out) HIP_TRY(hipMemcpyAsync(tmax_out + q0, c->bs_tmax.p, (size_t)m * sizeof(double), D2H, c->stream));
-        if (lin_out) HIP_TRY(hipMemcpyAsync(lin_out + q0, c->bs_lin.p, (size_t)m * sizeof(int32_t), D2H, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->bs.read());
-        total += c->bs.ms;
-    }
-    c->bs.ms = total;        // the call's figure: its chunks' kernels
-    return BMX_OK;
+    return listed_surfaces(c, "base_surfaces", n, tests, c->bs, [&](const SurfsParams &S, int64_t, dim3 grid) {
+        hipLaunchKernelGGL(base_surfaces_kernel, grid, dim3(SURFS_THREADS), 0, c->stream, S, BaselineSide{s->bl_d.p, s->bl_cnt.p});
+    }, T_out, nsites_out, nshared_out, tmax_out, lin_out);
 }
 
 int bmx_ctx_base_surfaces_ms(bmx_ctx *c, double *ms) {

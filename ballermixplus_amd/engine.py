@@ -543,17 +543,19 @@ class Context:
         cond_lin[q] = (iA * nx + ix) * nab + ia (< 0: none).  Returns a dict: T f64[n, nA, nx, nab] (None without want_T: the
         surfaces are then not copied back), nsites i32[n, nA], nshared i32[n, nA], tmax f64[n] and lin i32[n] (the scan's rule on
         each pair's T; 0 and -1 when nothing is > 0)."""
-        m = self.model
         t, ct, cl = _lib.i32(tests), _lib.i32(cond_test), _lib.i32(cond_lin)
         if t.ndim != 1 or ct.shape != t.shape or cl.shape != t.shape:
             raise ValueError('a flat list of test site indices and one conditioning site and grid point per entry are needed')
-        n = len(t)
+        return self._sided_surfaces(self._L.bmx_ctx_cond_surfaces, (_lib.as_ip(t), _lib.as_ip(ct), _lib.as_ip(cl)), len(t), want_T)
+
+    def _sided_surfaces(self, call, lists, n, want_T):
+        """cond_surfaces' and base_surfaces' dict, filled by `call` (their entry point) on the list(s) of n entries."""
+        m = self.model
         out = {'T': np.empty((n, self.nA, len(m.x), len(m.abeta)), dtype=np.float64) if want_T else None,
                'nsites': np.empty((n, self.nA), dtype=np.int32), 'nshared': np.empty((n, self.nA), dtype=np.int32),
                'tmax': np.empty(n, dtype=np.float64), 'lin': np.empty(n, dtype=np.int32)}
-        _lib.check(self._L.bmx_ctx_cond_surfaces(self._h, n, _lib.as_ip(t), _lib.as_ip(ct), _lib.as_ip(cl),
-                                                 _lib.as_dp(out['T']) if want_T else None, _lib.as_ip(out['nsites']),
-                                                 _lib.as_ip(out['nshared']), _lib.as_dp(out['tmax']), _lib.as_ip(out['lin'])))
+        _lib.check(call(self._h, n, *lists, _lib.as_dp(out['T']) if want_T else None, _lib.as_ip(out['nsites']),
+                        _lib.as_ip(out['nshared']), _lib.as_dp(out['tmax']), _lib.as_ip(out['lin'])))
         return out
 
     def cond_surfaces_ms(self):
@@ -585,18 +587,10 @@ class Context:
         accepted loci (ballermixplus_amd/stepwise.py).  Returns cond_surfaces' dict: T f64[n, nA, nx, nab] (None without want_T:
         the surfaces are then not copied back), nsites i32[n, nA], nshared i32[n, nA] (the sites an accepted locus reaches),
         tmax f64[n] and lin i32[n] (the scan's rule on each window's T; 0 and -1 when nothing is > 0)."""
-        m = self.model
         t = _lib.i32(tests)
         if t.ndim != 1:
             raise ValueError('a flat list of test site indices is needed')
-        n = len(t)
-        out = {'T': np.empty((n, self.nA, len(m.x), len(m.abeta)), dtype=np.float64) if want_T else None,
-               'nsites': np.empty((n, self.nA), dtype=np.int32), 'nshared': np.empty((n, self.nA), dtype=np.int32),
-               'tmax': np.empty(n, dtype=np.float64), 'lin': np.empty(n, dtype=np.int32)}
-        _lib.check(self._L.bmx_ctx_base_surfaces(self._h, n, _lib.as_ip(t), _lib.as_dp(out['T']) if want_T else None,
-                                                 _lib.as_ip(out['nsites']), _lib.as_ip(out['nshared']), _lib.as_dp(out['tmax']),
-                                                 _lib.as_ip(out['lin'])))
-        return out
+        return self._sided_surfaces(self._L.bmx_ctx_base_surfaces, (_lib.as_ip(t),), len(t), want_T)
 
     def base_surfaces_ms(self):
         """Device milliseconds of the kernels of the context's last base_surfaces() call."""

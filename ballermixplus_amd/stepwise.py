@@ -109,32 +109,11 @@ def host_baseline_add(d, cnt, genpos, rows, R, tc, clo, chi, A_c, ix_c, ia_c, zc
 
 
 def host_base_surface(genpos, rows, R, A, tg, lo, hi, d, cnt, zcut, scale=False):
-    """The surface of one window against the baseline (d[N], cnt[N]) in numpy: conditional.host_cond_surface with d_i read from
-    the array and `shared` meaning cnt_i > 0.  Returns (T[nA][nx][nab], NaN where no site qualifies; nsites[nA]; nshared[nA]) and
+    """The surface of one window against the baseline (d[N], cnt[N]) in numpy: conditional.host_cond_surface's body
+    (surfaces.host_sided_surface) with d_i read from the array and `shared` meaning cnt_i > 0.  Returns (T[nA][nx][nab], NaN where no site qualifies; nsites[nA]; nshared[nA]) and
     with scale=True also S[nA][nx][nab] = 2 sum_i |term_i|."""
-    g = np.asarray(genpos, dtype=np.float64)
-    rows = np.asarray(rows, dtype=np.int64)
-    R = np.asarray(R, dtype=np.float64)
-    A = np.atleast_1d(np.asarray(A, dtype=np.float64))
-    a, b = max(int(lo), 0), min(int(hi), len(g) - 1)
-    T = np.full((len(A),) + R.shape[:2], np.nan)
-    S = np.zeros(T.shape)
-    ns, nsh = np.zeros(len(A), dtype=np.int32), np.zeros(len(A), dtype=np.int32)
-    if b >= a:
-        gw, rw = g[a:b + 1], rows[a:b + 1]
-        dw, shared = np.asarray(d, dtype=np.float64)[a:b + 1], np.asarray(cnt)[a:b + 1] > 0
-        dist = np.abs(gw - tg)
-        for i, Av in enumerate(A.tolist()):
-            z = Av * dist
-            keep = (z <= zcut) & (gw != tg)
-            ns[i], nsh[i] = int(keep.sum()), int((keep & shared).sum())
-            if ns[i]:
-                with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
-                    u = np.exp(-z[keep]) / (1.0 + dw[keep])
-                    term = np.log1p(u * (R[:, :, rw[keep]] - dw[keep]))
-                    T[i] = 2.0 * np.sum(term, axis=2)
-                    S[i] = 2.0 * np.sum(np.abs(term), axis=2)
-    return (T, ns, nsh, S) if scale else (T, ns, nsh)
+    side = lambda a, b, gw, rw, R: (np.asarray(d, dtype=np.float64)[a:b + 1], np.asarray(cnt)[a:b + 1] > 0)
+    return surfaces.host_sided_surface(genpos, rows, R, A, tg, lo, hi, side, zcut, scale)
 
 
 def site_ranges(genpos, tg, lo, hi, A_min, zcut):

@@ -84,6 +84,38 @@ def host_surface(genpos, rows, R, A, tg, lo, hi, zcut):
     return T, ns
 
 
+def host_sided_surface(genpos, rows, R, A, tg, lo, hi, side, zcut, scale=False):
+    """The surface of one window whose sites follow g (1 + d_i) instead of neutrality, in numpy: the body that
+    conditional.host_cond_surface and stepwise.host_base_surface share (the definitions are theirs).  host_surface's arguments,
+    and side(a, b, gw, rw, R) -> (d f64[b - a + 1], shared bool[b - a + 1]) of the sites a .. b of the clipped window (gw, rw:
+    their positions and table rows).  T = 2 sum_i log1p(u_i (R_i - d_i)), u_i = alpha_i / (1.0 + d_i), over host_surface's sites.
+    Returns (T[nA][nx][nab], NaN where no site qualifies; nsites[nA]; nshared[nA]: the shared sites among them) and with
+    scale=True also S[nA][nx][nab] = 2 sum_i |term_i| (0 where no site qualifies): the size of what cancels in T."""
+    g = np.asarray(genpos, dtype=np.float64)
+    rows = np.asarray(rows, dtype=np.int64)
+    R = np.asarray(R, dtype=np.float64)
+    A = np.atleast_1d(np.asarray(A, dtype=np.float64))
+    a, b = max(int(lo), 0), min(int(hi), len(g) - 1)
+    T = np.full((len(A),) + R.shape[:2], np.nan)
+    S = np.zeros(T.shape)
+    ns, nsh = np.zeros(len(A), dtype=np.int32), np.zeros(len(A), dtype=np.int32)
+    if b >= a:
+        gw, rw = g[a:b + 1], rows[a:b + 1]
+        d, shared = side(a, b, gw, rw, R)
+        dist = np.abs(gw - tg)
+        for i, Av in enumerate(A.tolist()):
+            z = Av * dist
+            keep = (z <= zcut) & (gw != tg)
+            ns[i], nsh[i] = int(keep.sum()), int((keep & shared).sum())
+            if ns[i]:
+                with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+                    u = np.exp(-z[keep]) / (1.0 + d[keep])
+                    term = np.log1p(u * (R[:, :, rw[keep]] - d[keep]))
+                    T[i] = 2.0 * np.sum(term, axis=2)
+                    S[i] = 2.0 * np.sum(np.abs(term), axis=2)
+    return (T, ns, nsh, S) if scale else (T, ns, nsh)
+
+
 # ---------------------------------------------------------------------------------------------------------- output
 
 def output_name(outfile):

@@ -1,11 +1,12 @@
 """The listed-window calls across their chunk seams: the cases of tests/test_chunkseams_cpu.py (which shows on the host that every
 case crosses the seam it is named for) and tests/test_gpu_chunk_seams.py (which runs them on the device), and a host restatement of
-the six rules by which bmx_ctx_surfaces, _influence, _fit and _cond_surfaces cut their list into chunks.  numpy and the package's
-pure-Python modules only; nothing is read from a file.
+the six rules by which bmx_ctx_surfaces, _influence, _fit, _cond_surfaces and _base_surfaces cut their list into chunks.  numpy and
+the package's pure-Python modules only; nothing is read from a file.
 
 The rules (ballermixplus_amd/csrc/bmxscan.hip; LITERALS below are matched against the sources by the CPU module):
-  1. surfaces_step, bytes     BMX_SURFACES_CHUNK_BYTES / (nA * npairs * 8) windows         surfaces, influence, cond_surfaces
-  2. surfaces_step, threads   (0xffffffff / 256) / (nA * nsl) windows, nsl = slices of 256 pairs          the same three
+  1. surfaces_step, bytes     BMX_SURFACES_CHUNK_BYTES / (nA * npairs * 8) windows         surfaces, influence, cond_surfaces,
+                                                                                                       base_surfaces
+  2. surfaces_step, threads   (0xffffffff / 256) / (nA * nsl) windows, nsl = slices of 256 pairs           the same four
   3. influence, range pass    rstep = 1 << 20 windows
   4. influence, blocks        INFL_CHUNK_BLOCKS = 1 << 22 blocks per chunk, one window if it has more
   5. fit, outputs             (64 << 20) / (D * F * 20) windows
@@ -20,7 +21,8 @@ q mod 13 of a call that lists the 13 once.
 
 Cases (name: model, calls):
   bytes      gridshape 'small', 17 x 61 pairs (5 slices of 256), 64 A: one surface 530 944 bytes, step 505.  surfaces, influence
-             (block 10^6 and 3) and cond_surfaces with T at n = step + 3; cond_surfaces without T at n = 2 step + 3 (three chunks)
+             (block 10^6 and 3) and cond_surfaces with T at n = step + 3; cond_surfaces without T at n = 2 step + 3 (three chunks);
+             base_surfaces after one baseline_add the same two ways
   threads    one pair, 16 A: bytes 2 097 152, threads 1 048 575 windows.  surfaces and cond_surfaces at n = step + 5
   range      the same model.  influence, block 10^6, at n = 2^20 + 3: the range pass cuts at 2^20, the window chunks at 1 048 575
   blocks     one pair, one A that reaches across the 700 sites of chromosome 'S', whole-chromosome windows, block 1: about 700
@@ -75,13 +77,14 @@ LITERALS = [
     ('ballermixplus_amd/csrc/bmxscan.hip',
      r'if \(!in_lds\) step = std::min\(step, std::max<int64_t>\(BMX_SURFACES_CHUNK_BYTES / \(int64_t\)\(tab \* sizeof\(double\)\), 1\)\);'),
 ]
-# how often the byte-and-thread step is taken: bmx_ctx_surfaces, _influence and _cond_surfaces
-LITERAL_COUNTS = {5: 3}
+# how often the byte-and-thread step is taken: listed_surfaces (the loop of bmx_ctx_surfaces, _cond_surfaces and _base_surfaces) and
+# bmx_ctx_influence
+LITERAL_COUNTS = {5: 2}
 
 
 # ------------------------------------------------------------------------------------------------ the rules, restated
 def surfaces_step(nA, npairs):
-    """(windows per chunk, by rule 1, by rule 2) of bmx_ctx_surfaces, _influence and _cond_surfaces."""
+    """(windows per chunk, by rule 1, by rule 2) of bmx_ctx_surfaces, _influence, _cond_surfaces and _base_surfaces."""
     nsl = -(-npairs // SURFS_THREADS)
     by_bytes = max(CHUNK_BYTES // (nA * npairs * 8), 1)
     by_threads = max((LAUNCH_THREADS // SURFS_THREADS) // (nA * nsl), 1)
@@ -160,6 +163,13 @@ def cond_partners(points):
     cl = [(j * 7919 + 11) % points for j in range(K)]
     ct[11], cl[2] = -1, -1
     return np.array(ct, dtype=np.int32), np.array(cl, dtype=np.int32)
+
+
+def base_locus(sc):
+    """(test site, lin) of the ONE locus the base_surfaces calls put into the baseline: entry 5 of the 13 (site 1203, a position
+    tie) held at the smallest A of the grid, which reaches every site of its window; entry 6's window (site 1206) overlaps it."""
+    assert int(np.argmin(sc.As)) == 0
+    return 5, 500 % sc.npairs
 
 
 # ------------------------------------------------------------------------------------------------ scenes
@@ -324,7 +334,7 @@ def fit_arrays(sc, F, D, zcut):
 
 # ------------------------------------------------------------------------------------------------ cases
 class Call:
-    """One call of a case: op in ('surfaces', 'influence', 'cond', 'fit'), its list length n, the restated chunk lengths per loop
+    """One call of a case: op in ('surfaces', 'influence', 'cond', 'base', 'fit'), its list length n, the restated chunk lengths per loop
     ({'windows': [...]} and, for influence, {'range': [...]}), the bytes of its host outputs, and the op's own arguments."""
 
     def __init__(self, op, n, cuts, host_bytes, **kw):
@@ -362,6 +372,8 @@ def bytes_case(zcut):
     calls.append(Call('cond', n, {'windows': even_cuts(n, step)}, _cond_bytes(sc, n), want_T=True))
     n3 = 2 * step + 3
     calls.append(Call('cond', n3, {'windows': even_cuts(n3, step)}, _cond_bytes(sc, n3, False), want_T=False))
+    calls.append(Call('base', n, {'windows': even_cuts(n, step)}, _cond_bytes(sc, n), want_T=True))
+    calls.append(Call('base', n3, {'windows': even_cuts(n3, step)}, _cond_bytes(sc, n3, False), want_T=False))
     return sc, calls
 
 

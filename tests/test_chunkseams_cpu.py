@@ -66,9 +66,10 @@ def test_every_case_crosses_its_seam(name):
     step, by_bytes, by_threads = cs.surfaces_step(sc.nA, sc.npairs)
     if name == 'bytes':
         assert sc.nA * sc.npairs * 8 == 530944 and -(-sc.npairs // 256) == 5 and (step, by_bytes) == (505, 505) and by_threads > step
-        assert [c.cuts['windows'] for c in calls] == [[505, 3]] * 4 + [[505, 505, 3]]
+        assert [c.cuts['windows'] for c in calls] == [[505, 3]] * 4 + [[505, 505, 3]] + [[505, 3], [505, 505, 3]]
         assert [c.kw.get('block') for c in calls[1:3]] == [10 ** 6, 3] and calls[1].cuts['range'] == [508]
         assert calls[3].kw['want_T'] and not calls[4].kw['want_T'] and 260e6 < calls[0].host_bytes < 280e6
+        assert [(c.op, c.kw['want_T']) for c in calls[3:]] == [('cond', True), ('cond', False), ('base', True), ('base', False)]
     if name == 'threads':
         assert (by_bytes, by_threads, step) == (2097152, 1048575, 1048575)
         assert all(c.cuts['windows'] == [1048575, 5] for c in calls) and [c.op for c in calls] == ['surfaces', 'cond']

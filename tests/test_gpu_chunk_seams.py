@@ -1,4 +1,4 @@
-"""bmx_ctx_surfaces, _influence, _fit and _cond_surfaces across their chunk seams (tests/chunkseams.py holds the cases and the
+"""bmx_ctx_surfaces, _influence, _fit, _cond_surfaces and _base_surfaces across their chunk seams (tests/chunkseams.py holds the cases and the
 restated chunk rules; tests/test_chunkseams_cpu.py shows on the host that every case crosses the seam it is named for).
 
 Every call lists tests[q] = q mod 13 over 13 distinct test sites, long enough for a second (or third) chunk.  Two layers:
@@ -8,7 +8,8 @@ Every call lists tests[q] = q mod 13 over 13 distinct test sites, long enough fo
   * the 13-entry call against the host restatements (surfaces.host_surface, influence.host_influence, fit.host_fit,
     conditional.host_cond_surface) on the device's own table, at the tolerances those features have: influencecases.REL_TOL of
     max |T|, fitcases.TOL * max(1, n_d), condcases.REL_TOL of the conditional scale; integer fields exact; lin and lin_b exact
-    where the host margin exceeds twice the tolerance (at least 99 % of the blocks).
+    where the host margin exceeds twice the tolerance (at least 99 % of the blocks).  base_surfaces, after ONE baseline_add, against
+    cond_surfaces of every window given that locus: the same bytes, which is the contract between the two.
 The one-window case lists three windows once: the long one against the vectorised one-point jackknife of chunkseams.py, and the
 three against calls that list them apart.
 
@@ -70,7 +71,7 @@ def _release():
     for ctx, _ in _CTX.values():
         ctx.close()
     _CTX.clear()
-    for f in (_short_surfaces, _short_influence, _short_cond, _short_fit):
+    for f in (_short_surfaces, _short_influence, _short_cond, _short_base, _short_fit):
         f.cache_clear()
 
 
@@ -248,6 +249,22 @@ def _short_cond(scene):
     return res
 
 
+@functools.lru_cache(maxsize=None)
+def _short_base(scene):
+    """The 13 windows against a baseline of one locus (chunkseams.base_locus), which stays in the scene's slot for the long calls."""
+    sc, (ctx, R) = cs.scene(scene), _ctx(scene)
+    t, lin = cs.base_locus(sc)
+    ctx.baseline_reset()
+    assert ctx.baseline_add(t, lin)[2] > 0
+    res = ctx.base_surfaces(cs.rotation(K), want_T=True)
+    pair = ctx.cond_surfaces(cs.rotation(K), np.full(K, t, np.int32), np.full(K, lin, np.int32), want_T=True)
+    assert all(_u(res[k]).tobytes() == _u(pair[k]).tobytes() for k in ('T', 'nsites', 'nshared', 'tmax', 'lin'))
+    assert (res['nshared'].max(axis=1) > 0).sum() >= 2 and not (res['nshared'].max(axis=1) > 0).all()
+    bare = ctx.base_surfaces(cs.rotation(K), want_T=False)
+    assert bare['T'] is None and all(_u(bare[k]).tobytes() == _u(res[k]).tobytes() for k in ('nsites', 'nshared', 'tmax', 'lin'))
+    return res
+
+
 def _fit_call(scene, call, n=None):
     sc, (ctx, R) = cs.scene(scene), _ctx(scene)
     n = call.n if n is None else n
@@ -306,6 +323,21 @@ def _cond_seam(name, scene, want_T):
     assert want_T or res['T'] is None
 
 
+def _base_seam(name, scene, want_T):
+    sc, calls = _case(name)
+    call = [c for c in calls if c.op == 'base' and c.kw['want_T'] == want_T][0]
+    assert len(call.cuts['windows']) >= (2 if want_T else 3)
+    ctx, R = _ctx(scene)
+    short = _short_base(scene)
+    t0 = time.perf_counter()
+    res = ctx.base_surfaces(cs.rotation(call.n), want_T=want_T)
+    _timed('%s: base_surfaces of %d windows in chunks of %s, T %s (kernels %.1f ms)'
+           % (name, call.n, call.cuts['windows'], 'copied back' if want_T else 'left on the device', ctx.base_surfaces_ms()), t0)
+    for k in ('T', 'nsites', 'nshared', 'tmax', 'lin') if want_T else ('nsites', 'nshared', 'tmax', 'lin'):
+        _rot_equal(res[k], short[k], '%s base_surfaces %s' % (name, k))
+    assert want_T or res['T'] is None
+
+
 def _influence_seam(name, scene, block, chunks=2):
     sc, calls = _case(name)
     call = [c for c in calls if c.op == 'influence' and c.kw['block'] == block][0]
@@ -335,6 +367,14 @@ def test_bytes_seam_cond_surfaces():
 
 def test_bytes_seam_cond_surfaces_three_chunks_without_T():
     _cond_seam('bytes', 'bytes', False)
+
+
+def test_bytes_seam_base_surfaces():
+    _base_seam('bytes', 'bytes', True)
+
+
+def test_bytes_seam_base_surfaces_three_chunks_without_T():
+    _base_seam('bytes', 'bytes', False)
 
 
 def test_threads_seam_surfaces():
