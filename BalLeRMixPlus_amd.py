@@ -16,13 +16,23 @@ def _prewarm():
         pass
 
 
+_warm = None
 if __name__ == '__main__' and len(sys.argv) > 1 and not any(a in sys.argv for a in ('--getSpect', '--getConfig', '-h', '--help')):
-    threading.Thread(target=_prewarm, daemon=True).start()
+    _warm = threading.Thread(target=_prewarm, daemon=True)
+    _warm.start()
 
 from ballermixplus_amd.cli import main  # noqa: E402
 
 if __name__ == '__main__':
-    main()
+    try:
+        main()
+    except BaseException:
+        # An early way out (a refusal of the arguments and its sys.exit(1), an uncaught exception) can end the run within
+        # milliseconds, while the helper thread is still inside the HIP runtime's start-up; the interpreter then tore the process
+        # down under it (once seen as a SIGSEGV after the refusal was printed).  Wait for the thread, then leave as before.
+        if _warm is not None:
+            _warm.join()
+        raise
     # Every output file is written, closed and (multi-process runs) the process group destroyed by now.  Tearing down the HIP
     # runtime and Python takes ~0.1 s of a 0.75 s run on a 1M-SNP file; BMX_FAST_EXIT=0 keeps the orderly shutdown.
     sys.stdout.flush()

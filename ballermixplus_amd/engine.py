@@ -84,6 +84,8 @@ class Context:
         _lib.check(self._L.bmx_ctx_create(C.byref(self._h), int(device)))
         self.device = int(device)
         self.M = 0
+        self.N = 0                   # (before set_sites / set_model the library refuses with BMX_E_STATE: the wrapper must get that far)
+        self.model, self.nA = None, 0
         self.slot = 0
         self._slot_M = {}
         self._locate_shape = {}      # slot -> (R, K) of its locate_begin
@@ -551,7 +553,8 @@ class Context:
     def _sided_surfaces(self, call, lists, n, want_T):
         """cond_surfaces' and base_surfaces' dict, filled by `call` (their entry point) on the list(s) of n entries."""
         m = self.model
-        out = {'T': np.empty((n, self.nA, len(m.x), len(m.abeta)), dtype=np.float64) if want_T else None,
+        nx, nab = (len(m.x), len(m.abeta)) if m is not None else (0, 0)        # (no model yet: the library answers BMX_E_STATE)
+        out = {'T': np.empty((n, self.nA, nx, nab), dtype=np.float64) if want_T else None,
                'nsites': np.empty((n, self.nA), dtype=np.int32), 'nshared': np.empty((n, self.nA), dtype=np.int32),
                'tmax': np.empty(n, dtype=np.float64), 'lin': np.empty(n, dtype=np.int32)}
         _lib.check(call(self._h, n, *lists, _lib.as_dp(out['T']) if want_T else None, _lib.as_ip(out['nsites']),
@@ -622,7 +625,7 @@ class Context:
 
     def refine_R(self, x, abeta):
         """R f64[table rows] at the off-grid point (x, abeta): the refinement's own arithmetic for every row of the model."""
-        R = np.empty(self.model.rows, dtype=np.float64)
+        R = np.empty(self.model.rows if self.model is not None else 0, dtype=np.float64)   # (no model yet: BMX_E_STATE)
         _lib.check(self._L.bmx_ctx_refine_R(self._h, float(x), float(abeta), _lib.as_dp(R)))
         return R
 

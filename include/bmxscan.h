@@ -292,7 +292,9 @@ int bmx_ctx_cond_surfaces_ms(bmx_ctx *c, double *ms);
  * cnt[N] (int32): under the accepted loci site i follows g (1 + d_i), and cnt_i of them reach it.
  * bmx_ctx_baseline_reset: allocates the two arrays for the slot's N sites, or zeroes them (d = 0.0, cnt = 0).  BMX_E_INVALID: a
  *   NULL context; BMX_E_STATE without sites.  bmx_ctx_set_sites, _resample_sites and _plant_sites on a slot (and a new model)
- *   drop its baseline: the calls below are then BMX_E_STATE until the next reset.
+ *   drop its baseline: the calls below are then BMX_E_STATE until the next reset.  Nothing else does: a baseline survives
+ *   bmx_ctx_set_tests, scans, bmx_ctx_permute_rows and bmx_ctx_restore_rows (and bmx_ctx_select_slot away and back), and each
+ *   locus keeps the d formed from the rows in force when it was added.
  * bmx_ctx_baseline_add: adds the locus "test site `test` held at the grid point lin = (iA_c * nx + ix_c) * nab + ia_c".  Its sites
  *   are the surfaces' sites at A_c: max(win_lo, 0) <= i <= min(win_hi, N - 1), z_i = A_c * |g_i - tc| <= bmx_alpha_cut() (that
  *   single product), g_i != tc.  Each of them gets

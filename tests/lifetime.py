@@ -9,8 +9,12 @@ Models (name: table, pairs, slices, A values, table rows, row index width):
     g1       gridshape 'small', fixX / fixAlpha, one A                1 x 1 x 1
     l2       gridshape 'large' (150, 160, 170), (5, 13), 2 A          483 rows: the table is read from L2, the <., false> kernels
     w4       resamplers.table('t90831'), 2 x 2 pairs, 2 A             90 831 rows: 4-byte row indices
+    w729     offgrid's 'wide729' and its 'wideA' grid, 3 x 3, 2 A     729 rows: the first whose refinement workspace is in the slab
 HAND_MODELS is the order of the hand-written script: pairs 9 -> 1037 -> 1 -> 65 -> 4 -> 9, slices 1 -> 17 -> 1 -> 2 -> 1, A values
-4 -> 3 -> 1 -> 2 -> 2 -> 4, rows 21 -> 483 -> 90 831 -> 21, row width 2 -> 4 -> 2 bytes: each goes up and down.
+4 -> 3 -> 1 -> 2 -> 2 -> 4, rows 21 -> 483 -> 90 831 -> 21, row width 2 -> 4 -> 2 bytes: each goes up and down.  w729 (HAND_TAIL)
+follows in a last segment of its own and in the newest walks; its chromosomes are wide729's 1 500 sites ('M', 'L') and their first
+500 ('S').  It is the one table on which the compass kernels and sandwich_kernel all work in rf_slab and are cheap (w4 is left out
+of the off-grid searches).
 
 Chromosomes of every model: 'S' 700, 'M' 4 003 (w4: 4 000) and 'L' 12 009 (12 000) sites, position ties as gridshape.POS_TIES (the
 gridshape ones: the first 700 sites of gridshape.chromosome, the chromosome itself, and three seeds of it laid end to end).  Test
@@ -23,10 +27,22 @@ points and cond_surfaces' conditioning sites and grid points follow fixed spread
 admissible weights (capped at 1: fit_gw), cls fit.classes and edges fit.default_edges of the op's (F, D) out of FIT_SHAPES.  On
 w4 (221 sample sizes) F = 7 and F = 10 keep fit's prologue sums in the workspace in device memory, everything else in LDS.
 
-Scripts: the hand-written one and five seeded walks.  The three walks of OLD_WALK_SEEDS were drawn before fit and cond_surfaces had
+The baseline calls (group 'baseline': baseline_reset, baseline_add, baseline_fetch, base_surfaces) and the sandwich calls (group
+'sandwich': sandwich, refine_R).  Slot.bl is the baseline's history: None, or the loci added since the last reset, each with the
+test site (tg, lo, hi) it was formed from, its grid point and the slot's permutation at the time; drop_sites() alone clears it
+(set_sites, resample_sites and plant_sites into the slot, set_model), drop_tests(), permute_rows and restore_rows do not.
+baseline_add spreads its two plain numbers over the test sites and the grid's points (baseline_locus; 'M' and 'top' are the bad
+forms); base_surfaces lists as surfaces does.  sandwich lists as surfaces does, at one point per entry (sandwich_points: a grid
+point by the spread rule, then eval_point's off-grid point inside the hull, alternating), with a block out of SANDWICH_BLOCKS (1
+and 7: a thread per block; 64 and 10 ** 6: a wave per block); its bad forms are block = 0, hx = 0, x = HX / 2 and an index M.  The
+workspace of sandwich_kernel is the refinement's: in LDS up to 728 table rows, in rf_slab on w729 and w4 (ws_in_lds).
+
+Scripts: the hand-written one and seven seeded walks.  The three walks of OLD_WALK_SEEDS were drawn before fit and cond_surfaces had
 ops and stay op for op what they were (walk() draws them from _WEIGHTS); the two of NEW_WALK_SEEDS draw from _NEW_WEIGHTS, which
-weights the two new ops 3 each.  The hand-written script keeps its earlier ops in order, the new ones are inserted
-(tests/test_lifetime_cpu.py pins both with a sha256).
+weights those two ops 3 each, and stay what they were as well; the two of LIST_WALK_SEEDS draw from _LIST_WEIGHTS, which also
+weights the six baseline and sandwich ops, and go on to the baseline a scanned slot lacks at BASELINE_RATE.  The hand-written script
+keeps its earlier ops in order: the new ones are inserted and the segment on w729 stands behind them all
+(tests/test_lifetime_cpu.py pins all six earlier scripts with a sha256).
 
 An op is (name, {argument: plain value}); every array an op needs is derived from its plain arguments and the state by the
 functions at the end of this module, so that a script is a list of small tuples that can be compared and printed.
@@ -35,8 +51,9 @@ import numpy as np
 
 import gridshape as gs
 import resamplers as rs
+import offgrid as og
 
-from ballermixplus_amd import locate, null, power
+from ballermixplus_amd import locate, null, power, sandwich
 
 INVALID, LIMIT, STATE = -1, -4, -5
 NAN = 'nan'                      # a NaN argument, spelt so that two scripts compare equal; float() of it is the NaN
@@ -65,6 +82,8 @@ GROUPS = {
     'surfaces': ('surfaces', 'influence'),
     'fit': ('fit',),
     'conditional': ('cond_surfaces',),
+    'baseline': ('baseline_reset', 'baseline_add', 'baseline_fetch', 'base_surfaces'),
+    'sandwich': ('sandwich', 'refine_R'),
     'locate': ('resample_sites', 'locate_begin', 'locate_accumulate', 'fetch_locate'),
     'plant': ('plant_sites', 'fetch_at'),
     'pack_records': ('pack_records',),
@@ -80,9 +99,15 @@ LISTS = (1, 3, 40)
 FIT_SHAPES = ((1, 1), (7, 6), (10, 25))          # (F, D) of a fit call: on w4 the last two keep their sums in the workspace home
 FIT_LDS_BYTES = 40 << 10                         # BMX_FIT_LDS_BYTES: n_sizes * (F + 1) * 24 bytes of sums fit LDS up to here
 FIT_BAD = ('F', 'lin', 'gw')                     # F = 0, lin = nA * npairs, gw[0] = 1.5: all BMX_E_INVALID
+SANDWICH_BLOCKS = (1, 7, 64, 10 ** 6)             # a sandwich call's block: the first two a thread per block, the others a wave
+SANDWICH_WAVE_BLOCK = 64                         # SANDWICH_WAVE_BLOCK of bmxscan.hip
+SANDWICH_BAD = ('block', 'hx', 'x', 'index')     # block = 0, hx = 0, x = HX / 2, an index M: all BMX_E_INVALID
+BASELINE_BAD = ('test', 'lin')                   # test = M, lin = nA * npairs: both BMX_E_INVALID
+REFINE_LDS_WS = 32 << 10                         # REFINE_LDS_WS: a workspace of (rows * 45 + 15) // 16 * 16 bytes is in LDS up to here
 STRIDES = (1, 5, 20)
 WINDOWS = ('all', 'ragged')
 MAX_SLOTS = 4096
+ANCHOR_SLOT = MAX_SLOTS - 1      # no script selects it: the GPU module builds its base_surfaces anchor there, at the checkpoints
 COST_CAP = 3e9
 # the off-grid searches build the selection probabilities of every candidate point over all table rows: with 90 831 rows a
 # refinement of a hundred windows takes seconds (tests/test_gpu_offgrid.py has that table); the scripts leave them out there
@@ -91,6 +116,7 @@ SLOW_OFFGRID = ('w4',)
 # ------------------------------------------------------------------------------------------------ worlds
 LENGTHS = {'S': 700, 'M': gs.N, 'L': 3 * gs.N}
 W4_LENGTHS = {'S': 700, 'M': 4000, 'L': 12000}
+W729_LENGTHS = {'S': 500, 'M': og.WIDE_N, 'L': og.WIDE_N}          # offgrid's 1 500 sites and their first 500
 DENSE_M = gs.DENSE_M
 MODEL_SPECS = {
     'g3x3': ('small', (3, 3), gs.A_LIST),
@@ -98,8 +124,11 @@ MODEL_SPECS = {
     'g1': ('small', (1, 1), (5000.0,)),
     'l2': ('large', (5, 13), (5000.0, 30000.0)),
     'w4': ('t90831', (2, 2), rs.NULL_AS),
+    'w729': ('wide729', (3, 3), og.GRIDS['wideA'][2]),
 }
+SCAN_WORLDS = ('g3x3', 'g17x61', 'g1', 'l2', 'w4')       # the worlds of the earlier scripts: three chromosomes of rising length each
 HAND_MODELS = ('g3x3', 'g17x61', 'g1', 'l2', 'w4', 'g3x3')
+HAND_TAIL = 'w729'               # the model of the hand-written script's last segment, appended after the earlier ops
 _WORLDS = {}
 
 
@@ -114,6 +143,7 @@ class World:
         if data == 't90831':
             t = rs.table(data)
             self.model, self.xs, self.abetas = t.model, list(rs.XS), list(rs.ABETAS)
+            self.neutral = (t.sizes, t.spect, t.props)              # (sample sizes, spectrum, shares): what util.oracle_R takes
             for c, n in W4_LENGTHS.items():
                 gen, rows = t.sites(n, 3)
                 gen = gen.copy()
@@ -121,10 +151,19 @@ class World:
                     if j + 1 < n:
                         gen[j + 1] = gen[j]
                 self.chroms[c] = (_frozen(gen), _frozen(np.asarray(rows, dtype=np.int32)))
+        elif data == 'wide729':
+            d = og.dataset(data)
+            self.xs, self.abetas = list(og.GRIDS['wideA'][0]), list(og.GRIDS['wideA'][1])
+            self.model = engine.ModelArrays('B2', 1, d.sizes, d.spect, d.props, self.xs, self.abetas)
+            self.neutral = (d.sizes, d.spect, d.props)
+            rows = np.asarray(og.rows_of(data), dtype=np.int32)
+            self.chroms['S'] = (_frozen(d.gen[:W729_LENGTHS['S']]), _frozen(rows[:W729_LENGTHS['S']]))
+            self.chroms['M'] = self.chroms['L'] = (_frozen(d.gen), _frozen(rows))
         else:
             self.xs, self.abetas = gs.x_grid(shape[0]), gs.abeta_grid(shape[1])
             spect, props = gs.spectrum(data)
             self.model = engine.ModelArrays('B2', 1, gs.sizes_of(data), spect, props, self.xs, self.abetas)
+            self.neutral = (gs.sizes_of(data), spect, props)
             parts, at = [], 0.0
             for j in range(3):
                 gen, k, nn = gs.chromosome(data, gs.SEED + j)
@@ -217,6 +256,40 @@ def fit_in_lds(w, F):
     return len(w.model.sizes) * (F + 1) * 24 <= FIT_LDS_BYTES
 
 
+def spread(j, n):
+    """The fixed spread rule of index_list and fit_lins for one plain number j: an index into n things."""
+    return (int(j) * 7919 + 5) % max(int(n), 1)
+
+
+def baseline_locus(a, M, points):
+    """(test, lin) of a baseline_add op: its plain numbers spread over the M test sites and the grid's points; the bad forms
+    'M' and 'top' are the first index past either."""
+    return (M if a['test'] == 'M' else spread(a['test'], M)), (points if a['lin'] == 'top' else spread(a['lin'], points))
+
+
+def sandwich_points(w, kind):
+    """(A, x, abeta) f64[kind] of a sandwich call: the even entries a grid point by the spread rule, the odd ones eval_point's
+    off-grid point inside the hull (the grid point itself where a grid has one value, as on g1)."""
+    lin = (np.arange(kind, dtype=np.int64) * 7919 + 5) % (w.nA * w.nx * w.nab)
+    pts = np.array([(w.As[l // (w.nx * w.nab)], w.xs[(l // w.nab) % w.nx], w.abetas[l % w.nab]) for l in lin.tolist()], dtype=np.float64)
+    pts[1::2] = eval_point(w)
+    return pts[:, 0].copy(), pts[:, 1].copy(), pts[:, 2].copy()
+
+
+def refine_ws(rows):
+    """Bytes of the workspace of refine_kernel, support_kernel, boot_kernel and sandwich_kernel (refine_workspace's expression)."""
+    return (rows * 45 + 15) // 16 * 16
+
+
+def ws_in_lds(w):
+    return refine_ws(w.model.rows) <= REFINE_LDS_WS
+
+
+def list_cost(w, N, windows, kind):
+    """COST_CAP's product for a call that lists `kind` of the slot's windows (base_surfaces, sandwich)."""
+    return float(kind) * (N if windows == 'all' else 2 * gs.RAGGED_R) * w.cost
+
+
 def track_of(n, seed):
     """A caller's track for peaks_track: n rows, non-decreasing positions with ties, values with exact ties and zeros."""
     rng = np.random.default_rng([77, n, seed])
@@ -263,6 +336,8 @@ class Slot:
         self.scan = None         # the last scan's description (results exist), see State.describe
         self.pl = 0              # the profiles the last scan computed
         self.rf = self.sp = self.bt = self.pk = self.null = self.lc = None
+        self.bl = None           # the baseline: None, or the loci added since the last reset, each {'tg', 'lo', 'hi', 'lin', 'perm'}:
+        #                          the locus' test site as it was, its grid point and the slot's permutation when it was added
 
     def rows_now(self):
         g = self.sites['given']
@@ -272,8 +347,8 @@ class Slot:
         self.tests = self.scan = self.rf = self.sp = self.bt = self.pk = self.null = None
         self.pl = 0
 
-    def drop_sites(self):
-        self.sites = self.perm = None
+    def drop_sites(self):                # (the one place that drops the baseline; drop_tests, permute and restore do not)
+        self.sites = self.perm = self.bl = None
         self.drop_tests()
 
     @property
@@ -543,6 +618,49 @@ class State:
             return STATE
         return INVALID if a.get('bad') else 0
 
+    # ---- the baseline of accepted loci: the slot's own, dropped with its sites alone
+    def _baseline_reset(self, a, commit):
+        if self.slot.sites is None:
+            return STATE
+        if commit:
+            self.slot.bl = []
+        return 0
+
+    def _baseline_add(self, a, commit):
+        s = self.slot
+        if not self.ready() or s.bl is None:
+            return STATE
+        w = self.w
+        test, lin = baseline_locus(a, s.M, w.nA * w.nx * w.nab)
+        if test >= s.M or lin >= w.nA * w.nx * w.nab:
+            return INVALID
+        if commit:
+            t = s.tests
+            s.bl = s.bl + [{'tg': float(t['tg'][test]), 'lo': None if t['lo'] is None else int(t['lo'][test]),
+                            'hi': None if t['hi'] is None else int(t['hi'][test]), 'lin': lin, 'perm': s.perm}]
+        return 0
+
+    def _baseline_fetch(self, a, commit):
+        return STATE if self.slot.sites is None or self.slot.bl is None else 0
+
+    def _base_surfaces(self, a, commit):
+        if not self.ready() or self.slot.bl is None:
+            return STATE
+        return INVALID if a.get('bad') else 0
+
+    # ---- sandwich, refine_R: list_ready's rule after the call's own block and steps; they commit nothing
+    def _sandwich(self, a, commit):
+        if a['block'] < 1 or not a.get('hx', sandwich.HX) > 0.0:
+            return INVALID
+        if not self.ready():
+            return STATE
+        return INVALID if a.get('bad') else 0
+
+    def _refine_R(self, a, commit):
+        if not self.ready():
+            return STATE
+        return 0 if 0.0 < a['x'] < 1.0 and a['abeta'] > 0.0 else INVALID
+
     # ---- derived sites
     def _source(self, a):
         """(code, source slot) of resample_sites / plant_sites' src argument, before their own argument checks."""
@@ -659,22 +777,51 @@ def _prepare(chrom, stride, windows):
     return [op('set_sites', chrom=chrom), op('set_tests', stride=stride, windows=windows), op('scan')]
 
 
+# after a call that drops the slot's baseline: each of the three is BMX_E_STATE until the next baseline_reset
+_REFUSED_BASELINE = [op('baseline_add', test=0, lin=0), op('baseline_fetch'), op('base_surfaces', kind=1, want_T=True)]
+EMPTY_LOCUS = 1                  # spread(1, 801) = 715: a ragged window of the 'M' chromosome's every-5th test sites with lo > hi
+
+
 def hand_script():
     """The required transitions, in the order of their list where the state allows it (tests/test_lifetime_cpu.py finds each one
-    in the script itself); the fit and cond_surfaces ops (transition 13) stand among the surfaces and influence calls of 9. and 2."""
+    in the script itself); the fit and cond_surfaces ops (transition 13) stand among the surfaces and influence calls of 9. and 2.,
+    the baseline and sandwich ops (14. to 22.) are inserted where the earlier ops bring the state they need about."""
     K1, K2 = 0x1234567890ABCDEF, 0x0FEDCBA987654321
     s = [op('scan'), op('set_sites', chrom='S'), op('scan_write', chunk=0), op('restore_rows'), op('null_begin'), op('eval_points'),
          op('fetch_peaks'),                                                          # all refused: nothing is set
+         op('baseline_reset'), op('sandwich', kind=1, block=1), op('refine_R', x=0.31, abeta=7.0),
          op('set_model', model='g3x3'),
-         op('fit', kind=1, F=1, D=1), op('cond_surfaces', kind=1, want_T=True)]         # refused: no sites yet
+         op('fit', kind=1, F=1, D=1), op('cond_surfaces', kind=1, want_T=True),         # refused: no sites yet
+         op('baseline_add', test=0, lin=0), op('baseline_fetch'), op('base_surfaces', kind=1, want_T=True), op('sandwich', kind=3, block=7)]
     # 1. one slot long -> short -> medium, M large -> small -> larger
-    s += _prepare('L', 5, 'all') + _prepare('S', 20, 'ragged') + _prepare('M', 5, 'ragged')
+    #    17. a baseline at each length, fetched; 15. set_sites meets the long one: add, fetch and base_surfaces refuse until the reset
+    s += _prepare('L', 5, 'all') + [op('baseline_fetch'), op('baseline_reset'), op('baseline_add', test=2, lin=5), op('baseline_fetch'),
+                                    op('base_surfaces', kind=3, want_T=True), op('sandwich', kind=3, block=64)]
+    s += _prepare('S', 20, 'ragged') + _REFUSED_BASELINE + [op('baseline_reset'), op('base_surfaces', kind=3, want_T=False),
+                                                            op('baseline_add', test=1, lin=3), op('baseline_fetch')]
+    s += _prepare('M', 5, 'ragged') + [op('baseline_reset'), op('baseline_fetch')]
+    # 14. the plain chain (two loci on one test site: cnt = 2), then one locus whose window is empty: it writes nothing
+    #     22. a refused op directly before a compared one of its group
+    s += [op('baseline_reset'), op('baseline_add', test=7, lin=0), op('baseline_add', test=7, lin=1), op('base_surfaces', kind=40, want_T=True),
+          op('base_surfaces', kind=1, want_T=False), op('baseline_fetch'), op('baseline_reset'), op('baseline_fetch'),
+          op('baseline_add', test='M', lin=0), op('baseline_add', test=7, lin=2), op('baseline_add', test=0, lin='top'),
+          op('baseline_add', test=EMPTY_LOCUS, lin=4), op('base_surfaces', kind=3, want_T=True, bad=True), op('base_surfaces', kind=3, want_T=True),
+          op('baseline_add', test=9, lin=7)]
+    #     16. that baseline (three loci, one of them empty) now meets scans, set_profiles and set_variant
     # 3. the same test sites under profiles 0 -> 7 -> 1 -> 0 and variants 0 -> 12 -> 0 (and the LIMIT refusal in between)
     s += [op('set_profiles', which=7), op('scan'), op('fetch_profile', which=2), op('set_profiles', which=1), op('scan'),
           op('fetch_profile', which=4), op('set_variant', variant=12), op('set_profiles', which=8), op('scan'),
           op('set_profiles', which=0), op('scan'), op('set_variant', variant=16), op('scan'), op('set_variant', variant=0), op('scan')]
+    s += [op('base_surfaces', kind=3, want_T=True), op('baseline_fetch'),
+          # 19. the plain sandwich chain on a model in LDS, all four blocks; 22. each refusal directly before a compared call
+          op('sandwich', kind=40, block=1), op('sandwich', kind=1, block=7), op('sandwich', kind=3, block=0), op('sandwich', kind=1, block=64),
+          op('sandwich', kind=3, block=7, hx=0.0), op('sandwich', kind=40, block=10 ** 6), op('sandwich', kind=3, block=7, bad='x'),
+          op('sandwich', kind=3, block=7), op('sandwich', kind=3, block=64, bad='index'), op('sandwich', kind=3, block=64),
+          op('refine_R', x=1.0, abeta=7.0), op('refine_R', x=0.31, abeta=7.0)]
     # 10. scan_write on a small M, on a larger M in another slot, then a plain scan of the first
+    #     17. a second slot with a baseline of another length (700 sites against slot 0's 4 003)
     s += [op('select_slot', slot=1), op('set_sites', chrom='S'), op('set_tests', stride=20, windows='all'), op('scan_write', chunk=64),
+          op('baseline_reset'), op('baseline_add', test=3, lin=8), op('baseline_add', test=4, lin=20), op('base_surfaces', kind=3, want_T=True),
           op('select_slot', slot=2), op('set_sites', chrom='M'), op('set_tests', stride=1, windows='all'), op('scan_write', chunk=1000),
           op('select_slot', slot=1), op('scan'), op('set_variant', variant=12), op('set_profiles', which=2), op('scan_write', chunk=64),
           op('set_profiles', which=0), op('scan_write', chunk=0), op('set_variant', variant=0)]
@@ -682,20 +829,28 @@ def hand_script():
     s += [op('pack_records'), op('select_slot', slot=MAX_SLOTS), op('select_slot', slot=2), op('set_tests', stride=5, windows='ragged'), op('pack_records', short=True),
           op('pack_records'), op('scan')]
     # 4. permute -> scan -> resample and plant into other slots from the permuted source -> restore -> scan
-    s += [op('select_slot', slot=0), op('set_tests', stride=5, windows='all'), op('scan'), op('permute_rows', key=K1, block=0),
-          op('permute_rows', key=K1, block=7), op('scan'),
-          op('select_slot', slot=1), op('resample_sites', src=1, key=K2, block=5), op('resample_sites', src=0, key=K2, block=5),
-          op('set_tests', stride=5, windows='all'), op('scan'),
+    #    16. slot 0's baseline after set_tests, on permuted rows (a locus is added there) and restored ones; 21. sandwich on both
+    #    15. resample_sites into slot 1 drops its baseline, the source's (slot 0) is unchanged
+    s += [op('select_slot', slot=0), op('baseline_fetch'), op('base_surfaces', kind=1, want_T=True),
+          op('set_tests', stride=5, windows='all'), op('base_surfaces', kind=3, want_T=True), op('scan'), op('permute_rows', key=K1, block=0),
+          op('permute_rows', key=K1, block=7), op('base_surfaces', kind=3, want_T=True), op('sandwich', kind=3, block=7),
+          op('baseline_add', test=11, lin=30), op('scan'),
+          op('select_slot', slot=1), op('resample_sites', src=1, key=K2, block=5), op('resample_sites', src=0, key=K2, block=5)]
+    s += _REFUSED_BASELINE + [op('baseline_reset'),
+          op('set_tests', stride=5, windows='all'), op('base_surfaces', kind=3, want_T=True), op('scan'),
           op('select_slot', slot=3), op('plant_sites', src=0, key=K2, K=2, iA=4, ix=0, ia=0),
           op('plant_sites', src=0, key=K2, K=2, iA=3, ix=1, ia=2), op('set_tests', stride=20, windows='all'), op('scan'),
           op('fetch_at', kind=40, bad=True), op('fetch_at', kind=40),
-          op('select_slot', slot=0), op('restore_rows'), op('scan')]
+          op('select_slot', slot=0), op('baseline_fetch'), op('restore_rows'), op('base_surfaces', kind=3, want_T=True),
+          op('sandwich', kind=3, block=7), op('baseline_fetch'), op('scan')]
     # 5. two null runs on one slot, the second with fewer replicates; then set_tests and a third
     s += [op('null_accumulate'), op('null_begin'), op('null_accumulate')]
     for r in range(3):
         s += [op('permute_rows', key=K1 + r, block=3), op('scan'), op('null_accumulate')]
     s += [op('null_fetch'), op('restore_rows'), op('scan'), op('null_begin'), op('permute_rows', key=K2, block=1), op('scan'),
-          op('null_accumulate'), op('null_fetch'), op('restore_rows'), op('set_tests', stride=20, windows='ragged'), op('null_fetch'),
+          op('null_accumulate'), op('null_fetch'), op('restore_rows'), op('set_tests', stride=20, windows='ragged'),
+          op('base_surfaces', kind=3, want_T=False), op('baseline_add', test=13, lin=17), op('base_surfaces', kind=1, want_T=True),  # 16.
+          op('null_fetch'),
           op('scan'), op('null_begin'), op('permute_rows', key=K2 + 1, block=2), op('scan'), op('null_accumulate'), op('null_fetch'),
           op('restore_rows')]
     # 6. a locate run K x R fully accumulated, then a smaller one in which one replicate is never accumulated
@@ -708,33 +863,48 @@ def hand_script():
           op('locate_accumulate', r=2), op('locate_accumulate', r=1), op('fetch_locate')]
     # 7. refine -> new scan on permuted rows -> support / boot refuse, fetch_refined still answers -> refine -> support -> boot
     s += [op('select_slot', slot=0), op('set_tests', stride=20, windows='ragged'), op('scan'), op('fetch_refined'), op('refine', min_clr=2.0),
+          op('sandwich', kind=3, block=1),                                                                  # 20. between the compass calls
           op('support', drop=1.0, min_clr=60.0), op('fetch_support'), op('permute_rows', key=K1, block=4), op('scan'),
           op('support', drop=1.0, min_clr=60.0), op('boot', key=K2, R=3, block=8, min_clr=60.0), op('fetch_refined'), op('fetch_support'),
-          op('fetch_boot'), op('refine', min_clr=NAN), op('refine', min_clr=2.0), op('support', drop=0.0, min_clr=60.0),
-          op('support', drop=1.0, min_clr=60.0), op('fetch_support'), op('boot', key=K2, R=3, block=0, min_clr=60.0),
-          op('boot', key=K2, R=3, block=8, min_clr=60.0), op('fetch_boot'), op('eval_points'), op('eval_points_weighted', key=K1, block=0),
+          op('fetch_boot'), op('refine', min_clr=NAN), op('refine', min_clr=2.0), op('sandwich', kind=1, block=64), op('support', drop=0.0, min_clr=60.0),
+          op('support', drop=1.0, min_clr=60.0), op('sandwich', kind=3, block=7), op('fetch_support'), op('boot', key=K2, R=3, block=0, min_clr=60.0),
+          op('boot', key=K2, R=3, block=8, min_clr=60.0), op('sandwich', kind=40, block=10 ** 6), op('fetch_boot'), op('eval_points'),
+          op('eval_points_weighted', key=K1, block=0),
           op('eval_points_weighted', key=K1, block=6), op('restore_rows')]
     # 8. peaks -> refine_at_peaks -> scan -> refine refuses; a peaks_track of another length does not count; peaks -> refine
     s += [op('scan'), op('peaks', sep=2e-4, min_clr=1.0, frac=0.0), op('peaks', **PEAKS), op('fetch_peaks'), op('refine_at_peaks', on=True),
           op('scan'), op('refine', min_clr=0.0), op('peaks_track', n=300, seed=1, sep=NAN, min_clr=1.0, frac=0.5),
           op('peaks_track', n=300, seed=1, **PEAKS), op('fetch_peaks'), op('refine', min_clr=0.0),
-          op('peaks', **PEAKS), op('refine', min_clr=0.0), op('fetch_refined'), op('refine_at_peaks', on=False)]
+          op('peaks', **PEAKS), op('refine', min_clr=0.0), op('sandwich', kind=3, block=7), op('fetch_refined'), op('refine_at_peaks', on=False)]
     # 9. surfaces and influence with 40 windows, then 1, then again after every change of the model's shape
     #    13. fit and cond_surfaces with 40 windows, then 1, directly after surfaces and influence calls with longer and shorter lists
-    s += [op('surfaces', kind=40), op('fit', kind=1, F=7, D=6), op('influence', kind=40, block=50), op('cond_surfaces', kind=1, want_T=True),
-          op('fit', kind=40, F=10, D=25), op('cond_surfaces', kind=40, want_T=True),
-          op('surfaces', kind=1, bad=True), op('surfaces', kind=1), op('cond_surfaces', kind=40, want_T=False), op('fit', kind=1, F=1, D=1),
+    #    18. base_surfaces directly after each of the four with a longer and with a shorter list
+    s += [op('surfaces', kind=40), op('fit', kind=1, F=7, D=6), op('base_surfaces', kind=40, want_T=True),
+          op('influence', kind=40, block=50), op('cond_surfaces', kind=1, want_T=True), op('base_surfaces', kind=3, want_T=False),
+          op('fit', kind=40, F=10, D=25), op('base_surfaces', kind=1, want_T=True), op('cond_surfaces', kind=40, want_T=True),
+          op('base_surfaces', kind=3, want_T=True),
+          op('surfaces', kind=1, bad=True), op('surfaces', kind=1), op('base_surfaces', kind=40, want_T=False),
+          op('cond_surfaces', kind=40, want_T=False), op('fit', kind=1, F=1, D=1),
           op('influence', kind=3, block=0), op('influence', kind=1, block=50), op('fit', kind=40, F=1, D=1), op('fit', kind=3, F=0, D=6),
           op('fit', kind=3, F=7, D=6), op('fit', kind=3, F=7, D=6, bad='lin'), op('fit', kind=1, F=10, D=25), op('fit', kind=40, F=7, D=6, bad='gw'),
           op('cond_surfaces', kind=3, want_T=True, bad=True), op('cond_surfaces', kind=1, want_T=False), op('cond_surfaces', kind=3, want_T=True)]
     # 2. the models, each with a scan (and the 4-byte rows between two scans on 2-byte rows); every other slot's sites are gone
     for m in HAND_MODELS[1:]:
-        s += [op('set_model', model='bad'), op('set_model', model=m), op('select_slot', slot=2), op('set_tests', stride=5, windows='all'),
+        #    15. set_model meets slot 0's baseline; 14. and 19. the plain chains again under every model; 21. refine_R across it
+        s += [op('refine_R', x=0.31, abeta=7.0), op('set_model', model='bad'), op('set_model', model=m)] + _REFUSED_BASELINE
+        s += [op('select_slot', slot=2), op('set_tests', stride=5, windows='all'),
               op('select_slot', slot=0)]
-        s += _prepare('M', 1, 'ragged') + [op('surfaces', kind=40), op('cond_surfaces', kind=3, want_T=False),
-                                          op('influence', kind=40, block=64), op('fit', kind=3, F=1, D=1),
+        s += _prepare('M', 1, 'ragged') + [op('baseline_reset'), op('baseline_add', test=2, lin=0), op('baseline_add', test=3, lin=1),
+                                          op('surfaces', kind=40), op('cond_surfaces', kind=3, want_T=False),
+                                          op('base_surfaces', kind=40, want_T=m != 'g17x61'),
+                                          op('influence', kind=40, block=64), op('base_surfaces', kind=1, want_T=m == 'g17x61'),
+                                          op('fit', kind=3, F=1, D=1),
                                           op('influence', kind=1, block=64), op('cond_surfaces', kind=40, want_T=True),
                                           op('fit', kind=40, F=7, D=6), op('fit', kind=1, F=10, D=25), op('cond_surfaces', kind=1, want_T=False),
+                                          op('baseline_fetch'), op('baseline_reset'), op('baseline_fetch'), op('baseline_add', test=5, lin=2),
+                                          op('refine_R', x=0.31, abeta=7.0),
+                                          op('sandwich', kind=40, block=1), op('sandwich', kind=1, block=7), op('sandwich', kind=1, block=64),
+                                          op('sandwich', kind=40, block=10 ** 6),
                                           op('select_slot', slot=1)] + _prepare('S', 5, 'all')
         s += [op('set_profiles', which=4), op('permute_rows', key=K1, block=2), op('scan'), op('fetch_profile', which=1),
               op('fetch_profile', which=4), op('set_profiles', which=0)]
@@ -746,21 +916,47 @@ def hand_script():
               op('select_slot', slot=4), op('select_slot', slot=MAX_SLOTS), op('resample_sites', src=1, key=K2, block=3),
               op('set_tests', stride=20, windows='all'), op('scan_write', chunk=0), op('peaks', **PEAKS), op('pack_records'),
               op('select_slot', slot=0)]
-    return s
+    return s + _hand_tail(K1, K2)
+
+
+def _hand_tail(K1, K2):
+    """The last segment, on the 729-row table: the smallest whose workspace leaves LDS, so that the compass kernels and
+    sandwich_kernel meet in rf_slab (20.), and the one place where plant_sites meets a baseline (15.).  It stands after every
+    earlier op; tests/test_lifetime_cpu.py cuts the script at its set_model before it takes the sha256."""
+    t = [op('refine_R', x=0.31, abeta=7.0), op('set_model', model=HAND_TAIL)] + _REFUSED_BASELINE
+    t += _prepare('M', 20, 'all') + [op('refine_R', x=0.31, abeta=7.0), op('baseline_reset'), op('baseline_add', test=1, lin=1),
+                                       op('baseline_add', test=2, lin=2), op('base_surfaces', kind=40, want_T=True),
+                                       op('base_surfaces', kind=1, want_T=False), op('baseline_fetch'), op('baseline_reset'),
+                                       op('baseline_fetch'), op('baseline_add', test=1, lin=1), op('baseline_add', test=2, lin=2)]
+    t += [op('refine', min_clr=5.0), op('sandwich', kind=40, block=1), op('fetch_refined'), op('support', drop=1.0, min_clr=60.0),
+          op('sandwich', kind=1, block=7), op('fetch_support'), op('boot', key=K1, R=2, block=16, min_clr=60.0),
+          op('sandwich', kind=1, block=64), op('fetch_boot'), op('eval_points'), op('sandwich', kind=40, block=10 ** 6), op('eval_points'),
+          op('permute_rows', key=K2, block=9), op('sandwich', kind=3, block=7), op('restore_rows'), op('sandwich', kind=3, block=7)]
+    t += [op('select_slot', slot=1), op('set_sites', chrom='S'), op('baseline_reset'), op('baseline_add', test=0, lin=0), op('baseline_fetch'),
+          op('set_tests', stride=5, windows='all'), op('baseline_add', test=0, lin=0), op('baseline_fetch'),
+          op('plant_sites', src=0, key=K2, K=0, iA=1, ix=1, ia=1)] + _REFUSED_BASELINE
+    t += [op('baseline_reset'), op('set_tests', stride=20, windows='all'), op('base_surfaces', kind=3, want_T=True), op('scan'),
+          op('select_slot', slot=0), op('baseline_fetch'), op('base_surfaces', kind=3, want_T=True), op('scan')]
+    return t
 
 
 OLD_WALK_SEEDS = (20261101, 20261102, 20261103)               # drawn before fit and cond_surfaces had ops: they stay what they were
 NEW_WALK_SEEDS = (20261105, 20261110)                         # drawn from the table that also weights the two (the first two seeds
 #                                                               after the earlier ones whose walk has both ops succeed twice, one of
 #                                                               them on the workspace home of w4; tests/test_lifetime_cpu.py asserts it)
-WALK_SEEDS = OLD_WALK_SEEDS + NEW_WALK_SEEDS
+LIST_WALK_SEEDS = (20261506, 20266493)                        # drawn from the table that also weights the baseline and sandwich ops: the first seed
+#                                                               after the earlier ones, for either tuple of LIST_WALK_MODELS, whose walk has all
+#                                                               six succeed twice (tests/test_lifetime_cpu.py asserts it)
+WALK_SEEDS = OLD_WALK_SEEDS + NEW_WALK_SEEDS + LIST_WALK_SEEDS
 NEW_OPS = ('fit', 'cond_surfaces')
+LIST_OPS = GROUPS['baseline'] + GROUPS['sandwich']
 WALK_LENGTH = 88
 WALK_SLOTS = (0, 1, 2)
 WALK_MODELS = {20261101: ('g3x3', 'l2', 'g1', 'g17x61'), 20261102: ('w4', 'g3x3', 'g17x61', 'l2'), 20261103: ('g17x61', 'g1', 'w4', 'g3x3'),
                20261105: ('w4', 'g1', 'l2', 'g17x61'), 20261110: ('g1', 'w4', 'g3x3', 'l2')}
 BAD_SHARE = 0.07                 # deliberately bad arguments; refusals by state come on top (kept with probability KEEP_REFUSED)
 KEEP_REFUSED = 0.3
+BASELINE_RATE = 0.4             # how often the newest walks turn to the baseline a scanned slot lacks, then to its first locus
 
 _WEIGHTS = {'set_sites': 4, 'set_tests': 6, 'select_slot': 6, 'set_variant': 3, 'set_profiles': 4, 'fetch_profile': 5, 'scan': 14,
             'scan_write': 3, 'permute_rows': 4, 'restore_rows': 2, 'null_begin': 2, 'null_accumulate': 3, 'null_fetch': 2, 'refine': 4,
@@ -769,6 +965,16 @@ _WEIGHTS = {'set_sites': 4, 'set_tests': 6, 'select_slot': 6, 'set_variant': 3, 
             'resample_sites': 3, 'locate_begin': 2, 'locate_accumulate': 3, 'fetch_locate': 2, 'plant_sites': 3, 'fetch_at': 3,
             'pack_records': 3}
 _NEW_WEIGHTS = dict(_WEIGHTS, fit=3, cond_surfaces=3)
+_LIST_WEIGHTS = dict(_NEW_WEIGHTS, baseline_reset=2, baseline_add=4, base_surfaces=3, baseline_fetch=2, sandwich=3, refine_R=1)
+LIST_WALK_MODELS = (('g3x3', 'w729', 'w4', 'g17x61'), ('w4', 'g1', 'w729', 'l2'))       # of LIST_WALK_SEEDS, in their order
+
+
+def _listed_kinds(st):
+    """The list lengths of a base_surfaces or sandwich op that COST_CAP's product allows on the selected slot's windows."""
+    s = st.slot
+    if s.sites is None or s.tests is None:
+        return LISTS
+    return tuple(k for k in LISTS if list_cost(st.w, len(s.sites['gen']), s.tests['windows'], k) <= COST_CAP) or LISTS[:1]
 
 
 def _draw(rng, st, name):
@@ -824,6 +1030,17 @@ def _draw(rng, st, name):
         return op(name, kind=pick(LISTS), F=0 if how == 'F' else F, D=D, **({'bad': how} if how in ('lin', 'gw') else {}))
     if name == 'cond_surfaces':
         return op(name, kind=pick(LISTS), want_T=bool(pick((True, False))), **({'bad': True} if bad else {}))
+    if name == 'baseline_add':
+        how = pick(BASELINE_BAD) if bad else None
+        return op(name, test='M' if how == 'test' else int(rng.integers(6)), lin='top' if how == 'lin' else int(rng.integers(50)))
+    if name == 'base_surfaces':
+        return op(name, kind=pick(_listed_kinds(st)), want_T=bool(pick((True, False))), **({'bad': True} if bad else {}))
+    if name == 'sandwich':
+        how = pick(SANDWICH_BAD) if bad else None
+        return op(name, kind=pick(_listed_kinds(st)), block=0 if how == 'block' else pick(SANDWICH_BLOCKS), **({'hx': 0.0} if how == 'hx' else {}),
+                  **({'bad': how} if how in ('x', 'index') else {}))
+    if name == 'refine_R':
+        return op(name, x=1.0 if bad else pick((0.31, 0.07)), abeta=pick((7.0, 300.0)))
     if name == 'resample_sites':
         return op(name, src=st.cur if bad else pick(others), key=key, block=pick((1, 5, 64)))
     if name == 'plant_sites':
@@ -845,9 +1062,9 @@ def walk(seed, length=WALK_LENGTH):
     selected slot lacks (sites, test sites, a scan) preferred, refusals kept at about one op in eight."""
     rng = np.random.default_rng([20261023, seed])
     st = State(R_of=lambda m: None)
-    table = _WEIGHTS if seed in OLD_WALK_SEEDS else _NEW_WEIGHTS
+    table = _WEIGHTS if seed in OLD_WALK_SEEDS else _NEW_WEIGHTS if seed in NEW_WALK_SEEDS else _LIST_WEIGHTS
     names, weights = list(table), np.array(list(table.values()), dtype=np.float64)
-    models = WALK_MODELS[seed]
+    models = WALK_MODELS[seed] if seed in WALK_MODELS else LIST_WALK_MODELS[LIST_WALK_SEEDS.index(seed)]
     ops = []
     while len(ops) < length:
         due = models[min(len(ops) * len(models) // length, len(models) - 1)]
@@ -861,6 +1078,10 @@ def walk(seed, length=WALK_LENGTH):
             name = lack if lack and rng.random() < 0.75 else names[int(rng.choice(len(names), p=weights / weights.sum()))]
             if name in ('refine', 'support', 'boot') and st.model in SLOW_OFFGRID:
                 continue
+            # the newest walks go on to the baseline a scanned slot lacks and to its first locus, at a lower rate (the earlier
+            # walks never come here: their random numbers are what they were)
+            if table is _LIST_WEIGHTS and lack is None and (s.bl is None or not s.bl) and rng.random() < BASELINE_RATE:
+                name = 'baseline_reset' if s.bl is None else 'baseline_add'
             new = _draw(rng, st, name)
         code = st.predict(new)
         if code and new[0] != 'set_model' and not (new[1].get('bad') or rng.random() < KEEP_REFUSED or _is_bad(new)):
@@ -874,7 +1095,7 @@ def _is_bad(o):
     a = o[1]
     return (a.get('block') == 0 or a.get('R') == 0 or a.get('stride') == 0 or a.get('chrom') == 'bad' or a.get('slot') == MAX_SLOTS
             or a.get('which') == 8 or a.get('F') == 0 or a.get('frac') == 0.0 or a.get('drop') == 0.0 or a.get('short')
-            or NAN in a.values())
+            or NAN in a.values() or a.get('hx') == 0.0 or a.get('test') == 'M' or a.get('lin') == 'top' or a.get('x') == 1.0)
 
 
 def scripts():

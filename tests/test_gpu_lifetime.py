@@ -15,7 +15,24 @@ Every test runs one script in ONE engine.Context that is closed only at the end.
     the windows), CLR within rtol 1e-9 / atol 1e-12 on every window -- so that the two contexts cannot be wrong together.  At the
     same checkpoints its fit and cond_surfaces of a 3-entry list are compared with fit.host_fit and
     conditional.host_cond_surface on the device's own table, at those features' tolerances (fitcases.TOL * max(1, n_d) per cell,
-    condcases.REL_TOL of the conditional scale; integer fields exact).
+    condcases.REL_TOL of the conditional scale; integer fields exact), and its sandwich of a 3-entry list with
+    sandwich.host_sandwich on the device's own five columns (Context.refine_R at sandwich.shifted_points; sandwichcases.TOL of |T|
+    and of the sums of absolute terms, the counts exact).
+  * the baseline calls (baseline_reset, _add, _fetch, base_surfaces): the clean room takes the model and the sites as given, resets
+    and replays the loci the state model recorded, each under the permutation and on the single test site it was added with, then
+    sets the permutation and the test sites of now and runs the op; d, cnt, baseline_add's three numbers and every array of
+    base_surfaces are compared as bytes.  Every baseline_fetch is also compared with stepwise.host_baseline_add on the device's
+    table (stepcases.D_TOL of each site's absolute increments, cnt exact).  At the three checkpoints of every script the
+    long-lived context's base_surfaces of a 3-entry list after two adds is compared with stepwise.host_base_surface on the
+    device's table (stepcases.REL_TOL of the scale; integer fields exact): a live baseline cannot be reset without changing its
+    history, so this happens in lifetime.ANCHOR_SLOT, a slot of the same context that no script selects, on the checkpoint's
+    sites and test sites.  Where a script itself calls base_surfaces with T on two loci or more (the hand-written one does, under
+    every model; no walk does), the first two such calls under every model are compared in the same way, the list's first three
+    entries, against the host's replay of the recorded history.
+  * around every successful baseline or sandwich op the selected slot's scan results and, where the state model says they exist,
+    fetch_refined, fetch_support and fetch_boot must be what they were; around a refused baseline op so must baseline_fetch; after
+    every op one OTHER slot that holds a baseline has it fetched again.  The same sandwich call on permuted and on restored rows
+    must differ.
 """
 import collections
 import time
@@ -27,13 +44,16 @@ import condcases as cc
 import fitcases as fc
 import gridshape as gs
 import lifetime as lt
+import sandwichcases as swc
+import stepcases as stc
 from util import c_oracle, c_scan
 
-from ballermixplus_amd import conditional, fit
+from ballermixplus_amd import conditional, fit, null, sandwich, stepwise
 
 pytestmark = pytest.mark.gpu
 
 ANCHOR_FIT = (7, 6)                  # (F, D) of the fit compared with host_fit at the checkpoints
+ANCHOR_BLOCK = 7                     # block of the sandwich compared with host_sandwich there
 
 
 def _zcut():
@@ -124,6 +144,9 @@ class Runner:
         self.plans, self.kernels, self.wide_scans, self.anchors = set(), set(), 0, []
         self.rooms, self.t_rooms, self.t_anchors = 0, 0.0, 0.0
         self.slow = collections.Counter()    # (op, model) -> seconds, the op and its clean room together
+        self.bl_snap, self.bl_rot, self.bl_refetched = {}, 0, 0        # slot -> _bytes of its baseline after its last baseline op
+        self.bl_hosted, self.bl_most, self.bs_anchors, self.sw_anchors, self.base_anchors = 0, 0, [], [], []
+        self.untouched, self.sw_seen, self.sw_last, self.sw_perm_pairs = 0, set(), {}, 0
 
     # ---- the arrays of an op, from its plain arguments and the state BEFORE it
     def args(self, o):
@@ -168,6 +191,22 @@ class Runner:
             if a.get('bad'):
                 ct[-1] = s.M
             return {'list': v, 'ct': ct, 'cl': cl}
+        if name == 'baseline_add':
+            test, lin = lt.baseline_locus(a, s.M, w.nA * w.nx * w.nab) if w else (0, 0)
+            return {'test': test, 'lin': lin}
+        if name == 'base_surfaces':
+            v = lt.index_list(a['kind'], s.M)
+            if a.get('bad'):
+                v[-1] = s.M
+            return {'list': v}
+        if name == 'sandwich':
+            v = lt.index_list(a['kind'], s.M)
+            A, x, ab = lt.sandwich_points(w or lt.world('g1'), a['kind'])
+            if a.get('bad') == 'x':
+                x[-1] = sandwich.HX / 2
+            if a.get('bad') == 'index':
+                v[-1] = s.M
+            return {'list': v, 'A': A, 'x': x, 'ab': ab}
         if name == 'plant_sites':
             src = st.slots.get(a['src'])
             have = src is not None and src.sites is not None and 0 <= a['iA'] < w.nA if w else False
@@ -267,6 +306,19 @@ class Runner:
             return ctx.fit(g['list'], g['lin'], g['gw'], g['cls'], a['F'], g['edges'])
         if name == 'cond_surfaces':
             return ctx.cond_surfaces(g['list'], g['ct'], g['cl'], want_T=a['want_T'])
+        if name == 'baseline_reset':
+            ctx.baseline_reset()
+            return ctx.baseline_fetch(N)
+        if name == 'baseline_add':
+            return ctx.baseline_add(g['test'], g['lin']), ctx.baseline_fetch(N)
+        if name == 'baseline_fetch':
+            return ctx.baseline_fetch(N or 0)
+        if name == 'base_surfaces':
+            return ctx.base_surfaces(g['list'], want_T=a['want_T'])
+        if name == 'sandwich':
+            return ctx.sandwich(g['list'], g['A'], g['x'], g['ab'], a['block'], hx=a.get('hx'))
+        if name == 'refine_R':
+            return ctx.refine_R(a['x'], a['abeta'])
         if name == 'resample_sites':
             n = ctx.resample_sites(a['src'], a['key'], a['block'])
             return n, (ctx.fetch_sites(n) if n else None)
@@ -316,6 +368,75 @@ class Runner:
         self._to_perm(room, rf['scan']['perm'], rf['perm'])
         room.refine(float(rf['min_clr']))
 
+    def _based(self, room, o):
+        """A fresh context up to the selected slot's baseline: the model, the sites as they were given, a reset, then every recorded
+        locus under the permutation it was added under and on its single test site (the locus of a baseline_add op, the last, is
+        left to the op itself); then the permutation and the test sites of now."""
+        st, s = self.st, self.st.slot
+        room.set_model(st.w.model, st.w.As)
+        room.set_sites(s.sites['gen'], s.sites['given'])
+        have = None
+        if o[0] != 'baseline_reset':
+            room.baseline_reset()
+            for l in (s.bl[:-1] if o[0] == 'baseline_add' else s.bl):
+                self._to_perm(room, have, l['perm'])
+                have = l['perm']
+                one = lambda v: None if v is None else np.array([v], dtype=np.int64)
+                room.set_tests(np.array([l['tg']]), one(l['lo']), one(l['hi']))
+                room.baseline_add(0, l['lin'])
+        self._to_perm(room, have, s.perm)
+        if s.tests is not None:
+            room.set_tests(s.tests['tg'], s.tests['lo'], s.tests['hi'])
+
+    def host_baseline(self):
+        """(d, cnt, scale) of the selected slot's recorded baseline by stepwise.host_baseline_add on the device's own table; scale:
+        each site's sum of absolute increments."""
+        st, s = self.st, self.st.slot
+        w, gen, given, R = st.w, s.sites['gen'], s.sites['given'], device_table(st.model)
+        d, cnt, scale = np.zeros(len(gen)), np.zeros(len(gen), dtype=np.int32), np.zeros(len(gen))
+        for l in s.bl:
+            rows = given if l['perm'] is None else given[null.block_permutation(len(given), *l['perm'])]
+            stepwise.host_baseline_add(d, cnt, gen, rows, R, l['tg'], 0 if l['lo'] is None else l['lo'], len(gen) - 1 if l['hi'] is None else l['hi'],
+                                       w.As[l['lin'] // (w.nx * w.nab)], (l['lin'] // w.nab) % w.nx, l['lin'] % w.nab, _zcut(), scale=scale)
+        return d, cnt, scale
+
+    def anchor_baseline(self, i, o, got):
+        """A baseline_fetch against the host's replay of the record (stepcases.D_TOL of each site's absolute increments, the counts
+        exact); a 3-entry base_surfaces on two loci or more against stepwise.host_base_surface (stepcases.REL_TOL of the scale)."""
+        st, s = self.st, self.st.slot
+        if o[0] == 'baseline_fetch':
+            dh, ch, scale = self.host_baseline()
+            assert np.array_equal(got[1], ch), (i, o)
+            err = np.abs(got[0] - dh)
+            assert np.all(err <= stc.D_TOL * scale), (i, o, float(np.max(err[scale > 0] / scale[scale > 0])))
+            self.bl_hosted += 1
+            self.bl_most = max(self.bl_most, int(ch.max(initial=0)))
+        elif o[1]['kind'] >= 3 and o[1]['want_T'] and len(s.bl) >= 2 and sum(m == st.model for _, m, _, _ in self.bs_anchors) < 2:
+            dh, ch, _ = self.host_baseline()                # (the first two such calls under every model; the list's first three entries)
+            w, gen, rows, t, R = st.w, s.sites['gen'], s.rows_now(), s.tests, device_table(st.model)
+            worst = 0.0
+            for q, j in enumerate(lt.index_list(o[1]['kind'], s.M)[:3].tolist()):
+                lo, hi = (0, len(gen) - 1) if t['lo'] is None else (t['lo'][j], t['hi'][j])
+                Th, nh, sh, S = stepwise.host_base_surface(gen, rows, R, w.As, t['tg'][j], lo, hi, dh, ch, _zcut(), scale=True)
+                assert np.array_equal(got['nsites'][q], nh) and np.array_equal(got['nshared'][q], sh), (i, q)
+                assert np.array_equal(np.isnan(got['T'][q]), np.isnan(Th)), (i, q)
+                if (nh > 0).any():
+                    worst = max(worst, float(np.nanmax(np.abs(got['T'][q] - Th))) / (stc.REL_TOL * float(S.max())))
+            assert worst <= 1.0, (i, worst)
+            self.bs_anchors.append((i, st.model, len(s.bl), worst))
+
+    def held(self):
+        """What a baseline or sandwich call must leave alone in the selected slot: its scan results and, where the state model
+        says they exist, its refinement, support intervals and bootstrap."""
+        st, s, out = self.st, self.st.slot, {'scan': self.fetch_now()}
+        if s.rf is not None:
+            out['refined'] = _bytes(self.ctx.fetch_refined())
+        if st.predict(lt.op('fetch_support')) == 0:
+            out['support'] = _bytes(self.ctx.fetch_support())
+        if st.predict(lt.op('fetch_boot')) == 0:
+            out['boot'] = _bytes(self.ctx.fetch_boot())
+        return out
+
     def clean(self, o, g):
         """What a context created for this one comparison returns for op o (the state is the one AFTER the op)."""
         name, a = o
@@ -326,6 +447,9 @@ class Runner:
         kw = dict(N=N, M=s.M, profiles=st.profiles, tag='room')
         try:
             if name in ('set_model', 'peaks_track'):
+                return self.do(room, o, g, **kw)
+            if name in lt.GROUPS['baseline']:
+                self._based(room, o)
                 return self.do(room, o, g, **kw)
             if name == 'fetch_peaks' and s.pk['kind'] == 'track':
                 t = lt.track_of(*s.pk['track'])
@@ -400,7 +524,8 @@ class Runner:
             elif name == 'set_variant':
                 self._setup(room, dict(d, variant=0))
             else:
-                assert name in ('scan', 'scan_write', 'surfaces', 'influence', 'fit', 'cond_surfaces', 'eval_points', 'eval_points_weighted'), name
+                assert name in ('scan', 'scan_write', 'surfaces', 'influence', 'fit', 'cond_surfaces', 'eval_points', 'eval_points_weighted',
+                                'sandwich', 'refine_R'), name
                 self._setup(room, d)
             return self.do(room, o, g, **kw)
         finally:
@@ -449,7 +574,43 @@ class Runner:
             assert np.array_equal(got[q][keep], ref[q][keep]), (i, q, np.nonzero(got[q] != ref[q])[0][:8])
         assert np.allclose(got[0], ref[0], rtol=1e-9, atol=1e-12), (i, worst)
         self.anchor_listed(i, w, gen, rows, t['tg'], lo, hi)
+        self.anchor_base(i, w, gen, rows, t, lo, hi)
         self.anchors.append(i)
+
+    def anchor_base(self, i, w, gen, rows, t, lo, hi):
+        """base_surfaces of a 3-entry list after two adds against stepwise.host_base_surface on the device's table
+        (stepcases.REL_TOL of the scale, integer fields exact; the adds' three numbers against stepwise.host_baseline_add).  A live
+        baseline cannot be reset without changing its history, so the long-lived context does this in lt.ANCHOR_SLOT, which no
+        script selects: the checkpoint's sites (the rows as they are now) and test sites are set there, and no recorded slot is
+        touched."""
+        st, ctx = self.st, self.ctx
+        R, zcut, M, points, npairs = device_table(st.model), _zcut(), len(t['tg']), w.nA * w.nx * w.nab, w.nx * w.nab
+        v = lt.index_list(3, M)
+        dh, ch = np.zeros(len(gen)), np.zeros(len(gen), dtype=np.int32)
+        ctx.select_slot(lt.ANCHOR_SLOT)
+        try:
+            ctx.set_sites(gen, rows)
+            ctx.set_tests(t['tg'], t['lo'], t['hi'])
+            ctx.baseline_reset()
+            for k, j in enumerate(v[:2].tolist()):
+                lin = lt.spread(k, points)
+                got = ctx.baseline_add(j, lin)
+                want = stepwise.host_baseline_add(dh, ch, gen, rows, R, t['tg'][j], lo[j], hi[j], w.As[lin // npairs], (lin // w.nab) % w.nx, lin % w.nab, zcut)
+                assert got == want if want[2] else (got[0] > got[1] and got[2] == 0), (i, k, got, want)
+            res = ctx.base_surfaces(v)
+        finally:
+            ctx.select_slot(st.cur)
+        worst = 0.0
+        for q, j in enumerate(v.tolist()):
+            Th, nh, sh, S = stepwise.host_base_surface(gen, rows, R, w.As, t['tg'][j], lo[j], hi[j], dh, ch, zcut, scale=True)
+            assert np.array_equal(res['nsites'][q], nh) and np.array_equal(res['nshared'][q], sh), (i, q)
+            assert np.array_equal(np.isnan(res['T'][q]), np.isnan(Th)), (i, q)
+            if (nh > 0).any():
+                worst = max(worst, float(np.nanmax(np.abs(res['T'][q] - Th))) / (stc.REL_TOL * float(S.max())))
+        assert worst <= 1.0, (i, worst)
+        self.base_anchors.append((i, int(ch.sum()), int(res['nshared'].sum()), worst))
+        print('  base_surfaces anchor at op %d: two loci on %d sites, %d shared sites in the three windows, worst %.2e of stepcases.REL_TOL x scale'
+              % (i, int(ch.sum()), int(res['nshared'].sum()), worst))
 
     def anchor_listed(self, i, w, gen, rows, tg, lo, hi):
         """The long-lived context's fit and cond_surfaces of a 3-entry list against the host restatements on the device's table."""
@@ -486,6 +647,22 @@ class Runner:
                 worst_cond = max(worst_cond, float(np.nanmax(np.abs(res['T'][q] - Th))) / (cc.REL_TOL * float(S.max())))
         assert worst_cond <= 1.0, (i, worst_cond)
         print('  listed anchor at op %d: fit (F %d, D %d) worst %.2e of its bound, cond_surfaces worst %.2e of its tolerance' % (i, F, D, worst_fit, worst_cond))
+        # sandwich of a 3-entry list against host_sandwich on the device's own five columns: tests/test_gpu_sandwich.py's bar and scales
+        pA, px, pab = lt.sandwich_points(w, 3)
+        got = self.ctx.sandwich(v, pA, px, pab, ANCHOR_BLOCK)
+        worst_sw = 0.0
+        for q, j in enumerate(v.tolist()):
+            tabs = np.array([self.ctx.refine_R(xx, aa) for xx, aa in sandwich.shifted_points(px[q], pab[q])])
+            h = sandwich.host_sandwich(gen, rows, tabs, pA[q], tg[j], lo[j], hi[j], ANCHOR_BLOCK, zcut=zcut)
+            assert (got['nsites'][q], got['nskipped'][q], got['nblocks'][q]) == (h['nsites'], h['nskipped'], h['nblocks']), (i, q)
+            if h['nsites'] == h['nskipped']:
+                assert got['T'][q] == -np.inf and not got['g'][q].any() and not got['H'][q].any() and not got['J'][q].any(), (i, q)
+                continue
+            for dev, ref, scale in [(got['T'][q], h['T'], abs(h['T']))] + [(got[k][q], h[k], h['abs' + k]) for k in ('g', 'H', 'J')]:
+                worst_sw = max(worst_sw, float(np.max(np.abs(dev - ref) / (swc.TOL * np.asarray(scale) + 1e-300))))
+        assert worst_sw <= 1.0, (i, worst_sw)
+        self.sw_anchors.append((i, int(got['nsites'].sum()), worst_sw))
+        print('  sandwich anchor at op %d: block %d, %d sites in the three windows, worst %.2e of sandwichcases.TOL x scale' % (i, ANCHOR_BLOCK, int(got['nsites'].sum()), worst_sw))
 
     def run(self, ops, anchors):
         st, ctx = self.st, self.ctx
@@ -498,20 +675,39 @@ class Runner:
             g = self.args(o)
             s = st.slot
             N = None if s.sites is None else len(s.sites['gen'])
+            listed = lt.GROUP_OF[name] in ('baseline', 'sandwich')
             if want:
                 before = self.fetch_now()
+                based = name in lt.GROUPS['baseline'] and s.sites is not None and s.bl is not None
+                bl_before = _bytes(ctx.baseline_fetch(N)) if based else None
                 with pytest.raises(self.BmxError) as e:
                     self.do(ctx, o, g, N=N, M=s.M, profiles=st.profiles)
                 assert e.value.code == want, (i, o, lt.CODE_NAMES[want], str(e.value))
                 assert self.fetch_now() == before, (i, o, 'a refused call changed the results')
+                assert not based or _bytes(ctx.baseline_fetch(N)) == bl_before, (i, o, 'a refused call changed the baseline')
                 self.refused[want] += 1
             else:
                 self.perm_before = s.perm
                 after_profiles = st.profiles
+                kept = self.held() if listed else None
                 got = self.do(ctx, o, g, N=N if name != 'plant_sites' else len(st.slots[a['src']].sites['gen']), M=s.M, profiles=after_profiles)
                 assert st.step(o) == 0
                 s = st.slot
                 self.host_sites(o, got)
+                if listed:
+                    assert self.held() == kept, (i, o, 'the call changed the results, the refinement, the support or the bootstrap')
+                    self.untouched += 1
+                if name in lt.GROUPS['baseline']:
+                    self.bl_snap[st.cur] = _bytes(ctx.baseline_fetch(N))
+                    if name in ('baseline_fetch', 'base_surfaces'):
+                        self.anchor_baseline(i, o, got)
+                if name == 'sandwich':
+                    self.sw_seen.add(('LDS' if lt.ws_in_lds(st.w) else 'slab', 'wave' if a['block'] >= lt.SANDWICH_WAVE_BLOCK else 'thread'))
+                    last = self.sw_last.get(st.cur)
+                    if last is not None and last[0] == o and last[1] is s.tests and (last[2] is None) != (s.perm is None) and got['nsites'].any():
+                        assert _bytes(got) != last[3], (i, o, 'the same answer on permuted and on restored rows')
+                        self.sw_perm_pairs += 1
+                    self.sw_last[st.cur] = (o, s.tests, s.perm, _bytes(got))
                 if name == 'select_slot':
                     if s.scan is not None:
                         assert _kept(self.snap[st.cur], _bytes(_results(ctx, s.pl))), (i, o)
@@ -547,6 +743,18 @@ class Runner:
                 assert _kept(self.snap[k], _bytes(_results(ctx, st.slots[k].pl))), (i, o, 'slot %d changed' % k)
                 ctx.select_slot(st.cur)
                 self.refetched += 1
+            # ... and one other slot that holds a baseline
+            for k in list(self.bl_snap):
+                if st.slots[k].bl is None:
+                    del self.bl_snap[k]
+            others = [k for k in sorted(self.bl_snap) if k != st.cur]
+            if others:
+                k = others[self.bl_rot % len(others)]
+                self.bl_rot += 1
+                ctx.select_slot(k)
+                assert _bytes(ctx.baseline_fetch(len(st.slots[k].sites['gen']))) == self.bl_snap[k], (i, o, 'the baseline of slot %d changed' % k)
+                ctx.select_slot(st.cur)
+                self.bl_refetched += 1
 
     def close(self):
         self.ctx.close()
@@ -580,8 +788,16 @@ def _run_script(name, tmp_path):
           % (name, len(ops), dt, run.t_rooms, run.t_anchors, run.rooms, dict(run.compared), {lt.CODE_NAMES[c]: n for c, n in run.refused.items()}, run.refetched,
              sorted(run.plans), run.wide_scans))
     print('  kernels: %s' % sorted(run.kernels))
+    print('  baseline ops compared %d, sandwich ops compared %d; %d baseline fetches against the host (largest cnt %d), base_surfaces anchors (op, model, loci, share of the tolerance) %s; '
+          'sandwich anchors (op, sites, share) %s; base_surfaces anchors at the checkpoints (op, sites written, shared sites, share) %s; %d ops left results, refinement, support and bootstrap as they were; %d re-fetches of another slot\'s baseline; '
+          'sandwich workspaces and block paths %s; %d sandwich pairs on permuted and restored rows'
+          % (run.compared['baseline'], run.compared['sandwich'], run.bl_hosted, run.bl_most, [(i, m, n, '%.1e' % x) for i, m, n, x in run.bs_anchors],
+             [(i, n, '%.1e' % x) for i, n, x in run.sw_anchors], [(i, n, k, '%.1e' % x) for i, n, k, x in run.base_anchors], run.untouched, run.bl_refetched, sorted(run.sw_seen), run.sw_perm_pairs))
     print('  slowest (op, model): %s' % ', '.join('%s/%s %.2f s' % (k[0], k[1], v) for k, v in run.slow.most_common(8)))
     assert len(run.anchors) >= 3 and max(run.anchors) > max(i for i, o in enumerate(ops) if o[0] == 'set_model')
+    # every script, the walks included: three sandwich and three base_surfaces anchors, one of either with sites to compare
+    assert len(run.sw_anchors) >= 3 and any(n > 0 for _, n, _ in run.sw_anchors), run.sw_anchors
+    assert len(run.base_anchors) >= 3 and any(n > 0 and shared > 0 for _, n, shared, _ in run.base_anchors), run.base_anchors
     return run
 
 
@@ -592,6 +808,12 @@ def test_hand_written_script(tmp_path):
     assert {(4, 16), (4, 8), (5, 1)} <= run.plans, run.plans
     assert any(k.endswith(',false>') or k.endswith('<false>') for k in run.kernels), run.kernels
     assert run.wide_scans >= 1
+    # the baseline and sandwich groups: both homes of the workspace and both block paths, a count of 2 on some site, three host
+    # anchors of either kind (one sandwich anchor with sites at least), the same call on permuted and restored rows
+    assert run.sw_seen == {(h, p) for h in ('LDS', 'slab') for p in ('thread', 'wave')}, run.sw_seen
+    assert run.bl_most >= 2 and run.bl_hosted >= 15 and run.bl_refetched >= 20
+    assert len(run.bs_anchors) >= 3 and {'w4', lt.HAND_TAIL} <= {m for _, m, _, _ in run.bs_anchors}, run.bs_anchors
+    assert run.sw_perm_pairs >= 2
 
 
 @pytest.mark.parametrize('seed', lt.WALK_SEEDS)
