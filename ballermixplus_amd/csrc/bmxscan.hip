@@ -3384,6 +3384,7 @@ struct FinalParams {
     double zcut;
     double *clr; int32_t *lin; int32_t *nsites;
     bmx_record *rec;   // the same three values as one 16-byte record per test site (what the multi-GPU gather moves)
+    int *over;         // the slot's range word: set to 1 where a winner's exponent sits at the clamp (its CLR is past the range)
 };
 
 // A winning key (mantissa, clamped exponent + 2^17) to its CLR: the one conversion of the scan's result and of every profile entry
@@ -3414,6 +3415,8 @@ __global__ void finalize_kernel(FinalParams F) {
     if (bL != 0x7fffffff) bT = key_clr(bM, bE);
     const bool none = (bL == 0x7fffffff);
     if (!none) {
+        // a winner AT the clamp (ec = 131071 + 2^17) may have been cut: its CLR, and its order among such grid points, is not known
+        if (bE >= 131071 + 131072) *F.over = 1;
         const double A = F.A[bL / F.npairs], tg = F.test_gen[t];
         const int64_t lo = max(F.win_lo[t], (int64_t)0), hi = min(F.win_hi[t], F.N - 1);
         // right of the test position: indices [a0, hi], predicate true on a prefix
@@ -5571,6 +5574,7 @@ struct ScanPlan {
 // A context holds ONE model and any number of slots (bmx_ctx_select_slot); a whole-genome run keeps every chromosome
 // resident and scans them back to back on the context's stream.
 struct ChromSlot {
+    int index = 0;               // the slot's number in its context
     // sites (grow-only buffers)
     bool has_sites = false;
     int64_t N = 0;
@@ -5742,7 +5746,7 @@ struct bmx_ctx {
     DevBuf<double> part_T;       // per-slice winners of one launch range
     DevBuf<int32_t> part_lin, part_ns;
     DevBuf<ScratchEnt> arena;    // prepared pipeline: the blobs of one launch range
-    int *d_status = nullptr;     // ... and its error bits
+    int *d_status = nullptr;     // ... and its error bits; behind them one range word per slot ([1 + slot index], finalize_kernel)
     DevBuf<double> surf_T;
     DevBuf<int32_t> surf_ns;
     // surfaces of a list of test sites (bmx_ctx_surfaces, _cond_surfaces, _base_surfaces): the list, one chunk's outputs (T and
@@ -5982,6 +5986,7 @@ int select_slot(bmx_ctx *c, int slot) {
     if ((size_t)slot >= c->slots.size()) c->slots.resize((size_t)slot + 1, nullptr);
     if (!c->slots[(size_t)slot]) {
         ChromSlot *s = new ChromSlot();
+        s->index = slot;
         if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) {
             s->release();
             delete s;
@@ -6155,7 +6160,8 @@ int bmx_ctx_create(bmx_ctx **out, int device) {
     for (int k = 0; ok && k < 2; k++)
         ok = hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&c->ev_copied[k], hipEventDisableTiming) == hipSuccess;
-    if (ok) ok = hipMalloc((void **)&c->d_status, sizeof(int)) == hipSuccess && hipMemset(c->d_status, 0, sizeof(int)) == hipSuccess;
+    if (ok) ok = hipMalloc((void **)&c->d_status, (1 + MAX_SLOTS) * sizeof(int)) == hipSuccess &&
+                 hipMemset(c->d_status, 0, (1 + MAX_SLOTS) * sizeof(int)) == hipSuccess;
     if (ok) ok = select_slot(c, 0) == BMX_OK;
     if (!ok) {
         bmx_ctx_destroy(c);
@@ -6783,6 +6789,7 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
     F.genpos = s->genpos.p; F.A = c->d_A; F.test_gen = P.test_gen; F.win_lo = P.win_lo; F.win_hi = P.win_hi;
     F.center = P.center; F.center_hi = P.center_hi; F.zcut = c->zcut;
     F.clr = s->clr.p + off; F.lin = s->lin.p + off; F.nsites = s->nsites.p + off; F.rec = s->rec.p + off;
+    F.over = c->d_status + 1 + s->index;
     const int fthreads = 256;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((cnt + fthreads - 1) / fthreads)), dim3(fthreads), 0, c->stream, F);
     HIP_TRY(hipGetLastError());
@@ -6826,13 +6833,27 @@ int scan_ranges(bmx_ctx *c, ChromSlot *s, std::vector<PrepRange> &out) {
     return BMX_OK;
 }
 
-// the device-side error bits of the prepared pipeline, checked wherever results leave the library
-int check_status(bmx_ctx *c) {
-    int st = 0;
-    HIP_TRY(hipMemcpy(&st, c->d_status, sizeof(int), hipMemcpyDeviceToHost));
-    if (st) {
+// before the launches of a scan of slot s: its range word starts at 0
+int begin_range_word(bmx_ctx *c, ChromSlot *s) {
+    HIP_TRY(hipMemsetAsync(c->d_status + 1 + s->index, 0, sizeof(int), c->stream));
+    return BMX_OK;
+}
+
+// the device-side error bits of the prepared pipeline, checked wherever results leave the library (the first reader clears them),
+// and with the same read the range word of slot s -- of every slot for s == nullptr -- where it holds scan results: a winner at
+// the exponent clamp is BMX_E_LIMIT every time, until that slot is scanned again
+int check_status(bmx_ctx *c, const ChromSlot *s) {
+    std::vector<int> st(1 + c->slots.size(), 0);
+    HIP_TRY(hipMemcpy(st.data(), c->d_status, st.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (st[0]) {
         HIP_TRY(hipMemset(c->d_status, 0, sizeof(int)));
-        return fail(BMX_E_HIP, st & 1 ? "prepared scan: a group's stream differs in size from the counting pass" : "prepared scan: bad zone header in a group's stream");
+        return fail(BMX_E_HIP, st[0] & 1 ? "prepared scan: a group's stream differs in size from the counting pass" : "prepared scan: bad zone header in a group's stream");
+    }
+    for (size_t i = 0; i < c->slots.size(); i++) {
+        const ChromSlot *q = c->slots[i];
+        if (q && (!s || s == q) && q->has_results() && st[1 + i])
+            return fail(BMX_E_LIMIT, "scan: a window of slot " + std::to_string(i) + " has a CLR past the scan's range (|T| <= 2 ln 2 x 131070 = 1.817e5 per "
+                                     "grid point): the slot's results are withheld until it is scanned again with narrower windows");
     }
     return BMX_OK;
 }
@@ -6850,6 +6871,7 @@ int bmx_ctx_scan(bmx_ctx *c) {
     int rc = scan_ranges(c, s, rs);
     if (rc) return rc;
     if ((rc = begin_profiles(c, s))) return rc;
+    if ((rc = begin_range_word(c, s))) return rc;
     HIP_TRY(hipEventRecord(s->ev0, c->stream));
     for (const PrepRange &r : rs)
         if ((rc = launch_range(c, s, s->plan, r.off, r.cnt, s->plan.mode >= 4 ? &r : nullptr))) return rc;
@@ -6921,7 +6943,7 @@ int bmx_ctx_sync(bmx_ctx *c) {
         if (tot > 0) for (int k = 0; k < 12; k++) fprintf(stderr, "[bmx prof] %-36s %5.1f %%\n", (prep_names ? np : nm)[k], 100.0 * (double)h[k] / tot);
     }
 #endif
-    return check_status(c);
+    return check_status(c, c->cur);
 }
 
 /* The records of every slot that holds scan results, in slot order, back to back: the whole genome's results with one
@@ -6935,6 +6957,8 @@ int bmx_ctx_pack_records(bmx_ctx *c, void *dst, int64_t cap, int32_t dst_on_devi
         if (s && s->has_results()) n += s->M;
     if (n_out) *n_out = n;
     if (n > cap) return fail(BMX_E_INVALID, "pack_records: destination too small");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int st = check_status(c, nullptr)) return st;        // before anything is copied: the destination may be another device's input
     int64_t at = 0;
     for (ChromSlot *s : c->slots) {
         if (!s || !s->has_results()) continue;
@@ -6943,7 +6967,7 @@ int bmx_ctx_pack_records(bmx_ctx *c, void *dst, int64_t cap, int32_t dst_on_devi
         at += s->M;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_status(c);
+    return BMX_OK;
 }
 
 int bmx_ctx_copy_records(bmx_ctx *c, void *dst_device, int64_t cap) {
@@ -6952,9 +6976,11 @@ int bmx_ctx_copy_records(bmx_ctx *c, void *dst_device, int64_t cap) {
     if (!s->has_results()) return fail(BMX_E_STATE, "no scan results in the selected slot");
     if (cap < s->M) return fail(BMX_E_INVALID, "copy_records: destination too small");
     HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int st = check_status(c, s)) return st;
     HIP_TRY(hipMemcpyAsync(dst_device, s->rec.p, (size_t)s->M * sizeof(bmx_record), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_status(c);
+    return BMX_OK;
 }
 
 int bmx_ctx_last_scan_ms(bmx_ctx *c, double *ms) {
@@ -6992,7 +7018,7 @@ int bmx_ctx_fetch_records(bmx_ctx *c, bmx_record *rec) {
     if (!s->has_results()) return fail(BMX_E_STATE, "no scan results to fetch");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int st = check_status(c)) return st;
+    if (int st = check_status(c, s)) return st;
     HIP_TRY(hipMemcpy(rec, s->rec.p, (size_t)s->M * sizeof(bmx_record), hipMemcpyDeviceToHost));
     return BMX_OK;
 }
@@ -7004,7 +7030,7 @@ int bmx_ctx_fetch(bmx_ctx *c, double *clr, int32_t *ix, int32_t *ia, int32_t *iA
     HIP_TRY(hipSetDevice(c->device));
     std::vector<int32_t> lin((size_t)s->M);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int st = check_status(c)) return st;
+    if (int st = check_status(c, s)) return st;
     HIP_TRY(download(clr, s->clr.p, (size_t)s->M));
     HIP_TRY(download(nsites, s->nsites.p, (size_t)s->M));
     HIP_TRY(hipMemcpy(lin.data(), s->lin.p, (size_t)s->M * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -7054,7 +7080,7 @@ int bmx_ctx_fetch_profile(bmx_ctx *c, int32_t which, double *out) {
     if (!s->has_results() || !(s->pl_have & which)) return fail(BMX_E_STATE, "the slot's last scan did not compute this profile");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int st = check_status(c)) return st;
+    if (int st = check_status(c, s)) return st;
     const int k = which == BMX_PL_A ? 0 : which == BMX_PL_X ? 1 : 2;
     const int n = k == 0 ? c->nA : k == 1 ? c->nx : c->nab;
     if (s->M) HIP_TRY(hipMemcpy(out, s->pl_out[k].p, (size_t)s->M * n * sizeof(double), hipMemcpyDeviceToHost));
@@ -7144,7 +7170,7 @@ int bmx_ctx_null_accumulate(bmx_ctx *c, double *max_out) {
     double m = 0.0;
     HIP_TRY(hipMemcpyAsync(&m, mx, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int st = check_status(c)) return st;      // the replicate's scan must have been sound (a stale prepared stream shows here)
+    if (int st = check_status(c, s)) return st;      // the replicate's scan must have been sound (a stale prepared stream shows here)
     s->null_seq = s->scan_seq;
     s->null_reps++;
     if (max_out) *max_out = m;
@@ -8111,7 +8137,7 @@ int bmx_ctx_locate_accumulate(bmx_ctx *c, int32_t r) {
                        (int)s->lc_K, s->lc_row.p + (size_t)r * s->lc_K, s->lc_clr.p + (size_t)r * s->lc_K);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int st = check_status(c)) return st;      // the replicate's scan must have been sound
+    if (int st = check_status(c, s)) return st;      // the replicate's scan must have been sound
     s->lc_seq = s->scan_seq;
     return BMX_OK;
 }
@@ -8556,6 +8582,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
     int rc = scan_ranges(c, s, rs);
     if (rc) return rc;
     if ((rc = begin_profiles(c, s))) return rc;
+    if ((rc = begin_range_word(c, s))) return rc;
     ScanPlan &pl = s->plan;
     // chunks: the prepared pipeline's launch ranges as they are (their blobs were sized per range); otherwise `chunk` test
     // sites at a time (0: 65536; whole workgroups, which keeps every result bit-identical to bmx_ctx_scan)
@@ -8653,7 +8680,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
         if (werr == 1) return fail(BMX_E_HIP, "streaming writer: waiting for a result copy failed");
         if (werr == 2) return fail(BMX_E_INVALID, std::string("streaming writer: ") + wmsg);
         if (wfail) return fail(BMX_E_INVALID, "write failed");
-        return check_status(c);
+        return check_status(c, s);
     };
 #define STREAM_TRY(expr)                                                                                  \
     do {                                                                                                  \

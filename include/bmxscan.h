@@ -33,7 +33,7 @@ enum {
     BMX_E_INVALID = -1,   /* bad argument (null pointer, size, unsorted positions, ...) */
     BMX_E_NODEVICE = -2,  /* no usable HIP device / device index out of range */
     BMX_E_HIP = -3,       /* a HIP runtime call failed; see bmx_last_error() */
-    BMX_E_LIMIT = -4,     /* a documented size limit was exceeded (2^24 LUT rows, 2^31 sites, 2^31 grid points) */
+    BMX_E_LIMIT = -4,     /* a documented limit was exceeded (2^24 LUT rows, 2^31 sites, 2^31 grid points, a CLR past the scan's range) */
     BMX_E_STATE = -5      /* call order violated (e.g. scan before model/sites were set) */
 };
 
@@ -148,9 +148,22 @@ int bmx_ctx_set_sites(bmx_ctx *c, int64_t N, const double *genpos, const int32_t
  * the bounds are then written on the device, nothing is copied. */
 int bmx_ctx_set_tests(bmx_ctx *c, int64_t M, const double *test_gen, const int64_t *win_lo,
                       const int64_t *win_hi);
-/* Launch the scan (K2 + argmax finalisation) on the context's stream; asynchronous. */
+/* Launch the scan (K2 + argmax finalisation) on the context's stream; asynchronous.
+ * CLR range: the scan compares grid points by the binary exponent E and the mantissa of the window's likelihood ratio and keeps
+ * E clamped to +-131071.  A winner AT the upper clamp may have been cut, so the argmax and the CLR are defined for E <= 131070,
+ * |T| <= 2 ln 2 x 131070 = 1.817e5 per (window, A, grid point).  If any window of a scan has its winner at the clamp, that
+ * slot's results are not handed out by the calls that return a scan: bmx_ctx_sync (on the selected slot), bmx_ctx_fetch, bmx_ctx_fetch_records,
+ * bmx_ctx_fetch_profile, bmx_ctx_pack_records (any slot it packs), bmx_ctx_copy_records, bmx_ctx_scan_write (the rows it
+ * appended are then not to be used), bmx_ctx_null_accumulate, bmx_ctx_locate_accumulate, bmx_scan and bmx_scan_multi return
+ * BMX_E_LIMIT naming the range -- every time, until the slot is scanned again; other slots are unaffected.  Below neutral the
+ * clamp is harmless: nothing with T <= 0 can win, and such a window comes out as "none" (clr +0.0, indices -1, nsites 0).
+ * The off-grid calls (surface, surfaces, eval_points, ...) are plain sums and have no such limit.
+ * NOT checked: bmx_ctx_result_ptrs and bmx_ctx_records (device addresses; nothing is read), and the calls that work on a
+ * finished scan of the selected slot -- bmx_ctx_fetch_at, bmx_ctx_peaks, bmx_ctx_refine and what is built on them.  They read
+ * the clamped clr / lin / nsites of a refused slot as they stand: call bmx_ctx_sync after the scan first, and go on only
+ * where it returns BMX_OK. */
 int bmx_ctx_scan(bmx_ctx *c);
-/* Block until the stream is idle. */
+/* Block until the stream is idle.  BMX_E_LIMIT if the selected slot's last scan left the CLR range (bmx_ctx_scan). */
 int bmx_ctx_sync(bmx_ctx *c);
 /* Milliseconds the last bmx_ctx_scan spent in the scan kernel(s), from HIP events
  * recorded on the context's stream (valid after bmx_ctx_sync). */
