@@ -48,6 +48,7 @@ PROTOTYPES = {
     'bmx_last_error': (C.c_char_p, []),
     'bmx_device_count': (C.c_int, []),
     'bmx_alpha_cut': (C.c_double, []),
+    'bmx_live_bytes': (None, [_lp, _lp]),
     'bmx_lut_build': (C.c_int, [C.POINTER(BmxModel), _dp, _dp, C.c_int]),
     'bmx_scan': (C.c_int, [C.POINTER(BmxModel), _dp, C.c_int32, C.c_int64, _dp, _ip, C.c_int64, _dp, _lp, _lp,
                            _dp, _ip, _ip, _ip, _ip, C.c_int]),

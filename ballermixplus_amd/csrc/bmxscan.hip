@@ -52,6 +52,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <type_traits>
 #include <string>
@@ -5447,12 +5448,6 @@ double compute_zcut() {
     return lo;
 }
 
-template <class T>
-void dfree(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 }  // namespace
 
 // -DBMX_DEVICE_PROBE=<kernel instantiation>: device code of that ONE kernel and nothing else (register / spill counts and the
@@ -5481,36 +5476,59 @@ extern "C" int bmx_tests_sorted_(int64_t M, const double *test_gen);
 // =================================================================================== ctx
 namespace {
 
-// Device buffer that only grows: set_sites / set_tests / surface of a long run (22 chromosomes, thousands of surfaces)
-// reuse their allocations instead of paying hipMalloc/hipFree per call.
-template <class T>
-struct DevBuf {
+// Bytes held by every DevBuf / PinnedBuf of the process (bmx_live_bytes)
+std::atomic<int64_t> g_device_bytes{0}, g_pinned_bytes{0};
+
+// What owns a device or host resource is never copied: contexts and slots live on the heap
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+
+// Device buffer that owns its allocation and only grows: set_sites / set_tests / surface of a long run (22 chromosomes,
+// thousands of surfaces) reuse their allocations instead of paying hipMalloc/hipFree per call.  Whoever holds one frees it
+// by going away; release() gives the memory back earlier.  PINNED: the same in pinned host memory.
+template <class T, bool PINNED = false>
+struct DevBuf : NoCopy {
     T *p = nullptr;
     size_t cap = 0;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t n) {
         if (n <= cap && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         const size_t want = std::max<size_t>(n, 1);
-        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+        hipError_t e = PINNED ? hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, want * sizeof(T));
         if (e == hipSuccess) cap = want;
+        live() += (int64_t)(cap * sizeof(T));
         return e;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        live() -= (int64_t)(cap * sizeof(T));
         p = nullptr;
         cap = 0;
     }
+    static std::atomic<int64_t> &live() { return PINNED ? g_pinned_bytes : g_device_bytes; }
 };
+using PinnedBuf = DevBuf<char, true>;   // ensure(bytes)
 
-// Device time of an interval on a stream; ms < 0: none measured yet.  The events are created on first use.
-struct DevTimer {
+// Device time of an interval on a stream; ms < 0: none measured yet.  The timer owns its two events, which begin() creates
+// on first use.
+struct DevTimer : NoCopy {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double ms = -1.0;
-    hipError_t begin(hipStream_t s) {
+    ~DevTimer() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    hipError_t create() {
         hipError_t e = ev0 ? hipSuccess : hipEventCreate(&ev0);
         if (e == hipSuccess && !ev1) e = hipEventCreate(&ev1);
+        return e;
+    }
+    hipError_t begin(hipStream_t s) {
+        const hipError_t e = create();
         return e == hipSuccess ? hipEventRecord(ev0, s) : e;
     }
     hipError_t end(hipStream_t s) { return hipEventRecord(ev1, s); }
@@ -5524,11 +5542,6 @@ struct DevTimer {
         if (ms < 0) return fail(BMX_E_STATE, none_yet);
         *out = ms;
         return BMX_OK;
-    }
-    void release() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        ev0 = ev1 = nullptr;
     }
 };
 
@@ -5600,7 +5613,7 @@ struct ChromSlot {
     DevBuf<double> clr;
     DevBuf<int32_t> lin, nsites;
     DevBuf<bmx_record> rec;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevTimer scan;               // the events around the last scan, created with the slot
     // plan of the scan, made once per (model, sites, tests, variant)
     bool plan_ok = false;
     int plan_variant = -1;
@@ -5700,23 +5713,6 @@ struct ChromSlot {
         release_support();
         release_boot();
     }
-    void release() {
-        genpos.release(); rowmax.release(); rowthr.release(); row16.release(); row32.release(); kmom.release(); d_row_of_slot.release();
-        orig16.release(); orig32.release(); null_obs.release(); null_part.release(); null_cnt.release();
-        test_gen.release(); win_lo.release(); win_hi.release(); center.release(); center_hi.release();
-        clr.release(); lin.release(); nsites.release(); rec.release();
-        blob_units.release(); blob_prefix.release();
-        for (auto &b : pl_out) b.release();
-        release_refined();
-        release_peaks();
-        lc_ok = false;
-        lc_lo.release(); lc_hi.release(); lc_row.release(); lc_clr.release();
-        bl_have = false;
-        bl_d.release(); bl_cnt.release();
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        ev0 = ev1 = nullptr;
-    }
 };
 
 struct bmx_ctx {
@@ -5729,24 +5725,24 @@ struct bmx_ctx {
     int stat = 0, min_count = 1, n_sizes = 0, rows = 0, nx = 0, nab = 0, npairs = 0, NP = 0, nslices = 0, nA = 0;
     int renorm_every = 16, span_hi = 1;
     double rmax = 0.0;
-    int32_t *d_sizes = nullptr, *d_row_off = nullptr;
-    double *d_g = nullptr, *d_prop = nullptr, *d_x = nullptr, *d_abeta = nullptr, *d_A = nullptr;
-    double *d_psel = nullptr, *d_R = nullptr, *d_Rt = nullptr;
+    DevBuf<int32_t> d_sizes, d_row_off;
+    DevBuf<double> d_g, d_prop, d_x, d_abeta, d_A;
+    DevBuf<double> d_psel, d_R, d_Rt;
     std::vector<double> h_A, h_rowmax;   // h_rowmax: [nslices][rows] max |R| (+inf: absent row)
-    uint64_t *d_patch_x = nullptr;
-    double *d_patch_y = nullptr;
+    DevBuf<uint64_t> d_patch_x;
+    DevBuf<double> d_patch_y;
     int n_patch = 0;
     std::vector<double> h_g;
     // chromosomes
-    std::vector<ChromSlot *> slots;      // slot 0 exists from creation; nullptr: never selected
+    std::vector<std::unique_ptr<ChromSlot>> slots;      // slot 0 exists from creation; empty: never selected
     ChromSlot *cur = nullptr;
     int cur_index = 0;
-    unsigned long long *d_prof = nullptr;   // -DBMX_PROFILE / -DBMX_COUNT builds
+    DevBuf<unsigned long long> d_prof;      // -DBMX_PROFILE / -DBMX_COUNT builds
     // scratch shared by the slots (launches of one context are serialised on its stream)
     DevBuf<double> part_T;       // per-slice winners of one launch range
     DevBuf<int32_t> part_lin, part_ns;
     DevBuf<ScratchEnt> arena;    // prepared pipeline: the blobs of one launch range
-    int *d_status = nullptr;     // ... and its error bits; behind them one range word per slot ([1 + slot index], finalize_kernel)
+    DevBuf<int> d_status;        // ... and its error bits; behind them one range word per slot ([1 + slot index], finalize_kernel)
     DevBuf<double> surf_T;
     DevBuf<int32_t> surf_ns;
     // surfaces of a list of test sites (bmx_ctx_surfaces, _cond_surfaces, _base_surfaces): the list, one chunk's outputs (T and
@@ -5812,9 +5808,18 @@ struct bmx_ctx {
     DevTimer pw;
     std::vector<double> h_x, h_ab;
     // pinned host staging of the streaming writer: two slots of (clr, lin, nsites)
-    void *h_stage[2] = {nullptr, nullptr};
-    size_t h_stage_cap = 0;
+    PinnedBuf h_stage[2];
     double zcut = 0;
+
+    // the handles that are no buffers; everything else frees itself
+    ~bmx_ctx() {
+        for (int k = 0; k < 2; k++) {
+            if (ev_done[k]) (void)hipEventDestroy(ev_done[k]);
+            if (ev_copied[k]) (void)hipEventDestroy(ev_copied[k]);
+        }
+        if (stream) (void)hipStreamDestroy(stream);
+        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    }
 };
 
 inline bool ChromSlot::ready_to_scan(const bmx_ctx *c) const { return c->has_model && has_sites && has_tests; }
@@ -5824,12 +5829,8 @@ inline bool ChromSlot::has_refinement_of_last_scan(const bmx_ctx *c) const {
 
 namespace {
 
-void free_model(bmx_ctx *c) {
-    dfree(c->d_sizes); dfree(c->d_row_off); dfree(c->d_g); dfree(c->d_prop); dfree(c->d_x);
-    dfree(c->d_abeta); dfree(c->d_A); dfree(c->d_psel); dfree(c->d_R); dfree(c->d_Rt);
-    dfree(c->d_patch_x); dfree(c->d_patch_y);
-    c->has_model = false;
-}
+// the model's arrays stay allocated for the next model, like every other buffer of the context
+void free_model(bmx_ctx *c) { c->has_model = false; }
 // sites / tests: the buffers stay allocated for the next chromosome; only the state is dropped
 void drop_tests(ChromSlot *s) {
     s->has_tests = false;
@@ -5848,12 +5849,6 @@ void drop_sites(ChromSlot *s) {
     drop_tests(s);        // test sites were located in the old site array
 }
 
-template <class T>
-int upload(T *&dst, const T *src, size_t n, hipStream_t s) {
-    HIP_TRY(hipMalloc((void **)&dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return BMX_OK;
-}
 template <class T>
 int upload(DevBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
     HIP_TRY(dst.ensure(n));
@@ -5902,7 +5897,7 @@ int64_t surfaces_step(const bmx_ctx *c, int nsl) {
 SurfsParams surfs_params(const bmx_ctx *c, const ChromSlot *s, int nsl) {
     SurfsParams S{};
     S.sites = site_view(s); S.win = window_view(c, s);
-    S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A; S.nA = c->nA;
+    S.Rt = c->d_Rt.p; S.NP = c->NP; S.npairs = c->npairs; S.nslices = nsl; S.A = c->d_A.p; S.nA = c->nA;
     return S;
 }
 // ... and everything bmx_ctx_surfaces, _cond_surfaces and _base_surfaces do with a list of n > 0 entries once their own refusals
@@ -5983,18 +5978,14 @@ int ensure_plan(bmx_ctx *c, ChromSlot *s);
 
 int select_slot(bmx_ctx *c, int slot) {
     if (slot < 0 || slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
-    if ((size_t)slot >= c->slots.size()) c->slots.resize((size_t)slot + 1, nullptr);
+    if ((size_t)slot >= c->slots.size()) c->slots.resize((size_t)slot + 1);
     if (!c->slots[(size_t)slot]) {
-        ChromSlot *s = new ChromSlot();
+        std::unique_ptr<ChromSlot> s(new ChromSlot());
         s->index = slot;
-        if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) {
-            s->release();
-            delete s;
-            return fail(BMX_E_HIP, "event creation failed");
-        }
-        c->slots[(size_t)slot] = s;
+        if (s->scan.create() != hipSuccess) return fail(BMX_E_HIP, "event creation failed");
+        c->slots[(size_t)slot] = std::move(s);
     }
-    c->cur = c->slots[(size_t)slot];
+    c->cur = c->slots[(size_t)slot].get();
     c->cur_index = slot;
     return BMX_OK;
 }
@@ -6096,7 +6087,7 @@ int derive_row_tables(bmx_ctx *c, ChromSlot *s, const std::vector<int64_t> &cnt,
 int source_slot(bmx_ctx *c, const char *who, int32_t src_slot, ChromSlot *&src) {
     if (src_slot < 0 || src_slot >= MAX_SLOTS) return fail(BMX_E_INVALID, "slot index out of range (0..4095)");
     if (src_slot == c->cur_index) return fail(BMX_E_INVALID, std::string(who) + ": the source slot must not be the selected slot");
-    src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot] : nullptr;
+    src = (size_t)src_slot < c->slots.size() ? c->slots[(size_t)src_slot].get() : nullptr;
     if (src && !src->has_sites) src = nullptr;
     return BMX_OK;
 }
@@ -6145,6 +6136,11 @@ int bmx_device_count(void) {
 
 double bmx_alpha_cut(void) { return compute_zcut(); }
 
+void bmx_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes) {
+    if (device_bytes) *device_bytes = g_device_bytes.load();
+    if (pinned_bytes) *pinned_bytes = g_pinned_bytes.load();
+}
+
 int bmx_ctx_create(bmx_ctx **out, int device) {
     if (!out) return fail(BMX_E_INVALID, "out is NULL");
     *out = nullptr;
@@ -6160,8 +6156,8 @@ int bmx_ctx_create(bmx_ctx **out, int device) {
     for (int k = 0; ok && k < 2; k++)
         ok = hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&c->ev_copied[k], hipEventDisableTiming) == hipSuccess;
-    if (ok) ok = hipMalloc((void **)&c->d_status, (1 + MAX_SLOTS) * sizeof(int)) == hipSuccess &&
-                 hipMemset(c->d_status, 0, (1 + MAX_SLOTS) * sizeof(int)) == hipSuccess;
+    if (ok) ok = c->d_status.ensure(1 + MAX_SLOTS) == hipSuccess &&
+                 hipMemset(c->d_status.p, 0, (1 + MAX_SLOTS) * sizeof(int)) == hipSuccess;
     if (ok) ok = select_slot(c, 0) == BMX_OK;
     if (!ok) {
         bmx_ctx_destroy(c);
@@ -6177,45 +6173,6 @@ void bmx_ctx_destroy(bmx_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    free_model(c);
-    for (ChromSlot *s : c->slots)
-        if (s) { s->release(); delete s; }
-    c->slots.clear();
-    c->part_T.release(); c->part_lin.release(); c->part_ns.release(); c->arena.release(); c->gap_sample.release();
-    c->surf_T.release(); c->surf_ns.release();
-    c->sfs_T.release(); c->sfs_ns.release(); c->sfs_list.release(); c->sfs_nsh.release(); c->sfs_tmax.release(); c->sfs_lin.release();
-    c->sfs.release();
-    c->if_rng1.release(); c->if_rng.release(); c->if_items.release(); c->if_tmax.release(); c->if_contrib.release();
-    c->if_L.release(); c->if_lin.release(); c->if_m.release(); c->if_blin.release();
-    c->ifl.release();
-    c->ft_gw.release(); c->ft_edges.release(); c->ft_ws.release(); c->ft_Es.release(); c->ft_En.release();
-    c->ft_lin.release(); c->ft_cls.release(); c->ft_O.release(); c->ft_skip.release();
-    c->ft.release();
-    c->cs_ctest.release(); c->cs_clin.release();
-    c->cs.release();
-    c->bs_out.release();
-    c->bs.release();
-    c->sw_list.release(); c->sw_cnt.release(); c->sw_pts.release(); c->sw_out.release(); c->sw_R.release();
-    c->sw.release();
-    c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
-    c->rf_flag.release(); c->rf_list.release(); c->rf_pns.release(); c->rf_pre.release();
-    c->rf_grid.release(); c->rf_pts.release(); c->rf_pT.release(); c->rf_slab.release();
-    c->bt_keys.release(); c->bt_pws.release();
-    c->pk_tmax.release(); c->pk_track.release(); c->pk_tfirst.release();
-    c->rs_tsum.release(); c->rs_cnt.release(); c->rs_tpre.release();
-    c->pw_centre.release(); c->pw_gw.release(); c->pw_first.release(); c->pw_count.release(); c->pw_changed.release();
-    c->fa_idx.release(); c->fa_clr.release(); c->fa_lin.release(); c->fa_ns.release();
-    c->pk.release();
-    c->pw.release();
-    dfree(c->d_prof);
-    dfree(c->d_status);
-    for (int k = 0; k < 2; k++) {
-        if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
-        if (c->ev_done[k]) (void)hipEventDestroy(c->ev_done[k]);
-        if (c->ev_copied[k]) (void)hipEventDestroy(c->ev_copied[k]);
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;
 }
 
@@ -6247,8 +6204,8 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_model(c);
-    for (ChromSlot *s : c->slots)
-        if (s) { drop_sites(s); s->lc_ok = false; }      // row indices and the moment slots belong to the model they were set under
+    for (const auto &s : c->slots)
+        if (s) { drop_sites(s.get()); s->lc_ok = false; }      // row indices and the moment slots belong to the model they were set under
     c->stat = m->stat; c->min_count = m->min_count; c->n_sizes = m->n_sizes;
     c->rows = m->row_off[m->n_sizes]; c->nx = m->nx; c->nab = m->nab; c->nA = nA;
     c->npairs = m->nx * m->nab;
@@ -6266,10 +6223,10 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
     c->h_x.assign(m->x, m->x + m->nx);
     c->h_ab.assign(m->abeta, m->abeta + m->nab);
     size_t tab = (size_t)c->npairs * c->rows;
-    HIP_TRY(hipMalloc((void **)&c->d_psel, tab * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->d_R, tab * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->d_Rt, (size_t)c->rows * c->NP * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(c->d_Rt, 0, (size_t)c->rows * c->NP * sizeof(double), c->stream));
+    HIP_TRY(c->d_psel.ensure(tab));
+    HIP_TRY(c->d_R.ensure(tab));
+    HIP_TRY(c->d_Rt.ensure((size_t)c->rows * c->NP));
+    HIP_TRY(hipMemsetAsync(c->d_Rt.p, 0, (size_t)c->rows * c->NP * sizeof(double), c->stream));
     // host-libm conformance patch (bmx_math.h): every argument that K1 takes a log of inside lgam's
     // Stirling branch, evaluated with this host's libm and with the device's correctly rounded log
     std::vector<uint64_t> px;
@@ -6314,11 +6271,11 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
         if ((rc = upload(c->d_patch_y, (const double *)py.data(), py.size(), c->stream))) return rc;
     }
     LutParams P;
-    P.patch = bmx::LogPatch{c->d_patch_x, c->d_patch_y, c->n_patch};
+    P.patch = bmx::LogPatch{c->d_patch_x.p, c->d_patch_y.p, c->n_patch};
     P.stat = c->stat; P.min_count = c->min_count; P.n_sizes = c->n_sizes; P.rows = c->rows;
     P.nx = c->nx; P.nab = c->nab; P.NP = c->NP;
-    P.sizes = c->d_sizes; P.row_off = c->d_row_off; P.g = c->d_g; P.prop = c->d_prop;
-    P.x = c->d_x; P.abeta = c->d_abeta; P.psel = c->d_psel; P.R = c->d_R; P.Rt = c->d_Rt;
+    P.sizes = c->d_sizes.p; P.row_off = c->d_row_off.p; P.g = c->d_g.p; P.prop = c->d_prop.p;
+    P.x = c->d_x.p; P.abeta = c->d_abeta.p; P.psel = c->d_psel.p; P.R = c->d_R.p; P.Rt = c->d_Rt.p;
     int threads = 128;
     int blocks = (int)((tab + threads - 1) / threads);
     TRACE("set_model: launching bb_lut_kernel, %d blocks x %d, rows=%d pairs=%d", blocks, threads, c->rows, c->npairs);
@@ -6327,7 +6284,7 @@ int bmx_ctx_set_model(bmx_ctx *c, const bmx_model *m, const double *A, int32_t n
     // How many sites may be multiplied between exponent extractions: every factor
     // 1 + alpha*R lies in [min(1, 1+Rmin), max(1, 1+Rmax)]; keep the product inside 2^+-1000.
     std::vector<double> hR(tab);
-    HIP_TRY(hipMemcpyAsync(hR.data(), c->d_R, tab * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hR.data(), c->d_R.p, tab * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     TRACE("set_model: table built");
     double fmax = 1.0, fmin = 1.0;
@@ -6476,9 +6433,9 @@ int64_t pl_bytes_per_test(const bmx_ctx *c, int which) {
 
 int plan_scan(bmx_ctx *c, ChromSlot *s, ScanPlan &pl) {
     ScanParams &P = pl.P;
-    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N; P.Rt = c->d_Rt;
+    P.genpos = s->genpos.p; P.row = s->row_array(); P.N = s->N; P.Rt = c->d_Rt.p;
     P.rows = c->rows; P.NP = c->NP; P.npairs = c->npairs; P.nslices = c->nslices;
-    P.A = c->d_A; P.nA = c->nA; P.zcut = c->zcut; P.renorm_every = c->renorm_every; P.span_hi = c->span_hi; P.rmax = c->rmax;
+    P.A = c->d_A.p; P.nA = c->nA; P.zcut = c->zcut; P.renorm_every = c->renorm_every; P.span_hi = c->span_hi; P.rmax = c->rmax;
     {
         // 8th order: economised coefficients, valid on [-0.05, 0.05] (FAR_W); lower orders: Taylor, cut at ~6e-15
         const double eps_default = FAR_ORDER >= 8 ? 0.05 : FAR_ORDER >= 6 ? 0.0105 : 0.0016;
@@ -6489,8 +6446,8 @@ int plan_scan(bmx_ctx *c, ChromSlot *s, ScanPlan &pl) {
         P.kmom = s->kmom.p;
         P.prof = nullptr;
 #if defined(BMX_PROFILE) || defined(BMX_COUNT)
-        if (!c->d_prof) { HIP_TRY(hipMalloc((void **)&c->d_prof, 32 * sizeof(unsigned long long))); HIP_TRY(hipMemset(c->d_prof, 0, 32 * sizeof(unsigned long long))); }
-        P.prof = c->d_prof;
+        if (!c->d_prof.p) { HIP_TRY(c->d_prof.ensure(32)); HIP_TRY(hipMemset(c->d_prof.p, 0, 32 * sizeof(unsigned long long))); }
+        P.prof = c->d_prof.p;
 #endif
         for (int k = 0; k < MOM_SLOTS; k++) P.row_of_slot[k] = s->row_of_slot[k];
         P.far_bits = (float)(eps * 1.4427 * 1.03);      // |log1p(x)| <= 1.027 |x| for |x| <= 0.05
@@ -6654,7 +6611,7 @@ PrepParams prep_params(bmx_ctx *c, ChromSlot *s, const ScanPlan &pl) {
     PrepParams Q;
     Q.genpos = s->genpos.p; Q.row = pl.P.row; Q.N = s->N;
     Q.rows = c->rows; Q.rowmul = pl.use_lds ? WAVE : c->NP;
-    Q.A = c->d_A; Q.nA = c->nA;
+    Q.A = c->d_A.p; Q.nA = c->nA;
     Q.test_gen = s->test_gen.p; Q.win_lo = s->win_lo.p; Q.win_hi = s->win_hi.p; Q.center = s->center.p; Q.center_hi = s->center_hi.p;
     Q.M = s->M; Q.zcut = c->zcut; Q.rmax = pl.P.rmax;
     Q.rowthr = s->rowthr.p; Q.thr_in_lds = pl.thr_in_lds;
@@ -6664,7 +6621,7 @@ PrepParams prep_params(bmx_ctx *c, ChromSlot *s, const ScanPlan &pl) {
     Q.ser_cap = !series ? 0 : diag_env("BMX_SER_CAP") ? std::min(std::max(atoi(diag_env("BMX_SER_CAP")), 0), SER_CAP) : SER_CAP;
     Q.g_begin = 0; Q.g_end = 0;
     Q.blob_units = s->blob_units.p; Q.blob_prefix = s->blob_prefix.p; Q.prefix_base = 0;
-    Q.arena = c->arena.p; Q.status = c->d_status;
+    Q.arena = c->arena.p; Q.status = c->d_status.p;
     return Q;
 }
 
@@ -6774,7 +6731,7 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
         if (pl.prep_lds) HIP_TRY(hipFuncSetAttribute(pl.prep_fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.prep_lds));
         HIP_TRY(hipLaunchKernel(pl.prep_fill, dim3((unsigned)((pr->ng + gpw - 1) / gpw)), dim3(pl.prep_threads), qargs, pl.prep_lds, c->stream));
         PrepView V;
-        V.arena = c->arena.p; V.blob_prefix = s->blob_prefix.p; V.prefix_base = pr->pbase; V.grp_base = pr->g0; V.status = c->d_status;
+        V.arena = c->arena.p; V.blob_prefix = s->blob_prefix.p; V.prefix_base = pr->pbase; V.grp_base = pr->g0; V.status = c->d_status.p;
         V.pl_am = (plw & BMX_PL_A) ? c->pl_am.p : nullptr; V.pl_ae = (plw & BMX_PL_A) ? c->pl_ae.p : nullptr;
         V.pl_pm = (plw & (BMX_PL_X | BMX_PL_ABETA)) ? c->pl_pm.p : nullptr; V.pl_pe = (plw & (BMX_PL_X | BMX_PL_ABETA)) ? c->pl_pe.p : nullptr;
         void *kargs[] = {&P, &V};
@@ -6786,10 +6743,10 @@ int launch_range(bmx_ctx *c, ChromSlot *s, ScanPlan &pl, int64_t off, int64_t cn
     FinalParams F;
     F.part_T = c->part_T.p; F.part_lin = c->part_lin.p; F.part_ns = c->part_ns.p;
     F.nslices = c->nslices; F.npairs = c->npairs; F.M = cnt; F.N = s->N;
-    F.genpos = s->genpos.p; F.A = c->d_A; F.test_gen = P.test_gen; F.win_lo = P.win_lo; F.win_hi = P.win_hi;
+    F.genpos = s->genpos.p; F.A = c->d_A.p; F.test_gen = P.test_gen; F.win_lo = P.win_lo; F.win_hi = P.win_hi;
     F.center = P.center; F.center_hi = P.center_hi; F.zcut = c->zcut;
     F.clr = s->clr.p + off; F.lin = s->lin.p + off; F.nsites = s->nsites.p + off; F.rec = s->rec.p + off;
-    F.over = c->d_status + 1 + s->index;
+    F.over = c->d_status.p + 1 + s->index;
     const int fthreads = 256;
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((cnt + fthreads - 1) / fthreads)), dim3(fthreads), 0, c->stream, F);
     HIP_TRY(hipGetLastError());
@@ -6835,7 +6792,7 @@ int scan_ranges(bmx_ctx *c, ChromSlot *s, std::vector<PrepRange> &out) {
 
 // before the launches of a scan of slot s: its range word starts at 0
 int begin_range_word(bmx_ctx *c, ChromSlot *s) {
-    HIP_TRY(hipMemsetAsync(c->d_status + 1 + s->index, 0, sizeof(int), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_status.p + 1 + s->index, 0, sizeof(int), c->stream));
     return BMX_OK;
 }
 
@@ -6844,13 +6801,13 @@ int begin_range_word(bmx_ctx *c, ChromSlot *s) {
 // the exponent clamp is BMX_E_LIMIT every time, until that slot is scanned again
 int check_status(bmx_ctx *c, const ChromSlot *s) {
     std::vector<int> st(1 + c->slots.size(), 0);
-    HIP_TRY(hipMemcpy(st.data(), c->d_status, st.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st.data(), c->d_status.p, st.size() * sizeof(int), hipMemcpyDeviceToHost));
     if (st[0]) {
-        HIP_TRY(hipMemset(c->d_status, 0, sizeof(int)));
+        HIP_TRY(hipMemset(c->d_status.p, 0, sizeof(int)));
         return fail(BMX_E_HIP, st[0] & 1 ? "prepared scan: a group's stream differs in size from the counting pass" : "prepared scan: bad zone header in a group's stream");
     }
     for (size_t i = 0; i < c->slots.size(); i++) {
-        const ChromSlot *q = c->slots[i];
+        const ChromSlot *q = c->slots[i].get();
         if (q && (!s || s == q) && q->has_results() && st[1 + i])
             return fail(BMX_E_LIMIT, "scan: a window of slot " + std::to_string(i) + " has a CLR past the scan's range (|T| <= 2 ln 2 x 131070 = 1.817e5 per "
                                      "grid point): the slot's results are withheld until it is scanned again with narrower windows");
@@ -6872,10 +6829,10 @@ int bmx_ctx_scan(bmx_ctx *c) {
     if (rc) return rc;
     if ((rc = begin_profiles(c, s))) return rc;
     if ((rc = begin_range_word(c, s))) return rc;
-    HIP_TRY(hipEventRecord(s->ev0, c->stream));
+    HIP_TRY(s->scan.begin(c->stream));
     for (const PrepRange &r : rs)
         if ((rc = launch_range(c, s, s->plan, r.off, r.cnt, s->plan.mode >= 4 ? &r : nullptr))) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, c->stream));
+    HIP_TRY(s->scan.end(c->stream));
     s->timed = true;
     s->pl_have = c->pl_which;
     s->scan_seq++;
@@ -6921,10 +6878,10 @@ int bmx_ctx_sync(bmx_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
 #if defined(BMX_PROFILE) || defined(BMX_COUNT)
-    if (c->d_prof) {
+    if (c->d_prof.p) {
         unsigned long long h[32];
-        HIP_TRY(hipMemcpy(h, c->d_prof, sizeof h, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(c->d_prof, 0, sizeof h));
+        HIP_TRY(hipMemcpy(h, c->d_prof.p, sizeof h, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(c->d_prof.p, 0, sizeof h));
 #ifdef BMX_COUNT
         static const char *cn[16] = {"bulk passes with sites", "passes with a near list", "quad blocks", "pair blocks", "near-list sites",
                                      "far (moment) sites", "generic passes with sites", "generic passes", "zones folded/flushed",
@@ -6953,14 +6910,14 @@ int bmx_ctx_pack_records(bmx_ctx *c, void *dst, int64_t cap, int32_t dst_on_devi
     if (!c || (!dst && cap > 0)) return fail(BMX_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     int64_t n = 0;
-    for (ChromSlot *s : c->slots)
+    for (const auto &s : c->slots)
         if (s && s->has_results()) n += s->M;
     if (n_out) *n_out = n;
     if (n > cap) return fail(BMX_E_INVALID, "pack_records: destination too small");
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int st = check_status(c, nullptr)) return st;        // before anything is copied: the destination may be another device's input
     int64_t at = 0;
-    for (ChromSlot *s : c->slots) {
+    for (const auto &s : c->slots) {
         if (!s || !s->has_results()) continue;
         HIP_TRY(hipMemcpyAsync((bmx_record *)dst + at, s->rec.p, (size_t)s->M * sizeof(bmx_record),
                                dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
@@ -6987,10 +6944,9 @@ int bmx_ctx_last_scan_ms(bmx_ctx *c, double *ms) {
     if (!c || !ms) return fail(BMX_E_INVALID, "NULL argument");
     ChromSlot *s = c->cur;
     if (!s->timed) return fail(BMX_E_STATE, "no scan has been launched");
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    float f = 0;
-    HIP_TRY(hipEventElapsedTime(&f, s->ev0, s->ev1));
-    *ms = f;
+    HIP_TRY(hipEventSynchronize(s->scan.ev1));
+    HIP_TRY(s->scan.read());
+    *ms = s->scan.ms;
     return BMX_OK;
 }
 
@@ -7063,7 +7019,7 @@ int bmx_ctx_set_profiles(bmx_ctx *c, int32_t which) {
     c->pl_which = which;
     if (!which) {       // off: nothing of the profiles stays on the device
         c->pl_am.release(); c->pl_ae.release(); c->pl_pm.release(); c->pl_pe.release();
-        for (ChromSlot *s : c->slots) {
+        for (const auto &s : c->slots) {
             if (!s) continue;
             s->pl_have = 0;
             for (auto &b : s->pl_out) b.release();
@@ -7194,8 +7150,8 @@ int bmx_ctx_fetch_lut(bmx_ctx *c, double *psel_out, double *R_out) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t tab = (size_t)c->npairs * c->rows;
-    HIP_TRY(download(psel_out, c->d_psel, tab));
-    HIP_TRY(download(R_out, c->d_R, tab));
+    HIP_TRY(download(psel_out, c->d_psel.p, tab));
+    HIP_TRY(download(R_out, c->d_R.p, tab));
     return BMX_OK;
 }
 
@@ -7205,8 +7161,8 @@ int bmx_ctx_surface(bmx_ctx *c, double test_gen, int64_t win_lo, int64_t win_hi,
     if (!c->has_model || !s->has_sites) return fail(BMX_E_STATE, "model and sites must be set before surface");
     HIP_TRY(hipSetDevice(c->device));
     SurfParams S;
-    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N; S.Rt = c->d_Rt; S.NP = c->NP; S.npairs = c->npairs;
-    S.nslices = c->nslices; S.A = c->d_A; S.nA = c->nA; S.tg = test_gen;
+    S.genpos = s->genpos.p; S.row = s->row_array(); S.N = s->N; S.Rt = c->d_Rt.p; S.NP = c->NP; S.npairs = c->npairs;
+    S.nslices = c->nslices; S.A = c->d_A.p; S.nA = c->nA; S.tg = test_gen;
     S.lo = std::max<int64_t>(win_lo, 0); S.hi = std::min<int64_t>(win_hi, s->N - 1); S.zcut = c->zcut;
     HIP_TRY(c->surf_T.ensure((size_t)c->nA * c->npairs));
     HIP_TRY(c->surf_ns.ensure((size_t)c->nA));
@@ -7263,7 +7219,7 @@ int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block
     const int wpb = INFL_THREADS / WAVE;
     for (int64_t q0 = 0; q0 < n; q0 += rstep) {
         const int64_t m = std::min(rstep, n - q0);
-        Q.A = c->d_A + iAmin; Q.nA = 1; Q.tests = c->sfs_list.p + q0; Q.n = m; Q.rng = c->if_rng1.p;
+        Q.A = c->d_A.p + iAmin; Q.nA = 1; Q.tests = c->sfs_list.p + q0; Q.n = m; Q.rng = c->if_rng1.p;
         hipLaunchKernelGGL(influence_range_kernel, dim3((unsigned)((m + wpb - 1) / wpb)), dim3(INFL_THREADS), 0, c->stream, Q);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_rng.data() + (size_t)q0 * 4, c->if_rng1.p, (size_t)m * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -7286,8 +7242,8 @@ int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block
     const int64_t INFL_CHUNK_BLOCKS = 1 << 22;
     SurfsParams S = surfs_params(c, s, nsl);
     InflParams P;
-    P.sites = Q.sites; P.win = Q.win; P.Rt = c->d_Rt; P.NP = c->NP; P.npairs = c->npairs; P.nslices = nsl;
-    P.A = c->d_A; P.nA = c->nA; P.iAmin = iAmin; P.B = B;
+    P.sites = Q.sites; P.win = Q.win; P.Rt = c->d_Rt.p; P.NP = c->NP; P.npairs = c->npairs; P.nslices = nsl;
+    P.A = c->d_A.p; P.nA = c->nA; P.iAmin = iAmin; P.B = B;
     std::vector<InflItem> items;
     std::vector<int32_t> h_ns;
     double total_ms = 0.0;
@@ -7314,7 +7270,7 @@ int bmx_ctx_influence(bmx_ctx *c, int64_t n, const int32_t *tests, int64_t block
         if (!items.empty())
             HIP_TRY(hipMemcpyAsync(c->if_items.p, items.data(), items.size() * sizeof(InflItem), hipMemcpyHostToDevice, c->stream));
         S.tests = c->sfs_list.p + q0; S.T = c->sfs_T.p; S.ns = c->sfs_ns.p;
-        Q.A = c->d_A; Q.nA = c->nA; Q.tests = S.tests; Q.n = m; Q.rng = c->if_rng.p;
+        Q.A = c->d_A.p; Q.nA = c->nA; Q.tests = S.tests; Q.n = m; Q.rng = c->if_rng.p;
         P.tests = S.tests; P.T = c->sfs_T.p; P.ns = c->sfs_ns.p; P.rng = c->if_rng.p; P.lin = c->if_lin.p; P.items = c->if_items.p;
         P.m_out = c->if_m.p; P.contrib = c->if_contrib.p; P.L = c->if_L.p; P.blin = c->if_blin.p;
         HIP_TRY(c->ifl.begin(c->stream));
@@ -7420,8 +7376,8 @@ int bmx_ctx_fit(bmx_ctx *c, int64_t n, const int32_t *tests, const int32_t *lin,
     if (!in_lds) HIP_TRY(c->ft_ws.ensure((size_t)step * tab));
     FitParams P;
     P.sites = site_view(s); P.win = window_view(c, s);
-    P.R = c->d_R; P.rows = c->rows; P.npairs = c->npairs; P.A = c->d_A;
-    P.row_off = c->d_row_off; P.n_sizes = c->n_sizes;
+    P.R = c->d_R.p; P.rows = c->rows; P.npairs = c->npairs; P.A = c->d_A.p;
+    P.row_off = c->d_row_off.p; P.n_sizes = c->n_sizes;
     P.gw = c->ft_gw.p; P.cls = c->ft_cls.p; P.F = F; P.edges = c->ft_edges.p; P.D = D;
     P.ws = in_lds ? nullptr : c->ft_ws.p;
     P.O = c->ft_O.p; P.Esel = c->ft_Es.p; P.Eneu = c->ft_En.p; P.skipped = c->ft_skip.p;
@@ -7509,7 +7465,7 @@ int bmx_ctx_baseline_add(bmx_ctx *c, int32_t test, int32_t lin, int64_t *first, 
     HIP_TRY(c->bs_out.ensure(3));
     BaseAddParams P;
     P.sites = site_view(s); P.win = window_view(c, s);
-    P.Rt = c->d_Rt; P.NP = c->NP;
+    P.Rt = c->d_Rt.p; P.NP = c->NP;
     P.t = test; P.A = c->h_A[(size_t)(lin / c->npairs)]; P.p = lin % c->npairs;
     P.d = s->bl_d.p; P.cnt = s->bl_cnt.p; P.out = c->bs_out.p;
     const int64_t grid = std::min<int64_t>(std::max<int64_t>((s->N + SURFS_THREADS - 1) / SURFS_THREADS, 1), BASE_ADD_GRID_MAX);
@@ -7592,8 +7548,8 @@ int refine_setup(bmx_ctx *c, ChromSlot *s, RefineParams &P, int max_rounds) {
     const double *d = c->rf_grid.p;
     P.cu = d; P.cv = d + nA; P.h0u = d + nA + nab; P.h0x = d + 2 * nA + nab; P.h0v = d + 2 * nA + nab + nx;
     P.stat = c->stat; P.min_count = c->min_count; P.n_sizes = c->n_sizes; P.rows = c->rows;
-    P.sizes = c->d_sizes; P.row_off = c->d_row_off; P.g = c->d_g; P.prop = c->d_prop;
-    P.gA = c->d_A; P.gx = c->d_x; P.gab = c->d_abeta; P.npairs = c->npairs; P.nab = nab;
+    P.sizes = c->d_sizes.p; P.row_off = c->d_row_off.p; P.g = c->d_g.p; P.prop = c->d_prop.p;
+    P.gA = c->d_A.p; P.gx = c->d_x.p; P.gab = c->d_abeta.p; P.npairs = c->npairs; P.nab = nab;
     P.max_rounds = max_rounds;
     P.sites = site_view(s); P.win = window_view(c, s);
     P.M = s->M;
@@ -7696,7 +7652,7 @@ int bmx_ctx_refine(bmx_ctx *c, double min_clr) {
     RefineInitParams Q;
     Q.clr = s->clr.p; Q.lin = s->lin.p; Q.nsites = s->nsites.p;
     Q.apex = c->rf_at_peaks ? s->pk_flag.p : nullptr;
-    Q.gA = c->d_A; Q.gx = c->d_x; Q.gab = c->d_abeta; Q.npairs = c->npairs; Q.nab = c->nab;
+    Q.gA = c->d_A.p; Q.gx = c->d_x.p; Q.gab = c->d_abeta.p; Q.npairs = c->npairs; Q.nab = c->nab;
     Q.M = M; Q.min_clr = min_clr; Q.flag = c->rf_flag.p;
     Q.o_clr = s->rf_clr.p; Q.o_A = s->rf_A.p; Q.o_x = s->rf_x.p; Q.o_ab = s->rf_ab.p; Q.o_ns = s->rf_ns.p; Q.o_rounds = s->rf_rounds.p;
     hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, Q);
@@ -8217,8 +8173,8 @@ int bmx_ctx_plant_sites(bmx_ctx *c, int32_t src_slot, uint64_t key, int32_t K, c
             Q.centre = c->pw_centre.p; Q.first = c->pw_first.p; Q.count = c->pw_count.p; Q.K = K;
             Q.A = A; Q.zcut = c->zcut;
             Q.gw = c->pw_gw.p;
-            Q.R = c->d_R + ((size_t)ix * c->nab + ia) * (size_t)c->rows;
-            Q.row_off = c->d_row_off; Q.n_sizes = c->n_sizes; Q.rows = c->rows;
+            Q.R = c->d_R.p + ((size_t)ix * c->nab + ia) * (size_t)c->rows;
+            Q.row_off = c->d_row_off.p; Q.n_sizes = c->n_sizes; Q.rows = c->rows;
             Q.changed = c->pw_changed.p;
             const bool in_lds = (size_t)c->rows * 16 <= (size_t)PLANT_LDS_BYTES;
             const size_t lds = in_lds ? (size_t)c->rows * 16 : 0;
@@ -8509,8 +8465,6 @@ void bmx_comm_destroy(bmx_comm *cm) {
     (void)hipSetDevice(cm->ctx->device);
     RcclApi *api = rccl_api();
     if (cm->comm && api->CommDestroy) (void)api->CommDestroy(cm->comm);
-    cm->send.release();
-    cm->recv.release();
     delete cm;
 }
 
@@ -8607,15 +8561,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
     int64_t chunk_max = 1;
     for (const PrepRange &q : chunks) chunk_max = std::max(chunk_max, q.cnt);
     const size_t slot_bytes = (size_t)chunk_max * 16;
-    if (c->h_stage_cap < slot_bytes) {
-        for (int k = 0; k < 2; k++) {
-            if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
-            c->h_stage[k] = nullptr;
-        }
-        c->h_stage_cap = 0;
-        for (int k = 0; k < 2; k++) HIP_TRY(hipHostMalloc(&c->h_stage[k], slot_bytes, hipHostMallocDefault));
-        c->h_stage_cap = slot_bytes;
-    }
+    for (PinnedBuf &h : c->h_stage) HIP_TRY(h.ensure(slot_bytes));
     bmx_row_tables_ *tabs = bmx_row_tables_new_(xs, nx, abs_, nab, As, nA);
     FILE *f = fopen(path, "a");
     if (!f) {
@@ -8644,7 +8590,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
             std::string msg;
             if (hipEventSynchronize(c->ev_copied[j.slot]) != hipSuccess) e = 1;
             if (!e && !werr) {
-                const char *base = (const char *)c->h_stage[j.slot];
+                const char *base = c->h_stage[j.slot].p;
                 const double *hclr = (const double *)base;
                 const int32_t *hlin = (const int32_t *)(base + (size_t)chunk_max * 8);
                 const int32_t *hns = (const int32_t *)(base + (size_t)chunk_max * 12);
@@ -8687,7 +8633,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
         hipError_t e_ = (expr);                                                                           \
         if (e_ != hipSuccess) return finish(BMX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
-    STREAM_TRY(hipEventRecord(s->ev0, c->stream));
+    STREAM_TRY(s->scan.begin(c->stream));
     size_t k = 0;
     bool stopped = false;
     for (; k < chunks.size(); ++k) {
@@ -8708,7 +8654,7 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
         } else if ((rc = launch_range(c, s, pl, q.off, q.cnt, nullptr))) return finish(rc, g_err);
         STREAM_TRY(hipEventRecord(c->ev_done[slot], c->stream));
         STREAM_TRY(hipStreamWaitEvent(c->copy_stream, c->ev_done[slot], 0));
-        char *base = (char *)c->h_stage[slot];
+        char *base = c->h_stage[slot].p;
         STREAM_TRY(hipMemcpyAsync(base, s->clr.p + q.off, (size_t)q.cnt * 8, hipMemcpyDeviceToHost, c->copy_stream));
         STREAM_TRY(hipMemcpyAsync(base + (size_t)chunk_max * 8, s->lin.p + q.off, (size_t)q.cnt * 4, hipMemcpyDeviceToHost, c->copy_stream));
         STREAM_TRY(hipMemcpyAsync(base + (size_t)chunk_max * 12, s->nsites.p + q.off, (size_t)q.cnt * 4, hipMemcpyDeviceToHost, c->copy_stream));
@@ -8719,24 +8665,32 @@ extern "C" int bmx_ctx_scan_write(bmx_ctx *c, const char *path, const int64_t *p
         }
         cv.notify_all();
     }
-    STREAM_TRY(hipEventRecord(s->ev1, c->stream));
+    STREAM_TRY(s->scan.end(c->stream));
 #undef STREAM_TRY
     all_launched = !stopped;
     return finish(BMX_OK, "");
 }
 
+namespace {
+// The context of a one-shot entry point: destroyed at the end of the call, with the thread's error text as the call left it
+struct OneShotCtx {
+    bmx_ctx *c = nullptr;
+    ~OneShotCtx() {
+        const std::string keep = g_err;
+        bmx_ctx_destroy(c);
+        g_err = keep;
+    }
+};
+}  // namespace
+
 extern "C" {
 
 int bmx_lut_build(const bmx_model *m, double *psel_out, double *R_out, int device) {
-    bmx_ctx *c = nullptr;
-    int rc = bmx_ctx_create(&c, device);
-    if (rc) return rc;
+    OneShotCtx own;
+    int rc = bmx_ctx_create(&own.c, device);
     const double A1 = 1.0;
-    rc = bmx_ctx_set_model(c, m, &A1, 1);
-    if (!rc) rc = bmx_ctx_fetch_lut(c, psel_out, R_out);
-    std::string keep = g_err;
-    bmx_ctx_destroy(c);
-    g_err = keep;
+    if (!rc) rc = bmx_ctx_set_model(own.c, m, &A1, 1);
+    if (!rc) rc = bmx_ctx_fetch_lut(own.c, psel_out, R_out);
     return rc;
 }
 
@@ -8744,17 +8698,13 @@ int bmx_scan(const bmx_model *m, const double *A, int32_t nA, int64_t N, const d
              const int32_t *row, int64_t M, const double *test_gen, const int64_t *win_lo,
              const int64_t *win_hi, double *clr, int32_t *ix, int32_t *ia, int32_t *iA,
              int32_t *nsites, int device) {
-    bmx_ctx *c = nullptr;
-    int rc = bmx_ctx_create(&c, device);
-    if (rc) return rc;
-    rc = bmx_ctx_set_model(c, m, A, nA);
-    if (!rc) rc = bmx_ctx_set_sites(c, N, genpos, row);
-    if (!rc) rc = bmx_ctx_set_tests(c, M, test_gen, win_lo, win_hi);
-    if (!rc) rc = bmx_ctx_scan(c);
-    if (!rc) rc = bmx_ctx_fetch(c, clr, ix, ia, iA, nsites);
-    std::string keep = g_err;
-    bmx_ctx_destroy(c);
-    g_err = keep;
+    OneShotCtx own;
+    int rc = bmx_ctx_create(&own.c, device);
+    if (!rc) rc = bmx_ctx_set_model(own.c, m, A, nA);
+    if (!rc) rc = bmx_ctx_set_sites(own.c, N, genpos, row);
+    if (!rc) rc = bmx_ctx_set_tests(own.c, M, test_gen, win_lo, win_hi);
+    if (!rc) rc = bmx_ctx_scan(own.c);
+    if (!rc) rc = bmx_ctx_fetch(own.c, clr, ix, ia, iA, nsites);
     return rc;
 }
 
@@ -8784,15 +8734,14 @@ int bmx_scan_multi(const bmx_model *m, const double *A, int32_t nA, int64_t N, c
         std::vector<int64_t> lo(n), hi(n);
         std::vector<int32_t> x_(n), a_(n), A_(n), ns_(n);
         for (size_t i = 0; i < n; ++i) { tg[i] = test_gen[idx[i]]; lo[i] = win_lo[idx[i]]; hi[i] = win_hi[idx[i]]; }
-        bmx_ctx *c = nullptr;
-        int rc = bmx_ctx_create(&c, devices ? devices[w] : w);
-        if (!rc) rc = bmx_ctx_set_model(c, m, A, nA);
-        if (!rc) rc = bmx_ctx_set_sites(c, N, genpos, row);
-        if (!rc) rc = bmx_ctx_set_tests(c, (int64_t)n, tg.data(), lo.data(), hi.data());
-        if (!rc) rc = bmx_ctx_scan(c);
-        if (!rc) rc = bmx_ctx_fetch(c, c_.data(), x_.data(), a_.data(), A_.data(), ns_.data());
+        OneShotCtx own;
+        int rc = bmx_ctx_create(&own.c, devices ? devices[w] : w);
+        if (!rc) rc = bmx_ctx_set_model(own.c, m, A, nA);
+        if (!rc) rc = bmx_ctx_set_sites(own.c, N, genpos, row);
+        if (!rc) rc = bmx_ctx_set_tests(own.c, (int64_t)n, tg.data(), lo.data(), hi.data());
+        if (!rc) rc = bmx_ctx_scan(own.c);
+        if (!rc) rc = bmx_ctx_fetch(own.c, c_.data(), x_.data(), a_.data(), A_.data(), ns_.data());
         if (rc) msgs[(size_t)w] = bmx_last_error();          // this thread's message
-        bmx_ctx_destroy(c);
         rcs[(size_t)w] = rc;
         if (rc) return;
         for (size_t i = 0; i < n; ++i) {

@@ -27,6 +27,14 @@ def stat_name(nofreq, MAF, nosub):
     return 'B0' if nosub else 'B2'
 
 
+def live_bytes():
+    """(device, pinned): the bytes of device and of pinned host memory that the library's contexts of this process hold now
+    (bmx_live_bytes)."""
+    dev, pin = C.c_int64(), C.c_int64()
+    _lib.lib().bmx_live_bytes(C.byref(dev), C.byref(pin))
+    return dev.value, pin.value
+
+
 class ModelArrays:
     """The bmx_model struct plus the numpy arrays that back its pointers."""
 

@@ -87,6 +87,11 @@ int bmx_device_count(void);
 /* The window cut-off in the exponent domain: largest double z with exp(-z) >= 1e-8, so that the
  * reference's predicate `np.exp(-A*dist) >= 1e-8` (BalLeRMix+_v1.py:454-455) is `A*dist <= z`. */
 double bmx_alpha_cut(void);
+/* Diagnostic: the bytes of device memory and of pinned host memory that the contexts and communicators of this process hold
+ * right now, summed over all of them and all devices.  Every allocation of the library is counted, at the size asked for;
+ * what the runtime itself or other libraries hold is not.  After the last context is destroyed both are what they were
+ * before the first was created.  Either pointer may be NULL; takes no context and never fails. */
+void bmx_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
 
 /* ---- one-shot entry points (host buffers in, host buffers out) ---------------------- */
 

@@ -777,12 +777,15 @@ def _anchor_points(ops):
 def _run_script(name, tmp_path):
     ops = lt.scripts()[name]
     anchors = _anchor_points(ops)
+    from ballermixplus_amd import engine
+    held = engine.live_bytes()
     run = Runner(tmp_path)
     t0 = time.perf_counter()
     try:
         run.run(ops, anchors)
     finally:
         run.close()
+    assert engine.live_bytes() == held       # the closed context, and every clean room, gave back all it had allocated
     dt = time.perf_counter() - t0
     print('%s: %d ops in %.2f s (%.2f s in the clean rooms, %.2f s in the oracle); %d clean rooms; compared per group %s; refused %s; %d re-fetches of another slot; plans %s; 4-byte-row scans %d'
           % (name, len(ops), dt, run.t_rooms, run.t_anchors, run.rooms, dict(run.compared), {lt.CODE_NAMES[c]: n for c, n in run.refused.items()}, run.refetched,

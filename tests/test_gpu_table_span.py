@@ -297,6 +297,7 @@ def test_limit_and_recovery(open_ctx):
     """A table placed at 2^241.5 is refused by set_model with the limit error, and the context takes a span-240 model next and
     scans it like any other."""
     from ballermixplus_amd import _lib, engine as eng
+    held = eng.live_bytes()
     kind = 'rare'
     gen, k, nn = _sites(kind)
     spect, props = tb.spectrum(kind, tb.SPAN_LIMIT + 2, _sel_max(kind), k, nn)         # log2(1 + max R) = 241.5
@@ -317,6 +318,7 @@ def test_limit_and_recovery(open_ctx):
         _check(_scan(ctx, kind, idx), _oracle(kind, tb.SPAN_LIMIT, tb.A_LIST, idx, R), 'span 240 after a refused model')
     finally:
         ctx.close()
+    assert eng.live_bytes() == held          # what the refused set_model had allocated went with the context
 
 
 @pytest.mark.parametrize('stride', (1, 20))
